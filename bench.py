@@ -1,7 +1,8 @@
 """bench.py — the contract benchmark: Gramian MVMs/s for the dense EQ kernel, n = 131072, d = 3, fp32
 (BASELINE.json metric / configs[1]) on N GPUs of one node.
 
-    python3 bench.py [--gpus N] [--steps K] [--warmup W]          (run it as `python3 bench.py`, also after `rocprofv3 ... --`:
+    python3 bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                                                                    (run it as `python3 bench.py`, also after `rocprofv3 ... --`:
                                                                      the file has no shebang, so nothing re-execs)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
@@ -14,9 +15,13 @@ One "step" = one full MVM b = G a with the points, a and b resident in HBM.  The
 symmetry NOT exploited — all n*m entries are evaluated (general matrix-core kernel); for N > 1 the rows of G are sharded over
 the ranks and ONE RCCL all-gather completes b on every rank (covgram.dist); n stays 131072, so scaling is "strong".
 gramian(EQ, x) is symmetric, and by default the library evaluates its upper triangle once (on N GPUs: the cyclic 256-row panels
-p % N == rank + ONE all-reduce): that path is timed after the contract run, same protocol, and reported as "symmetric_variant".
+p % N == rank + ONE all-reduce): with --full that path is timed after the contract run, same protocol, and reported as "symmetric_variant".
 
-Rank 0 prints one JSON line.  Besides the contract fields it carries
+A plain run sets up, warms up, times EXACTLY K steps and prints one JSON line (rank 0) with the contract fields: `value` (MVM/s) and
+`ms_per_step` from the wall clock of the K steps, per-step event statistics, the config.  `--dump-outputs DIR` writes b of the last
+timed step to DIR/b.npy; the inputs are seeded, so two builds can be compared output for output.  Everything else is behind `--full`:
+the parity spot check against the fp64 oracle, "symmetric_variant", "direct_difference_variant", "incl_h2d_d2h", the per-rank split
+and single-GPU time (N > 1), and the fields below.  With --full the line also carries
   roofline      the dominant kernel (the library reports which one ran) priced against the FP32 vector peak it is actually bound by
                 (the path is VALU/transcendental-bound; the HBM figures BASELINE.json's metric name asks
                 for are reported alongside as hbm_*), duration measured live with HIP events on the launch stream;
@@ -131,6 +136,38 @@ def _event_loop(fn, steps):
 def _stats(ms):
     v = sorted(ms)
     return {"ms_median": v[len(v) // 2], "ms_min": v[0], "ms_max": v[-1], "steps": len(v)}
+
+
+def headline(args, world, rehearsal, elapsed, step_ms, sym_path):
+    """The contract fields of the result line from the K timed steps: all a plain run prints, and the head of the --full line."""
+    n, m, d = N_POINTS, N_POINTS, DIM
+    mvms = args.steps / elapsed
+    step_stats = _stats(step_ms)
+    line = {
+        "metric": "Gramian MVMs/sec, dense EQ kernel, n=131072, d=3, fp32 (+ achieved HBM GB/s in roofline.hbm_*)",
+        "value": mvms, "unit": "MVM/s", "n_gpus": world, "rccl_ranks": world if (dist.is_initialized() and not rehearsal) else 0, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "ms_median": step_stats["ms_median"], "ms_min": step_stats["ms_min"], "ms_max": step_stats["ms_max"],
+        "timing_note": "value / ms_per_step: wall clock over the K steps between barrier + synchronize (the contract); ms_median / ms_min: one HIP event pair "
+                       "per step on the launch stream, same K steps",
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "EQ dense Gramian mul!, d=3 n=131072 fp32 (BASELINE.json configs[1]); x ~ N(0, I_3), a ~ N(0,1), "
+                               "alpha=1, beta=0, y == x" + ("; the upper triangle is evaluated once" if sym_path else "; all n*m entries evaluated") + "; points/a/b resident in HBM",
+                   "n": n, "d": d, "kernel": "EQ", "pairs_per_mvm": float(n) * m,
+                   "parallelism": "1 GPU" if world == 1 else (
+                       f"upper triangle by cyclic 256-row panels x{world} + 1 RCCL all-reduce of b per MVM" if sym_path
+                       else f"row-shard x{world} + 1 RCCL all-gather of b per MVM")},
+        "pairs_per_s": mvms * float(n) * m,
+    }
+    if rehearsal:
+        line["rehearsal"] = "COVGRAM_BENCH_REHEARSAL=1: all ranks on GPU 0, collectives over gloo through host memory — a code-path rehearsal, NOT a measurement"
+    return line
+
+
+def dump_outputs(out_dir, b):
+    """--dump-outputs: what a caller of the timed path receives, b = G a (n = 131072 fp32, 512 KiB), as out_dir/b.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "b.npy"), b.cpu().numpy().astype(np.float32))
 
 
 def _timed(fn, warm=5, reps=20, after_warm=None, warm_s=0.25):
@@ -393,13 +430,18 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the C1 / C3 / C4 / C5 block (N = 1)")
+    ap.add_argument("--full", action="store_true", help="after the headline run, everything else the benchmark measures and checks: CPU baseline, "
+                    "symmetric and direct-difference variants, transfers, parity spot check, roofline, per-rank split, C1 / C3 / C4 / C5 configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write b of the last timed step to DIR/b.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the C1 / C3 / C4 / C5 block (N = 1)")
     ap.add_argument("--dry-launch", action="store_true", help="start the --gpus N ranks over gloo, one all-gather, no GPU work (CPU-tier launch check)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.dry_launch):
         sys.exit(launch_ranks(args, sys.argv[1:]))
     if int(os.environ.get("WORLD_SIZE", "1")) != args.gpus:
@@ -427,7 +469,7 @@ def main():
 
     # the CPU baseline first: no GPU call has been made yet (torch.cuda is not initialised until set_device below)
     cpu_line = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         try:
             cpu_line = cpu_baseline(Xh, ah)
         except Exception as e:   # the baseline is reporting only; never fail the GPU measurement for it
@@ -497,6 +539,26 @@ def main():
     step_ms = [e0.elapsed_time(e1) for e0, e1 in step_ev]
     kernel_ms, launches = cg.kernel_time()
     cg.set_option("time_kernels", 0)
+    dense_path = cg.get_info("last_dense_path")
+    sym_path = cg.get_info("last_mfma_sym") == 1
+    f16_split = dense_path == 2 and cg.get_info("last_mfma_f16") == 1      # the matrix-core EQ kernels' fp16 two-way split of the coordinates (round 4)
+    mfma_inst = cg.get_info("last_mfma_instance")                          # template arguments of the kernel the timed steps launched
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, b)                    # the last timed step's b, before any later launch reuses the buffer
+
+    if not args.full:
+        # a plain run ends here: the headline line and nothing that its figure does not need
+        if world > 1:
+            t = torch.tensor([elapsed], dtype=torch.float64, device=sdev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)           # the slowest rank's wall clock, as in the --full line
+            elapsed = float(t[0])
+        if rank == 0:
+            os.write(json_fd, (json.dumps(headline(args, world, rehearsal, elapsed, step_ms, sym_path)) + "\n").encode())
+        if dist.is_initialized():
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     # where a step's time goes — AFTER the timed region, diagnostic: events around the local kernel and around the one collective, for the
     # route the timed steps took (C ABI: the library's own ncclAllGather on its stream) and for torch.distributed's (its own stream + two event hops)
     loc_ms, col_ms, nsplit, col_by_route = 0.0, 0.0, 0, None
@@ -526,10 +588,6 @@ def main():
                 del Gt, bt
             finally:
                 os.environ.pop("COVGRAM_ABI_COLLECTIVE", None)
-    dense_path = cg.get_info("last_dense_path")
-    sym_path = cg.get_info("last_mfma_sym") == 1
-    f16_split = dense_path == 2 and cg.get_info("last_mfma_f16") == 1      # the matrix-core EQ kernels' fp16 two-way split of the coordinates (round 4)
-    mfma_inst = cg.get_info("last_mfma_instance")                          # template arguments of the kernel the timed steps launched
 
     per_rank = None
     if world > 1:
@@ -707,8 +765,6 @@ def main():
     if rank == 0:
         n, m, d = N_POINTS, N_POINTS, DIM
         n_local = (n + world - 1) // world
-        ms_per_step = elapsed / args.steps * 1e3
-        mvms = args.steps / elapsed
         flops_launch = float(n_local) * m * (3 * d + 3)                 # 3d+3 flops per pair (+1 exp)
         bytes_launch = 4.0 * (n_local * d + m * (d + 1) + n_local)      # compulsory: x rows, packed (y, a) stream, b
         kern_s = kern_avg_ms * 1e-3
@@ -795,22 +851,8 @@ def main():
         # ceiling; it lives under its own keys (issue_roofline_frac, issue_peak_tflops) and never replaces frac.
         peak_tflops = FP32_VECTOR_PEAK_TFLOPS
         issue_peak_tflops = ceiling * flops_per_pair * 1e-12
-        step_stats = _stats(step_ms)
-        line = {
-            "metric": "Gramian MVMs/sec, dense EQ kernel, n=131072, d=3, fp32 (+ achieved HBM GB/s in roofline.hbm_*)",
-            "value": mvms, "unit": "MVM/s", "n_gpus": world, "rccl_ranks": world if (dist.is_initialized() and not rehearsal) else 0, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "ms_median": step_stats["ms_median"], "ms_min": step_stats["ms_min"], "ms_max": step_stats["ms_max"],
-            "timing_note": "value / ms_per_step: wall clock over the K steps between barrier + synchronize (the contract); ms_median / ms_min: one HIP event pair "
-                           "per step on the launch stream, same K steps",
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "EQ dense Gramian mul!, d=3 n=131072 fp32 (BASELINE.json configs[1]); x ~ N(0, I_3), a ~ N(0,1), "
-                                   "alpha=1, beta=0, y == x" + ("; the upper triangle is evaluated once" if sym_path else "; all n*m entries evaluated") + "; points/a/b resident in HBM",
-                       "n": n, "d": d, "kernel": "EQ", "pairs_per_mvm": float(n) * m,
-                       "parallelism": "1 GPU" if world == 1 else (
-                           f"upper triangle by cyclic 256-row panels x{world} + 1 RCCL all-reduce of b per MVM" if sym_path
-                           else f"row-shard x{world} + 1 RCCL all-gather of b per MVM")},
-            "pairs_per_s": mvms * float(n) * m,
+        line = headline(args, world, rehearsal, elapsed, step_ms, sym_path)
+        line.update({
             "rel_err_vs_fp64_oracle": rel_err, "rowwise_err_vs_fp64_oracle": row_err,
             "err_note": "1024 random rows against the fp64 oracle after the timed regions: rel = |b - ref|_2 / |ref|_2, rowwise = max_i |b_i - ref_i| / sum_j |G_ij a_j|",
             "symmetric_variant": symmetric_variant,
@@ -844,9 +886,7 @@ def main():
                 "hbm_achieved_GBps": bytes_launch / kern_s * 1e-9,
                 "hbm_frac": bytes_launch / kern_s * 1e-9 / HBM_PEAK_GBPS,
             },
-        }
-        if rehearsal:
-            line["rehearsal"] = "COVGRAM_BENCH_REHEARSAL=1: all ranks on GPU 0, collectives over gloo through host memory — a code-path rehearsal, NOT a measurement"
+        })
         if per_rank is not None:
             line["per_rank"] = per_rank
             line["per_rank_note"] = ("kernel_ms: the rank's dominant kernel by HIP events on the launch stream over the K timed steps; local_ms / collective_ms: 10 steps "

@@ -180,3 +180,11 @@ def test_bench_refuses_a_world_that_is_not_gpus():
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"], env=_clean_env(),
                            capture_output=True, text=True, timeout=300)
         assert r.returncode == 2 and "GPU(s) are visible" in r.stderr and not r.stdout.strip()
+
+
+def test_bench_refuses_fewer_than_one_timed_step():
+    """--steps sets the number of timed steps and ms_per_step divides by it: --steps 0 exits with code 2 and no JSON line, before any GPU work."""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "0", "--warmup", "0"], env=_clean_env(),
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr and not r.stdout.strip()

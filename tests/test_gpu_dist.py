@@ -119,7 +119,7 @@ def test_bench_runs_its_rccl_collectives_at_world_one():
     all-reduce of the symmetric variant are issued for real; the line must parse and both results must match the oracle."""
     env = dict(os.environ, COVGRAM_FORCE_COLLECTIVE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), RANK="0", WORLD_SIZE="1",
                LOCAL_RANK="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-configs"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-configs"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -132,10 +132,10 @@ def test_bench_runs_its_rccl_collectives_at_world_one():
 
 
 def test_bench_gpus_one_with_no_environment_at_all():
-    """`python3 bench.py --gpus 1` the way the driver types it — no WORLD_SIZE / RANK / MASTER_* in the environment: one process, no
-    process group (rccl_ranks 0), the contract line."""
+    """`python3 bench.py --gpus 1 --full` with no WORLD_SIZE / RANK / MASTER_* in the environment: one process, no
+    process group (rccl_ranks 0), the contract line with the oracle check and the roofline."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "COVGRAM_FORCE_COLLECTIVE")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-configs"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-configs"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -145,11 +145,66 @@ def test_bench_gpus_one_with_no_environment_at_all():
     assert line["roofline"]["peak"] == 157.3 and 0 < line["roofline"]["frac"] < 1 and line["roofline"]["issue_roofline_frac"] < 1
 
 
+_FULL_ONLY = ("rel_err_vs_fp64_oracle", "symmetric_variant", "direct_difference_variant", "incl_h2d_d2h", "roofline", "per_rank", "single_gpu_ms",
+              "cpu_baseline", "configs")
+
+
+def _plain_bench(tmp_path, gpus, steps, warmup, extra_env=None):
+    """A plain `bench.py --gpus N --steps K --warmup W --dump-outputs DIR` run: its one line, checked for the contract fields and for the
+    absence of --full's, and the b it dumped."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "COVGRAM_FORCE_COLLECTIVE")}
+    env.update(extra_env or {})
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", str(steps), "--warmup", str(warmup),
+                        "--dump-outputs", str(out)], env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    assert line["n_gpus"] == gpus and line["steps"] == steps and line["warmup"] == warmup
+    assert line["unit"] == "MVM/s" and line["higher_is_better"] is True and line["dtype"] == "f32" and line["metric"].startswith("Gramian MVMs/sec, dense EQ")
+    assert line["value"] > 50 and abs(line["ms_per_step"] * line["value"] - 1e3) < 1e-6
+    assert not set(_FULL_ONLY) & set(line), sorted(set(_FULL_ONLY) & set(line))
+    b = np.load(out / "b.npy")
+    assert b.dtype == np.float32 and b.shape == (131072,)
+    return line, b
+
+
+def _check_bench_b(oracle, b):
+    """The dumped b against the fp64 oracle on the 1024 rows --full's spot check uses, from bench.py's own seeded inputs."""
+    import bench
+    rng = np.random.default_rng(bench.SEED)
+    Xh = rng.standard_normal((bench.N_POINTS, bench.DIM)).astype(np.float32)
+    ah = rng.standard_normal(bench.N_POINTS).astype(np.float32)
+    rows = np.random.default_rng(1).choice(bench.N_POINTS, 1024, replace=False)
+    ref = oracle.mul(None, oracle.Kernel(oracle.EQ), Xh[rows], Xh, ah, dtype=np.float32)
+    absref = oracle.mul(None, oracle.Kernel(oracle.EQ), Xh[rows], Xh, np.abs(ah), dtype=np.float32)
+    got = b[rows].astype(np.float64)
+    assert np.linalg.norm(got - ref) / np.linalg.norm(ref) <= 1e-5
+    assert np.max(np.abs(got - ref) / absref) <= 1e-5
+
+
+def test_bench_plain_run_prints_the_headline_and_dumps_b(tmp_path, oracle):
+    """`python3 bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: exactly the contract line (K timed steps,
+    value = 1000 / ms_per_step) and DIR/b.npy = the last timed step's b, which must match the fp64 oracle."""
+    line, b = _plain_bench(tmp_path, 1, 7, 2)
+    assert line["rccl_ranks"] == 0 and line["config"]["parallelism"] == "1 GPU"
+    _check_bench_b(oracle, b)
+
+
+def test_bench_plain_run_multi_rank_path_rehearsed_on_one_gpu(tmp_path, oracle):
+    """The plain run's N > 1 path (slowest rank's wall clock, rank 0 writes the line and b) rehearsed with two ranks on the one GPU
+    (COVGRAM_BENCH_REHEARSAL=1, collectives over gloo): the all-gathered b must match the fp64 oracle."""
+    line, b = _plain_bench(tmp_path, 2, 3, 1, {"COVGRAM_BENCH_REHEARSAL": "1"})
+    assert line["rccl_ranks"] == 0 and "rehearsal" in line and "row-shard x2" in line["config"]["parallelism"]
+    _check_bench_b(oracle, b)
+
+
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs")
 def test_bench_gpus_two_launches_two_rccl_ranks():
     """`python3 bench.py --gpus 2` with no environment: the launcher starts two ranks over RCCL; the line says so."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -165,7 +220,7 @@ def test_bench_multi_rank_path_rehearsed_on_one_gpu():
     line must say that it is a rehearsal, carry two per-rank entries whose shards cover the rows, and both results must match the oracle."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["COVGRAM_BENCH_REHEARSAL"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"], env=env, capture_output=True, text=True, timeout=1200)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"], env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout

@@ -22,7 +22,7 @@ block = f"""<!-- headline:begin -->
 p = os.path.join(ROOT, "README.md"); s = open(p).read()
 s = re.sub(r"<!-- headline:begin -->.*?<!-- headline:end -->", lambda m: block, s, flags=re.S)
 open(p, "w").write(s)
-row = (f"| `{rnd}_bench_n1.json`, `{rnd}_bench_kernel_stats.csv` | <!-- check:{rnd} --> `python3 bench.py --steps 20 --warmup 5` on one MI355X at the end of round {int(rnd[1:])} and "
+row = (f"| `{rnd}_bench_n1.json`, `{rnd}_bench_kernel_stats.csv` | <!-- check:{rnd} --> `python3 bench.py --full --steps 20 --warmup 5` on one MI355X at the end of round {int(rnd[1:])} and "
        f"`rocprofv3 --kernel-trace --stats` of `bench.py` (`tools/profile_bench.sh`): the contract kernel is unchanged, `{inst}`, all n·m entries — contract run {line['value']:.1f} MVM/s, "
        f"live `kernel_avg_ms` {r['kernel_avg_ms']:.3f}, profiled average {float(k['AverageNs']) * 1e-6:.3f} ms over {int(k['Calls'])} dispatches (the profiler lowers the clock; cold dispatches included), "
        f"`roofline.frac` {r['frac']:.2f}; `roofline.traffic` taken only from a PMC pass of the launched instance (`traffic_check`), row-wise errors beside the norm-wise ones; "
