@@ -217,6 +217,22 @@ def _vec_arg(a: torch.Tensor, n: int, dtype, device, what: str) -> torch.Tensor:
     return a.to(device=device, dtype=dtype)
 
 
+def _overlaps(y: torch.Tensor, a: torch.Tensor) -> bool:
+    """True when the memory y may write intersects the memory a is read from (same storage, intersecting byte ranges)."""
+    if y.device != a.device or y.untyped_storage().data_ptr() != a.untyped_storage().data_ptr() or y.numel() == 0 or a.numel() == 0:
+        return False
+
+    def span(t):
+        lo = hi = t.data_ptr()
+        for size, stride in zip(t.shape, t.stride()):
+            ext = (size - 1) * stride * t.element_size()
+            lo, hi = (lo + ext, hi) if ext < 0 else (lo, hi + ext)
+        return lo, hi + t.element_size()
+
+    (ylo, yhi), (alo, ahi) = span(y), span(a)
+    return ylo < ahi and alo < yhi
+
+
 # ----------------------------------------------------------------------------------------------
 # lazy operators
 # ----------------------------------------------------------------------------------------------
@@ -720,6 +736,8 @@ class LazyMatrixSum(LazyOperator):
 
     def mul_(self, y, a, alpha=1.0, beta=0.0):
         a = _vec_arg(a, self.shape[1], self.dtype, self.device, "a")
+        if _overlaps(y, a):           # in place (mul!(x, G + D, x)): every term after the first must still see the a the caller passed
+            a = a.clone()
         first = True
         for A in self.args:
             b = beta if first else 1.0

@@ -298,6 +298,22 @@ int ws_reserve(covgram_ctx* ctx, int slot, size_t bytes, void** out) {
     return COVGRAM_OK;
 }
 
+int unalias_input(covgram_ctx* ctx, const void** a, int64_t* lda, int64_t rows_a, int64_t cols, const void* y, int64_t ldy, int64_t rows_y, size_t ts) {
+    if (*a == nullptr || y == nullptr || rows_a <= 0 || rows_y <= 0 || cols <= 0) return COVGRAM_OK;
+    const char* a0 = (const char*)*a;
+    const char* a1 = a0 + ((size_t)(cols - 1) * (size_t)*lda + (size_t)rows_a) * ts;
+    const char* y0 = (const char*)y;
+    const char* y1 = y0 + ((size_t)(cols - 1) * (size_t)ldy + (size_t)rows_y) * ts;
+    if (!(a0 < y1 && y0 < a1)) return COVGRAM_OK;
+    CG_DEVICE(ctx);
+    void* w;
+    int rc = ws_reserve(ctx, 5, (size_t)rows_a * (size_t)cols * ts, &w);
+    if (rc) return rc;
+    CG_CHECK_HIP(hipMemcpy2DAsync(w, (size_t)rows_a * ts, *a, (size_t)*lda * ts, (size_t)rows_a * ts, (size_t)cols, hipMemcpyDeviceToDevice, ctx->stream));
+    *a = w; *lda = rows_a;
+    return COVGRAM_OK;
+}
+
 int tickets_reserve(covgram_ctx* ctx, size_t count, unsigned** out) {
     if (ctx->tickets_cap < count) {
         if (ctx->tickets) {
@@ -850,11 +866,45 @@ static int constant_term_mvm(covgram_ctx* ctx, int dtype, const void* a, int64_t
     return COVGRAM_OK;
 }
 
+// loc == HOST for a product that runs in several steps (a Sum split term by term): a and y go to the device ONCE (workspace slots 2 / 3),
+// run(a_dev, y_dev) computes on the device copies, and y comes back once — every step then reads the a the caller passed, even when a and y
+// are the same host array
+extern "C++" {
+template <typename Run>
+static int host_staged(covgram_ctx* ctx, int dtype, const void* a, int64_t lda, int64_t rows_a, void* y, int64_t ldy, int64_t rows_y, int nrhs,
+                       double beta, Run run) {
+    CG_REQUIRE(nrhs >= 1, COVGRAM_EINVAL, "nrhs must be >= 1");
+    CG_REQUIRE(lda >= rows_a && ldy >= rows_y, COVGRAM_EINVAL, "DimensionMismatch: lda=%lld < %lld or ldy=%lld < %lld",
+               (long long)lda, (long long)rows_a, (long long)ldy, (long long)rows_y);
+    CG_REQUIRE((a != nullptr || rows_a == 0) && (y != nullptr || rows_y == 0), COVGRAM_EINVAL, "a or y is NULL");
+    if (rows_y == 0) return COVGRAM_OK;
+    CG_DEVICE(ctx);
+    const size_t ts = dtype_size(dtype);
+    void *sa, *sy;
+    int rc = ws_reserve(ctx, 2, (size_t)std::max<int64_t>(rows_a, 1) * nrhs * ts, &sa); if (rc) return rc;
+    rc = ws_reserve(ctx, 3, (size_t)rows_y * nrhs * ts, &sy); if (rc) return rc;
+    if (rows_a > 0)
+        CG_CHECK_HIP(hipMemcpy2DAsync(sa, (size_t)rows_a * ts, a, (size_t)lda * ts, (size_t)rows_a * ts, nrhs, hipMemcpyHostToDevice, ctx->stream));
+    if (beta != 0.0)
+        CG_CHECK_HIP(hipMemcpy2DAsync(sy, (size_t)rows_y * ts, y, (size_t)ldy * ts, (size_t)rows_y * ts, nrhs, hipMemcpyHostToDevice, ctx->stream));
+    rc = run((const void*)sa, sy);
+    if (rc) return rc;
+    CG_CHECK_HIP(hipMemcpy2DAsync(y, (size_t)ldy * ts, sy, (size_t)rows_y * ts, (size_t)rows_y * ts, nrhs, hipMemcpyDeviceToHost, ctx->stream));
+    CG_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    return COVGRAM_OK;
+}
+}  // extern "C++"
+
 int covgram_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, const void* a,
                 int64_t lda, void* y, int64_t ldy, int32_t nrhs, double alpha, double beta, int32_t loc) {
     int rc = check_pair(ctx, X, Y);
     if (rc) return rc;
     ctx->last_sum_fused = 0;
+    // a and y may overlap (include/covgram.h): the kernels below, and every term of a split Sum, read a private copy of a
+    if (loc == COVGRAM_DEVICE && nrhs >= 1 && lda >= Y->n && ldy >= X->n) {
+        rc = unalias_input(ctx, &a, &lda, Y->n, nrhs, y, ldy, X->n, dtype_size(X->dtype));
+        if (rc) return rc;
+    }
     {
         SumTerm terms[COVGRAM_COMPOSITE_MAX_TERMS];
         int nt = 0;
@@ -865,6 +915,9 @@ int covgram_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points*
             HostKernel chk;
             rc = make_host_kernel(k, X->dtype, false, &chk);   // the composite's own validation (traits, limits) still applies
             if (rc) return rc;
+            if (loc == COVGRAM_HOST) return host_staged(ctx, X->dtype, a, lda, Y->n, y, ldy, X->n, nrhs, beta, [&](const void* ad, void* yd) {
+                return covgram_mvm(ctx, k, X, Y, ad, Y->n, yd, X->n, nrhs, alpha, beta, COVGRAM_DEVICE);
+            });
             for (int t = 0; t < nt; ++t) {
                 rc = covgram_mvm(ctx, terms[t].ptr(), X, Y, a, lda, y, ldy, nrhs, alpha, t == 0 ? beta : 1.0, loc);
                 if (rc) return rc;
@@ -1215,6 +1268,10 @@ static int grad_mvm_impl(covgram_ctx* ctx, const covgram_kernel* k, const covgra
     CG_REQUIRE(nrhs >= 1, COVGRAM_EINVAL, "nrhs must be >= 1");
     CG_REQUIRE(lda >= Y->n * (int64_t)(Y->d + vg) && ldy >= X->n * (int64_t)(X->d + vg), COVGRAM_EINVAL,
                "lda / ldy smaller than the block vectors (%lld, %lld)", (long long)(Y->n * (int64_t)(Y->d + vg)), (long long)(X->n * (int64_t)(X->d + vg)));
+    if (loc == COVGRAM_DEVICE) {   // a and y may overlap (include/covgram.h): everything below reads a private copy of a
+        rc = unalias_input(ctx, &a, &lda, Y->n * (int64_t)(Y->d + vg), nrhs, y, ldy, X->n * (int64_t)(X->d + vg), dtype_size(X->dtype));
+        if (rc) return rc;
+    }
     {
         SumTerm terms[COVGRAM_COMPOSITE_MAX_TERMS];
         int nt = 0;
@@ -1225,6 +1282,10 @@ static int grad_mvm_impl(covgram_ctx* ctx, const covgram_kernel* k, const covgra
             HostKernel chk;
             rc = make_host_kernel(k, X->dtype, true, &chk);
             if (rc) return rc;
+            const int64_t ma = Y->n * (int64_t)(Y->d + vg), ny = X->n * (int64_t)(X->d + vg);
+            if (loc == COVGRAM_HOST) return host_staged(ctx, X->dtype, a, lda, ma, y, ldy, ny, nrhs, beta, [&](const void* ad, void* yd) {
+                return grad_mvm_impl(ctx, k, X, Y, ad, ma, yd, ny, nrhs, alpha, beta, COVGRAM_DEVICE, vg);
+            });
             for (int t = 0; t < nt; ++t) {
                 rc = grad_mvm_impl(ctx, terms[t].ptr(), X, Y, a, lda, y, ldy, nrhs, alpha, t == 0 ? beta : 1.0, loc, vg);
                 if (rc) return rc;
@@ -1491,6 +1552,9 @@ int covgram_mvm_sym_partial(covgram_ctx* ctx, const covgram_kernel* k, const cov
     int rc = covgram_mvm_sym_supported(ctx, k, X, world, &ok);
     if (rc) return rc;
     if (!ok) { set_error("no symmetric kernel applies to this kernel / point set / world size"); return COVGRAM_EUNSUPPORTED; }
+    int64_t lda = X->n;
+    rc = unalias_input(ctx, &a, &lda, X->n, 1, y, X->n, X->n, dtype_size(X->dtype));   // a and y may overlap: a private copy of a
+    if (rc) return rc;
     HostKernel hk;
     rc = make_host_kernel(k, X->dtype, false, &hk);
     if (rc) return rc;

@@ -158,8 +158,10 @@ int covgram_mvm_sharded(covgram_ctx* ctx, const covgram_kernel* k, const covgram
     const size_t ts = dtype_size(X->dtype);
     if (n == 0) return COVGRAM_OK;
     CG_REQUIRE(y != nullptr, COVGRAM_EINVAL, "y is NULL");
+    int64_t lda = Y->n;
+    int rc = unalias_input(ctx, &a, &lda, Y->n, 1, y, n, n, ts);   // a and y may overlap: every rank's rows read a private copy of a
+    if (rc) return rc;
     covgram_points* Xs = nullptr;
-    int rc = COVGRAM_OK;
     if (hi > lo) { rc = covgram_points_slice(X, lo, hi - lo, &Xs); if (rc) return rc; }
     const bool exact = per * world == n;
     if (exact) {

@@ -240,7 +240,7 @@ struct covgram_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
-    covgram::Workspace ws[5];  // 0: packed tile stream, 1: split-J partials, 2/3: host staging (device copies of a / y), 4: wide-gradient slices
+    covgram::Workspace ws[6];  // 0: packed tile stream, 1: split-J partials, 2/3: host staging (device copies of a / y), 4: wide-gradient slices, 5: private copy of an a that overlaps y
     // options
     int64_t dense_variant = 0;   // 0 auto (fp32 EQ on the matrix cores when the norm bound allows; Dot() as X (Y' a)), 1 direct differences / entry by entry, 2 MFMA whenever the shape allows
     int64_t rows_per_lane = 0;   // 0 = auto
@@ -344,6 +344,10 @@ inline bool inkernel_reduce_on(const covgram_ctx* ctx, bool mfma_eq_kernel, int6
     return ctx->inkernel_reduce == 1 || (mfma_eq_kernel && n <= 4096);
 }
 int ws_reserve(covgram_ctx* ctx, int slot, size_t bytes, void** out);
+// a (rows_a x cols, leading dimension *lda) and y (rows_y x cols, ldy) of one MVM, device memory: when their byte ranges intersect (an in-place
+// mul!, y == a, or any partial overlap) copy a ONCE into workspace slot 5 and point *a / *lda at the copy, so that nothing behind the entry reads
+// a after some launch has written y.  Separate buffers: no copy, no launch.
+int unalias_input(covgram_ctx* ctx, const void** a, int64_t* lda, int64_t rows_a, int64_t cols, const void* y, int64_t ldy, int64_t rows_y, size_t ts);
 // >= count zeroed arrival counters (grown stream-ordered; they return to zero by themselves after every launch that uses them)
 int tickets_reserve(covgram_ctx* ctx, size_t count, unsigned** out);
 // returns an event pair to record around the dominant kernel, or nullptr when timing is off / the pool is full

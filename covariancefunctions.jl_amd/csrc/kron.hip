@@ -226,6 +226,10 @@ int covgram_kron_mvm(covgram_ctx* ctx, const void* const* factors, const int64_t
         }
     }
     CG_DEVICE(ctx);
+    if (loc == COVGRAM_DEVICE) {   // a and y may overlap (include/covgram.h): the mode products read a private copy of a
+        int rc0 = unalias_input(ctx, &a, &lda, nin, nrhs, y, ldy, nout, ts);
+        if (rc0) return rc0;
+    }
     // right-hand sides that lie one after the other are one more (slowest) tensor index; padded ones are packed first
     const bool packed_a = (lda == nin) || nrhs == 1, packed_y = (ldy == nout) || nrhs == 1;
     const bool host = (loc == COVGRAM_HOST);

@@ -748,6 +748,10 @@ int covgram_lowrank_mvm(covgram_ctx* ctx, const void* U, int64_t ldu, const void
     CG_REQUIRE(r <= 8192, COVGRAM_EUNSUPPORTED, "lowrank: r = %lld exceeds 8192", (long long)r);
     const size_t ts = dtype_size(dtype);
     CG_DEVICE(ctx);
+    if (loc == COVGRAM_DEVICE) {   // a and y may overlap (include/covgram.h): both passes read a private copy of a
+        int rc0 = unalias_input(ctx, &a, &lda, m, nrhs, y, ldy, n, ts);
+        if (rc0) return rc0;
+    }
     const bool mfma = nrhs >= 8 && (dtype == COVGRAM_F32 ? lowrank_mfma_fits<float>(r) : lowrank_mfma_fits<double>(r));
     const int pz = mfma ? nrhs : 1;                              // columns of Z held at once
     // row slabs of V: ~4 workgroups per CU (GEMV form: ~2, i.e. at least two sweeps per slab at n = 2^20 — a slab of ONE sweep spends as long in

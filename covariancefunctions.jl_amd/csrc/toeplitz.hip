@@ -1197,6 +1197,11 @@ int covgram_toeplitz_mvm(covgram_toeplitz* T, const void* a, void* y, double alp
     CG_DEVICE(ctx);
     const size_t ts = dtype_size(T->dtype);
     const int64_t n = T->n, m = T->m, N = T->N, NC = N / 2 + 1;
+    if (loc == COVGRAM_DEVICE) {   // a and y may overlap (include/covgram.h): the transforms read a private copy of a
+        int64_t lda = m;
+        int rc0 = unalias_input(ctx, &a, &lda, m, 1, y, n, n, ts);
+        if (rc0) return rc0;
+    }
     const void* a_dev = a; void* y_dev = y;
     if (loc == COVGRAM_HOST) {
         if (!T->stage_a) CG_CHECK_HIP(hipMalloc(&T->stage_a, (size_t)m * ts));

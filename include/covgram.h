@@ -206,9 +206,9 @@ int covgram_points_info(const covgram_points* pts, int64_t* n, int32_t* d, int32
 
 /* y <- alpha * G(k; X, Y) * a + beta * y.   G is n×m (n = |X|, m = |Y|); a is m×nrhs (lda >= m),
  * y is n×nrhs (ldy >= n), column-major; dtype is that of the points.  loc applies to a and y.
- * Aliasing: y may be a itself (an in-place MVM with n == m: every dense path reads the weights from its own packed copy, or — the general
- * matrix-core EQ kernel, which reads a directly — falls back to the pack launch when the two ranges overlap); partially overlapping
- * columns of a multi-column a / y are not supported. */
+ * Aliasing: a and y may overlap in any way — y may be a itself (an in-place MVM, n == m), or any part of it, with any lda / ldy; the
+ * library then reads a from a private copy (loc == DEVICE: one device-to-device copy at entry; loc == HOST: a is staged to the device
+ * before anything is written back).  Separate ranges cost nothing. */
 int covgram_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y,
                 const void* a, int64_t lda, void* y, int64_t ldy, int32_t nrhs, double alpha, double beta,
                 int32_t loc);
@@ -231,6 +231,7 @@ int covgram_matrix(covgram_ctx* ctx, const covgram_kernel* k, const covgram_poin
  * every rank: it depends on k, x and world only), and covgram_mvm_sym_partial returns COVGRAM_EUNSUPPORTED exactly when it says 0 —
  * callers then shard rows and all-gather (covgram_mvm). */
 int covgram_mvm_sym_supported(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, int32_t world, int32_t* supported);
+/* Aliasing (covgram_mvm_sym_partial): a and y may overlap in any way; a is then read from a private copy. */
 int covgram_mvm_sym_partial(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, const void* a, void* y,
                             int32_t rank, int32_t world);
 
@@ -249,6 +250,7 @@ int covgram_mvm_sym_partial(covgram_ctx* ctx, const covgram_kernel* k, const cov
  *                            replicated device data; rank r evaluates the rows [r per, (r + 1) per), per = ceil(n / world), with the
  *                            single-GPU kernels — straight into its slice of y when world divides n, the all-gather then in place — and
  *                            ONE ncclAllGather completes y, which is the replicated `a` of the next Krylov iteration.  One right-hand side.
+ *                            Aliasing: a and y may overlap in any way; a is then read from a private copy.
  *   covgram_mvm_sym_allreduce  the same product of gramian(k, x) in the symmetric form: covgram_mvm_sym_partial(rank, world) + ONE
  *                            ncclAllReduce; COVGRAM_EUNSUPPORTED exactly when covgram_mvm_sym_supported says 0 (then: covgram_mvm_sharded). */
 #define COVGRAM_COMM_ID_BYTES 128
@@ -275,13 +277,15 @@ int covgram_grad_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram_po
  *     [ k(x_i,y_j)        (d/dy k)^T      ]
  *     [ d/dx k            d/dx d/dy^T k   ]
  * flat point-major block vectors: entry i*(d+1) is the value component, i*(d+1)+1+l the l-th gradient component; right-hand sides
- * as for covgram_grad_mvm (lda >= m*(d+1), ldy >= n*(d+1)). */
+ * as for covgram_grad_mvm (lda >= m*(d+1), ldy >= n*(d+1)).
+ * Aliasing (covgram_grad_mvm and covgram_valgrad_mvm): a and y may overlap in any way; a is then read from a private copy. */
 int covgram_valgrad_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, const void* a,
                         int64_t lda, void* y, int64_t ldy, int32_t nrhs, double alpha, double beta, int32_t loc);
 
 /* Toeplitz T[i,j] = vc[i-j] (i >= j), vr[j-i] (i < j); vr == NULL: symmetric (vr = vc, m = n).
  * circulant != 0: T[i,j] = vc[(i-j) mod n] (vr must be NULL).  The spectrum of the circulant embedding
- * (N = next power of two >= n+m-1, real-to-complex rocFFT) is computed once here and cached. */
+ * (N = next power of two >= n+m-1, real-to-complex rocFFT) is computed once here and cached.
+ * Aliasing (covgram_toeplitz_mvm): a and y may overlap in any way; a is then read from a private copy. */
 int covgram_toeplitz_create(covgram_ctx* ctx, covgram_toeplitz** out, const void* vc, const void* vr, int64_t n,
                             int64_t m, int32_t dtype, int32_t loc, int32_t circulant);
 int covgram_toeplitz_mvm(covgram_toeplitz* T, const void* a, void* y, double alpha, double beta, int32_t loc);
@@ -319,14 +323,16 @@ int covgram_cg_step_shifted(covgram_ctx* ctx, int64_t n, int32_t dtype, void* x,
  * factors[i]: dense rows[i]×cols[i] column-major matrix with leading dimension lds[i] (device or host per loc).
  * A: (prod cols)×nrhs (lda), Y: (prod rows)×nrhs (ldy), column-major; a vector is nrhs = 1.  Hand-written mode-product kernels on the
  * matrix cores of the data's own precision (csrc/kron.hip): the last two modes in ONE pass when cols[q-1] <= 128, so q = 3 costs two
- * passes over the tensor; a mode whose factor has a side >= 1024 (a compute-bound dense GEMM) goes to rocBLAS. */
+ * passes over the tensor; a mode whose factor has a side >= 1024 (a compute-bound dense GEMM) goes to rocBLAS.
+ * Aliasing: A and Y may overlap in any way (Y = A: an in-place product of a square operator); A is then read from a private copy. */
 int covgram_kron_mvm(covgram_ctx* ctx, const void* const* factors, const int64_t* rows, const int64_t* cols,
                      const int64_t* lds, int32_t q, int32_t dtype, const void* a, int64_t lda, void* y, int64_t ldy,
                      int32_t nrhs, double alpha, double beta, int32_t loc);
 
 /* Y <- alpha * U (V' A) + beta * Y;  U: n×r (ldu), V: m×r (ldv), A: m×nrhs (lda >= m), Y: n×nrhs (ldy >= n), column-major.
  * nrhs >= 8: both tall-skinny products run on the matrix cores in the data's own precision (v_mfma_f32_32x32x2_f32 /
- * v_mfma_f64_16x16x4_f64); fewer right-hand sides: streaming GEMV kernels, one pair per column. */
+ * v_mfma_f64_16x16x4_f64); fewer right-hand sides: streaming GEMV kernels, one pair per column.
+ * Aliasing: A and Y may overlap in any way; A is then read from a private copy. */
 int covgram_lowrank_mvm(covgram_ctx* ctx, const void* U, int64_t ldu, const void* V, int64_t ldv, int64_t n, int64_t m,
                         int64_t r, int32_t dtype, const void* a, int64_t lda, void* y, int64_t ldy, int32_t nrhs,
                         double alpha, double beta, int32_t loc);

@@ -410,3 +410,46 @@ def test_docs_quote_the_recorded_numbers():
         close(float(m.group(3)), float(k2["AverageNs"]) * 1e-6, f"{tag} profiled average")
         assert int(m.group(4)) == int(k2["Calls"])
         close(float(m.group(5)), l2["roofline"]["frac"], f"{tag} roofline.frac")
+
+
+def test_lazy_matrix_sum_in_place_on_cpu(cg):
+    """mul!(x, S, x, alpha, beta) on S = G + D (LazyMatrixSum) with a stand-in dense operator on CPU tensors: every term after the first
+    must read the a the caller passed, not the first term's output written over it.  Overlapping views of one buffer too."""
+
+    class Dense(cg.LazyOperator):
+        def __init__(self, M):
+            self.M, self.shape, self.dtype, self.device = M, tuple(M.shape), M.dtype, M.device
+
+        def mul_(self, y, a, alpha=1.0, beta=0.0):
+            t = self.M @ a
+            return y.copy_(alpha * t) if beta == 0 else y.mul_(beta).add_(t, alpha=alpha)
+
+    rng = np.random.default_rng(5)
+    for n, k in ((5, 1), (37, 3)):
+        M = torch.from_numpy(rng.standard_normal((n, n)))
+        diag = torch.from_numpy(rng.uniform(0.1, 1.0, n))
+        D2 = torch.from_numpy(rng.standard_normal((n, n)))
+        for S, dense in ((Dense(M) + diag, M + torch.diag(diag)), (diag + Dense(M), M + torch.diag(diag)),
+                         (Dense(M) + D2 + diag, M + D2 + torch.diag(diag)), (D2 + Dense(M), D2 + M)):
+            for alpha, beta in ((1.0, 0.0), (0.7, -1.3)):
+                a0 = torch.from_numpy(rng.standard_normal(n))
+                ref = alpha * (dense @ a0) + beta * a0
+                x = a0.clone()
+                assert cg.mul_(x, S, x, alpha, beta) is x
+                assert torch.allclose(x, ref, rtol=1e-12, atol=1e-12), (n, alpha, beta, float((x - ref).abs().max()))
+                y = torch.zeros(n, dtype=torch.float64)
+                assert torch.allclose(cg.mul_(y, S, a0.clone(), alpha, 0.0), alpha * (dense @ a0), rtol=1e-12, atol=1e-12)
+                # partial overlap: a = buf[:n], y = buf[s:s+n] and the other way round
+                for s in (1, 3):
+                    for a_first in (True, False):
+                        buf0 = torch.from_numpy(rng.standard_normal(n + s))
+                        buf = buf0.clone()
+                        ao, yo = (0, s) if a_first else (s, 0)
+                        cg.mul_(buf[yo:yo + n], S, buf[ao:ao + n], alpha, beta)
+                        want = alpha * (dense @ buf0[ao:ao + n]) + beta * buf0[yo:yo + n]
+                        assert torch.allclose(buf[yo:yo + n], want, rtol=1e-12, atol=1e-12), (n, s, a_first)
+                # matrix right-hand sides in place
+                A0 = torch.from_numpy(rng.standard_normal((n, k)))
+                X = A0.clone()
+                cg.mul_(X, S, X, alpha, beta)
+                assert torch.allclose(X, alpha * (dense @ A0) + beta * A0, rtol=1e-12, atol=1e-12)
