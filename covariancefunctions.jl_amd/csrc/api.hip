@@ -615,6 +615,8 @@ int covgram_ctx_get_info(covgram_ctx* ctx, const char* key, int64_t* value) {
     else if (!strcmp(key, "last_inkernel_reduce")) *value = ctx->last_inkernel_reduce;
     else if (!strcmp(key, "last_grad_expand")) *value = ctx->last_grad_expand;
     else if (!strcmp(key, "last_grad_bcast")) *value = ctx->last_grad_bcast;
+    else if (!strcmp(key, "last_grad_path")) *value = ctx->last_grad_path;
+    else if (!strcmp(key, "last_grad_jsplit")) *value = ctx->last_grad_jsplit;
     else if (!strcmp(key, "last_sum_fused")) *value = ctx->last_sum_fused;
     else if (!strcmp(key, "last_mfma_instance")) *value = ctx->last_mfma_instance;
     else if (!strcmp(key, "last_mfma_sym_rt")) *value = ctx->last_mfma_sym_rt;
@@ -1276,9 +1278,9 @@ static int grad_mvm_impl(covgram_ctx* ctx, const covgram_kernel* k, const covgra
         SumTerm terms[COVGRAM_COMPOSITE_MAX_TERMS];
         int nt = 0;
         double constant = 0.0;
-        // (a Sum the one-pass matrix-core kernels take is NOT split: every term shares the pair's distance, as in the reference's
-        //  per-pair evaluation src/algebra.jl:27-47 — dense_mfma.hip: sum_fused_applies)
-        if (!sum_fused_applies(ctx, k, X, Y, nrhs) && composite_sum_terms(ctx, k, loc, terms, &nt, &constant)) {   // derivatives are linear in the kernel: term by term as well
+        // (always split: the one-pass Sum kernels of covgram_mvm (dense_mfma.hip: sum_fused_applies) are value kernels only — there is no
+        //  one-pass gradient form, and the unsplit Sum would run the composite interpreter instead of each term's own kernel)
+        if (composite_sum_terms(ctx, k, loc, terms, &nt, &constant)) {   // derivatives are linear in the kernel: term by term as well
             HostKernel chk;
             rc = make_host_kernel(k, X->dtype, true, &chk);
             if (rc) return rc;
@@ -1319,6 +1321,7 @@ static int grad_mvm_impl(covgram_ctx* ctx, const covgram_kernel* k, const covgra
     const int D = wide ? ((d + 31) / 32) * 32 : pad_dim(d);
     grad_launch_fn launch = grad_launcher(hk.tu_family);
     CG_DEVICE(ctx);
+    ctx->last_grad_path = 0; ctx->last_grad_jsplit = 0; ctx->last_grad_expand = 0; ctx->last_grad_bcast = 0;
     if (n == 0) return COVGRAM_OK;
 
     const void* a_all = a;
@@ -1394,6 +1397,7 @@ static int grad_mvm_impl(covgram_ctx* ctx, const covgram_kernel* k, const covgra
         void* zslab = nullptr;
         const int64_t total = n * (int64_t)bd;
         if (zs > 1) { rc = ws_reserve(ctx, 4, (size_t)zs * total * ts, &zslab); if (rc) return rc; }
+        ctx->last_grad_path |= 4 | (mpad > panel ? 8 : 0) | (zs > 1 ? 16 : 0);
         for (int64_t col0 = 0; col0 < mpad; col0 += panel) {
             const int64_t pc = std::min<int64_t>(panel, mpad - col0);
             void *P, *C;
@@ -1496,6 +1500,8 @@ static int grad_mvm_impl(covgram_ctx* ctx, const covgram_kernel* k, const covgra
         ga.expd = expd ? 1 : 0; ga.Ex = Ex; ga.bcast = bcast;
         ga.nr = nr; ga.ldy = ldy_d;
         ctx->last_grad_expand = ga.expd;
+        ctx->last_grad_jsplit = jsplit;
+        ctx->last_grad_path |= 1 | (nr == 2 ? 2 : 0) | (jsplit > 1 ? 32 : 0);
         ga.vg_c = (iso ? -1.0 : 1.0) / hk.kp.gamma;
         ga.vg_b = iso ? -2.0 * hk.kp.gamma : hk.kp.gamma;
         if (jsplit == 1) ga.out = y_dev;

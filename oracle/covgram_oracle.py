@@ -407,6 +407,65 @@ def grad_mul(yv, k: Kernel, X, Y, a, alpha=1.0, beta=0.0, dtype=np.float64, chun
     return out.reshape(-1)
 
 
+def _absmul_pairs(k, Xi, Y, A, centre):
+    """Per-pair pieces of the absolute-value products: (k0, k1, k2) and the abs-magnitudes that stand in for r_l and r.a.
+    centre = None: |r_l| and |r|.|a| (isotropic), |y_l| and |x|.|a| (dot product).  centre = c (isotropic only): the same
+    quantities as the expanded form evaluates them, r_l = (x_l - c_l) - (y_l - c_l) and r.a = (x - c).a - (y - c).a, i.e.
+    |x_l - c_l| + |y_l - c_l| and |x - c|.|a| + |y - c|.|a| (grad_mvm.hpp, "Expanded form")."""
+    if k.trait == ISOTROPIC:
+        R = Xi[:, None, :] - Y[None, :, :]
+        kk = profile_derivatives(k, np.einsum("ijl,ijl->ij", R, R))
+        if centre is None:
+            Rl = np.abs(R)
+            ra = np.einsum("ijl,jl->ij", Rl, np.abs(A))
+        else:
+            xc, yc = np.abs(Xi - centre), np.abs(Y - centre)
+            Rl = xc[:, None, :] + yc[None, :, :]
+            ra = xc @ np.abs(A).T + (yc * np.abs(A)).sum(axis=1)[None, :]
+        return kk, Rl, ra
+    kk = profile_derivatives(k, Xi @ Y.T)
+    return kk, np.broadcast_to(np.abs(Y)[None], (Xi.shape[0],) + Y.shape), np.abs(Xi) @ np.abs(A).T
+
+
+def grad_absmul(k, X, Y, a, centre=None, chunk=64):
+    """For every entry l of every block row i: an upper bound on sum_j sum_k |block_ij[l, k]| |a_j[k]| in fp64 — the condition
+    denominator of output entry (i, l) as a dot product, what a row-wise error check of grad_mul divides by.  The bound only
+    splits the diagonal of each block from its rank-one part (a cancellation there is not credited):
+      isotropic:   2 (|k1| |a_l| + 2 |k2| |r_l| (|r|.|a|))      (block -2 (k1 I + 2 k2 r r'), gradient.jl:86-92)
+      dot product: |k1| |a_l| + |k2| |y_l| (|x|.|a|)            (block k1 I + k2 y x',        gradient.jl:109-115)
+    centre (isotropic): the same for the expanded form about that centre (_absmul_pairs)."""
+    X = as_points(X).astype(np.float64); Y = as_points(X if Y is None else Y).astype(np.float64)
+    n, d = X.shape; m = Y.shape[0]
+    A = np.asarray(a, dtype=np.float64).reshape(m, d)
+    out = np.zeros((n, d))
+    for i0 in range(0, n, chunk):
+        (_, k1, k2), Rl, ra = _absmul_pairs(k, X[i0:i0 + chunk], Y, A, centre)
+        f = 2.0 if k.trait == ISOTROPIC else 1.0
+        c = 2.0 if k.trait == ISOTROPIC else 1.0
+        out[i0:i0 + chunk] = f * (np.abs(k1) @ np.abs(A) + c * np.einsum("ij,ijl->il", np.abs(k2) * ra, Rl))
+    return out.reshape(-1)
+
+
+def valgrad_absmul(k, X, Y, a, centre=None, chunk=64):
+    """grad_absmul for ValueGradientKernel blocks (valgrad_block; value entry first):
+      isotropic:   value  |k0| |a0| + 2 |k1| (|r|.|a_g|);    gradient entry l  2 |k1| |r_l| |a0| + the grad_absmul bound
+      dot product: value  |k0| |a0| + |k1| (|x|.|a_g|);      gradient entry l  |k1| |y_l| |a0|   + the grad_absmul bound"""
+    X = as_points(X).astype(np.float64); Y = as_points(X if Y is None else Y).astype(np.float64)
+    n, d = X.shape; m = Y.shape[0]
+    A = np.asarray(a, dtype=np.float64).reshape(m, d + 1)
+    a0, Ag = np.abs(A[:, 0]), A[:, 1:]
+    out = np.zeros((n, d + 1))
+    iso = k.trait == ISOTROPIC
+    f = 2.0 if iso else 1.0
+    for i0 in range(0, n, chunk):
+        (k0, k1, k2), Rl, ra = _absmul_pairs(k, X[i0:i0 + chunk], Y, Ag, centre)
+        k0, k1, k2 = np.abs(k0), np.abs(k1), np.abs(k2)
+        out[i0:i0 + chunk, 0] = k0 @ a0 + f * (k1 * ra).sum(axis=1)
+        out[i0:i0 + chunk, 1:] = (f * np.einsum("ij,ijl->il", k1 * a0[None, :], Rl)
+                                  + f * (k1 @ np.abs(Ag) + f * np.einsum("ij,ijl->il", k2 * ra, Rl)))
+    return out.reshape(-1)
+
+
 def grad_matrix(k: Kernel, X, Y=None, dtype=np.float64):
     X = as_points(X); Y = as_points(X if Y is None else Y)
     n, d = X.shape; m = Y.shape[0]

@@ -307,3 +307,37 @@ def test_cpu_baseline_object_leaves_denormals_alone():
     c_oracle.eq_rows(X, X, X[:, 0].copy(), 0, 64, lib)
     assert (tiny * 1.0)[0] != 0.0, "the CPU-baseline object switched on flush-to-zero"
     assert np.finfo(np.float32).smallest_subnormal > 0
+
+
+def test_grad_absmul_bounds_the_absolute_block_product():
+    """grad_absmul / valgrad_absmul (the row-wise error denominators of the gradient tests) against |M| |a| of the explicit block
+    matrices: an upper bound on every entry for both traits, a Power, a Lengthscale, a scale and a composite, and the expanded-form
+    variant (centre given) bounds the direct one.  Tight to within a factor of 2 on every entry where a block's diagonal cannot
+    cancel: the bound splits k1 I from the rank-one part, so it exceeds |M| |a| only by what k1 + 2 k2 r_l^2 (isotropic) or
+    k1 + k2 y_l x_l (dot product) loses to cancellation — which the kernels, forming k1 a_l and the rank-one term apart, do not
+    enjoy either.  Isotropic: a compact cloud (4 |k2| r_l^2 <= 2 |k1| / 3 keeps the ratio below 2); dot product: positive
+    coordinates (no cancellation at all)."""
+    rng = np.random.default_rng(17)
+    n, m, d = 5, 7, 4
+    kernels = [o.Kernel(o.EQ), o.Kernel(o.MATERNP, p=2, lengthscale=1.3, scale=1.7), o.Kernel(o.RQ, param=1.5),
+               o.Kernel(o.DOT, power=3), o.Kernel(o.EXPDOT, scale=0.5),
+               o.Composite(((o.Kernel(o.MATERN, param=1.3), o.Kernel(o.EQ, lengthscale=1.5)), (o.Kernel(o.CAUCHY),)), o.ISOTROPIC, 1.2)]
+    for wide in (True, False):
+        X0 = rng.standard_normal((n, d)); Y0 = 0.8 * rng.standard_normal((m, d)) + 0.2
+        for k in kernels:
+            iso = k.trait == o.ISOTROPIC
+            X, Y = X0, Y0
+            if not wide:                               # the tight case
+                X, Y = (0.1 * X0, 0.1 * Y0) if iso else (np.abs(X0) + 0.1, np.abs(Y0) + 0.1)
+            for vg in (0, 1):
+                a = rng.standard_normal(m * (d + vg))
+                M = (o.valgrad_matrix if vg else o.grad_matrix)(k, X, Y)
+                exact = np.abs(M) @ np.abs(a)
+                bound = (o.valgrad_absmul if vg else o.grad_absmul)(k, X, Y, a)
+                assert bound.shape == exact.shape
+                assert np.all(bound >= exact * (1 - 1e-13)), (k, vg, wide)
+                if not wide:
+                    assert np.all(bound <= 2 * exact), (k, vg, float(np.max(bound / exact)))
+                if iso:
+                    bx = (o.valgrad_absmul if vg else o.grad_absmul)(k, X, Y, a, centre=Y.mean(axis=0))
+                    assert np.all(bx >= bound * (1 - 1e-13)), (k, vg, wide)
