@@ -406,8 +406,14 @@ class BlockGramian(LazyOperator):
     def issymmetric(self):
         return self.inner.issymmetric()
 
+    def _lower(self):
+        return K.require_device_spec(self.g.k)   # GenericInput gradient kernels have no device path
+
+    def _entry(self):
+        return _ffi.lib().covgram_valgrad_mvm if self.value else _ffi.lib().covgram_grad_mvm
+
     def mul_(self, y, a, alpha=1.0, beta=0.0):
-        spec = K.require_device_spec(self.g.k)   # GenericInput gradient kernels have no device path
+        spec = self._lower()
         a = _vec_arg(a, self.shape[1], self.dtype, self.device, "a")
         if y.shape[0] != self.shape[0] or y.dtype != self.dtype or y.dim() != a.dim() or (a.dim() == 2 and y.shape[1] != a.shape[1]):
             raise _ffi.DimensionMismatch(_ffi.EINVAL, f"DimensionMismatch: y has shape {tuple(y.shape)}")
@@ -422,7 +428,7 @@ class BlockGramian(LazyOperator):
             a_c = a.t().contiguous()
             y_c = y.t().contiguous() if beta != 0.0 else torch.empty((nrhs, self.shape[0]), dtype=self.dtype, device=self.device)
         ctx = self.inner._px.ctx.bind_stream()
-        fn = _ffi.lib().covgram_valgrad_mvm if self.value else _ffi.lib().covgram_grad_mvm
+        fn = self._entry()
         _ffi.check(fn(ctx, _ffi.kref(spec), self.inner._px.handle, self.inner._py.handle, _ffi._P(a_c.data_ptr()), self.shape[1],
                       _ffi._P(y_c.data_ptr()), self.shape[0], nrhs, float(alpha), float(beta), _ffi.DEVICE))
         if a.dim() == 2:
@@ -430,6 +436,27 @@ class BlockGramian(LazyOperator):
         elif y_c is not y:
             y.copy_(y_c)
         return y
+
+
+class HessianGramian(BlockGramian):
+    """Gramian of a HessianKernel: the lazy (n d²)×(m d²) BlockFactorization whose blocks are ∂⁴k / ∂x∂x∂y∂y (src/hessian.jl:33-41),
+    applied in O(d²) per pair by covgram_hess_mvm.  Block vectors are point-major, entry i d² + a + b d."""
+
+    def __init__(self, g, x, y=None):
+        self.g = g
+        self.value = False
+        self.inner = Gramian(g.k, x, y)
+        n, m = self.inner.shape
+        self.d = d = self.inner.x.shape[1]
+        self.block = d * d
+        self.shape = (n * self.block, m * self.block)
+        self.dtype, self.device = self.inner.dtype, self.inner.device
+
+    def _lower(self):
+        return K.require_hessian_spec(self.g.k, self.d)
+
+    def _entry(self):
+        return _ffi.lib().covgram_hess_mvm
 
 
 class _ToeplitzBase(LazyOperator):
@@ -891,6 +918,8 @@ def gramian(k, x=None, y=None, trait: Optional[K.InputTrait] = None):
 
     if isinstance(k, (K.GradientKernel, K.ValueGradientKernel)):   # src/gramian.jl:120-123
         return BlockGramian(k, x, None if same else y)
+    if isinstance(k, K.HessianKernel):
+        return HessianGramian(k, x, None if same else y)
     if isinstance(k, K.SeparableKernel):
         return SeparableGramian(k, x, None if same else y)
 

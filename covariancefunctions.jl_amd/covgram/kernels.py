@@ -520,6 +520,14 @@ class ValueGradientKernel(MultiKernel):
         self.input_trait = input_trait(k) if it is None else it
 
 
+class HessianKernel(MultiKernel):
+    """src/hessian.jl:2-23: the d²×d² block kernel ∂x ∂xᵀ ∂y ∂yᵀ k(x, y); carries input_trait(k) (src/hessian.jl:7)."""
+
+    def __init__(self, k, it: Optional[InputTrait] = None):
+        self.k = k
+        self.input_trait = input_trait(k) if it is None else it
+
+
 # ----------------------------------------------------------------------------------------------
 # input_trait (src/properties.jl:39-45, gradient.jl:16) — user-extensible like the reference
 # ----------------------------------------------------------------------------------------------
@@ -537,7 +545,7 @@ def input_trait(k) -> InputTrait:
     for t, tr in _USER_TRAITS.items():
         if isinstance(t, type) and isinstance(k, t):
             return tr
-    if isinstance(k, (Product, Sum, Power, GradientKernel, ValueGradientKernel)):
+    if isinstance(k, (Product, Sum, Power, GradientKernel, ValueGradientKernel, HessianKernel)):
         return k.input_trait
     if isinstance(k, (Dot, ExponentialDot, AsinDot)):
         return DotProductInput()
@@ -721,4 +729,27 @@ def require_device_spec(k):
             _ffi.EUNSUPPORTED,
             f"{type(k).__name__} has input_trait {input_trait(k)!r} / no compiled device profile; the reference would run its "
             "generic threaded loop (src/gramian.jl:78-87) here — this engine has no CPU fallback")
+    return spec
+
+
+HESSIAN_MAX_D = 32
+_HESSIAN_FAMILIES = (_ffi.EQ, _ffi.RQ, _ffi.CAUCHY, _ffi.IMQ, _ffi.DOT, _ffi.EXPDOT)
+
+
+def require_hessian_spec(k, d: Optional[int] = None):
+    """The covgram_kernel that covgram_hess_mvm runs for HessianKernel(k), checked on the host before any device call: a single
+    profile whose derivatives up to the fourth have closed forms in the library (EQ, RQ, Cauchy, IMQ with Lengthscale and Constant
+    factors; ExponentialDot, Dot), no Power wrapper, d <= 32.  Everything else raises UnsupportedKernel naming the kernel."""
+    name = type(k).__name__
+    spec = device_spec(k)
+    if spec is None or not isinstance(spec, _ffi.covgram_kernel):
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"HessianKernel({name}): only single profiles have a Hessian device path, "
+                                                        "not composites or GenericInput kernels")
+    if spec.family not in _HESSIAN_FAMILIES:
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"HessianKernel({name}): no closed-form fourth derivative is compiled for this profile "
+                                                        "(supported: EQ, RQ, Cauchy, InverseMultiQuadratic, ExponentialDot, Dot)")
+    if spec.power != 1:
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"HessianKernel({name}): Power wrappers (exponent {spec.power}) have no Hessian device path")
+    if d is not None and d > HESSIAN_MAX_D:
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"HessianKernel({name}): d = {d} exceeds the compiled maximum {HESSIAN_MAX_D}")
     return spec

@@ -14,6 +14,7 @@
 #include "grad_mvm.hpp"
 #include "grad_bcast.hpp"
 #include "grad_wide.hpp"
+#include "hess_mvm.hpp"
 
 namespace covgram {
 
@@ -56,6 +57,24 @@ dense_launch_fn dense_launcher(int family) {
         launch_dense_family_5, launch_dense_family_6, launch_dense_family_7, launch_dense_family_8, launch_dense_family_9,
         launch_dense_family_10, launch_dense_family_11, launch_dense_family_12};
     return (family >= 0 && family < NUM_TU_FAMILIES) ? t[family] : nullptr;
+}
+// Hessian-kernel MVM (hess_fam.hip: one translation unit per family that has one)
+int launch_hess_family_0(const HessArgs&, int dtype);
+int launch_hess_family_2(const HessArgs&, int dtype);
+int launch_hess_family_4(const HessArgs&, int dtype);
+int launch_hess_family_5(const HessArgs&, int dtype);
+int launch_hess_family_7(const HessArgs&, int dtype);
+int launch_hess_family_8(const HessArgs&, int dtype);
+hess_launch_fn hess_launcher(int family) {
+    switch (family) {
+        case COVGRAM_EQ: return launch_hess_family_0;
+        case COVGRAM_RQ: return launch_hess_family_2;
+        case COVGRAM_CAUCHY: return launch_hess_family_4;
+        case COVGRAM_IMQ: return launch_hess_family_5;
+        case COVGRAM_DOT: return launch_hess_family_7;
+        case COVGRAM_EXPDOT: return launch_hess_family_8;
+        default: return nullptr;
+    }
 }
 dense_launch_fn dense_wide_launcher(int family) {
     static const dense_launch_fn t[NUM_TU_FAMILIES] = {
@@ -617,6 +636,7 @@ int covgram_ctx_get_info(covgram_ctx* ctx, const char* key, int64_t* value) {
     else if (!strcmp(key, "last_grad_bcast")) *value = ctx->last_grad_bcast;
     else if (!strcmp(key, "last_grad_path")) *value = ctx->last_grad_path;
     else if (!strcmp(key, "last_grad_jsplit")) *value = ctx->last_grad_jsplit;
+    else if (!strcmp(key, "last_hess_path")) *value = ctx->last_hess_path;
     else if (!strcmp(key, "last_sum_fused")) *value = ctx->last_sum_fused;
     else if (!strcmp(key, "last_mfma_instance")) *value = ctx->last_mfma_instance;
     else if (!strcmp(key, "last_mfma_sym_rt")) *value = ctx->last_mfma_sym_rt;
@@ -1587,6 +1607,107 @@ int covgram_grad_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram_po
 int covgram_valgrad_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, const void* a, int64_t lda,
                         void* y, int64_t ldy, int32_t nrhs, double alpha, double beta, int32_t loc) {
     return grad_mvm_impl(ctx, k, X, Y, a, lda, y, ldy, nrhs, alpha, beta, loc, 1);
+}
+
+// Hessian-kernel Gramian (n d^2 x m d^2): hess_mvm.hpp.  Single profiles with closed-form derivatives up to the fourth only.
+int covgram_hess_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, const void* a, int64_t lda,
+                     void* y, int64_t ldy, int32_t nrhs, double alpha, double beta, int32_t loc) {
+    int rc = check_pair(ctx, X, Y);
+    if (rc) return rc;
+    CG_REQUIRE(k != nullptr, COVGRAM_EINVAL, "kernel is NULL");
+    static const char* const names[COVGRAM_NFAMILY] = {"ExponentiatedQuadratic", "Exponential", "RationalQuadratic", "GammaExponential", "Cauchy",
+                                                       "InverseMultiQuadratic", "MaternP", "Dot", "ExponentialDot", "Matern", "AsinDot"};
+    CG_REQUIRE(k->family != COVGRAM_COMPOSITE, COVGRAM_EUNSUPPORTED, "HessianKernel of a composite kernel (Sum / Product / Power) has no device path");
+    CG_REQUIRE(k->family >= 0 && k->family < COVGRAM_NFAMILY, COVGRAM_EUNSUPPORTED, "unknown kernel family %d", k->family);
+    CG_REQUIRE(hess_family_ok(k->family), COVGRAM_EUNSUPPORTED, "HessianKernel(%s) has no device path (no closed-form fourth derivative compiled)", names[k->family]);
+    CG_REQUIRE(k->power == 1, COVGRAM_EUNSUPPORTED, "HessianKernel(%s^%d): Power wrappers have no device path", names[k->family], k->power);
+    const int d = X->d;
+    CG_REQUIRE(d <= HESS_MAX_D, COVGRAM_EUNSUPPORTED, "HessianKernel(%s): d = %d exceeds the compiled maximum %d", names[k->family], d, HESS_MAX_D);
+    CG_REQUIRE(nrhs >= 1, COVGRAM_EINVAL, "nrhs must be >= 1");
+    const int64_t n = X->n, m = Y->n, bd = (int64_t)d * d;
+    CG_REQUIRE(lda >= m * bd && ldy >= n * bd, COVGRAM_EINVAL, "lda / ldy smaller than the block vectors (%lld, %lld)", (long long)(m * bd), (long long)(n * bd));
+    CG_REQUIRE((a != nullptr || m == 0) && (y != nullptr || n == 0), COVGRAM_EINVAL, "a or y is NULL");
+    const int dtype = X->dtype;
+    const size_t ts = dtype_size(dtype);
+    HostKernel hk;
+    rc = make_host_kernel(k, dtype, true, &hk);
+    if (rc) return rc;
+    hess_launch_fn launch = hess_launcher(hk.tu_family);
+    CG_REQUIRE(launch != nullptr, COVGRAM_EUNSUPPORTED, "HessianKernel(%s) has no device path", names[k->family]);
+    if (loc == COVGRAM_DEVICE) {   // a and y may overlap (include/covgram.h): everything below reads a private copy of a
+        rc = unalias_input(ctx, &a, &lda, m * bd, nrhs, y, ldy, n * bd, ts);
+        if (rc) return rc;
+    }
+    CG_DEVICE(ctx);
+    ctx->last_hess_path = 0;
+    if (n == 0) return COVGRAM_OK;
+
+    const void* a_all = a;
+    void* y_all = y;
+    int64_t lda_d = lda, ldy_d = ldy;
+    if (loc == COVGRAM_HOST) {
+        void *sa, *sy;
+        rc = ws_reserve(ctx, 2, (size_t)std::max<int64_t>(m, 1) * bd * nrhs * ts, &sa); if (rc) return rc;
+        rc = ws_reserve(ctx, 3, (size_t)n * bd * nrhs * ts, &sy); if (rc) return rc;
+        if (m > 0) CG_CHECK_HIP(hipMemcpy2DAsync(sa, (size_t)m * bd * ts, a, (size_t)lda * ts, (size_t)m * bd * ts, nrhs, hipMemcpyHostToDevice, ctx->stream));
+        if (beta != 0.0) CG_CHECK_HIP(hipMemcpy2DAsync(sy, (size_t)n * bd * ts, y, (size_t)ldy * ts, (size_t)n * bd * ts, nrhs, hipMemcpyHostToDevice, ctx->stream));
+        a_all = sa; y_all = sy; lda_d = m * bd; ldy_d = n * bd;
+    }
+    const bool iso = (k->trait == COVGRAM_ISOTROPIC);
+    const int D = hess_pad_dim(d);
+    const int rec = hess_rec(D);
+    // d^4 k / dx dx dy dy in the pre-scaled coordinates gamma (x - c): gamma^4 by the chain rule (dot product: gamma = 1)
+    const double alpha_eff = alpha * hk.kp.scale * (iso ? hk.kp.gamma2 * hk.kp.gamma2 : 1.0);
+    const int64_t total = n * bd;
+    // Column split: a workgroup holds 256 / D row points, so small n leaves most of the chip idle; split the columns over up to
+    // ~8 workgroups per CU, at least 4 staged chunks each, with the partial slabs (split x n d^2 scalars) within 256 MB
+    const int ppw = HESS_THREADS / D;
+    const int64_t rowwgs = (n + ppw - 1) / ppw;
+    const int64_t minchunk = 4 * (int64_t)hess_jc(D, (int)ts);
+    int64_t split = std::max<int64_t>(1, ((int64_t)ctx->num_cus * 8 + rowwgs - 1) / rowwgs);
+    split = std::min(split, std::max<int64_t>(1, m / minchunk));
+    split = std::min(split, std::max<int64_t>(1, (int64_t)(256.0e6 / ((double)total * ts))));
+    if (ctx->jsplit > 0) split = std::min<int64_t>(ctx->jsplit, std::max<int64_t>(1, m));
+    int64_t jchunk = std::max<int64_t>(1, (m + split - 1) / split);
+    const int jsplit = m > 0 ? (int)((m + jchunk - 1) / jchunk) : 0;
+    void *P = nullptr, *slab = nullptr;
+    if (m > 0) { rc = ws_reserve(ctx, 0, (size_t)m * rec * ts, &P); if (rc) return rc; }
+    if (jsplit > 1) { rc = ws_reserve(ctx, 1, (size_t)jsplit * total * ts, &slab); if (rc) return rc; }
+    const void* Cn = iso ? Y->center : nullptr;
+    for (int c0 = 0; c0 < nrhs; ++c0) {
+        const void* a_dev = (const char*)a_all + (size_t)c0 * lda_d * ts;
+        void* y_dev = (char*)y_all + (size_t)c0 * ldy_d * ts;
+        if (m > 0) {
+            const int64_t pe = m * (int64_t)rec;
+            if (dtype == COVGRAM_F32)
+                hipLaunchKernelGGL(hess_pack_kernel<float>, dim3((unsigned)((pe + 255) / 256)), dim3(256), 0, ctx->stream, (const float*)Y->dptr, m, d,
+                                   (const float*)a_dev, (float*)P, D, (float)hk.kp.gamma, (const float*)Cn);
+            else
+                hipLaunchKernelGGL(hess_pack_kernel<double>, dim3((unsigned)((pe + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)Y->dptr, m, d,
+                                   (const double*)a_dev, (double*)P, D, hk.kp.gamma, (const double*)Cn);
+            HessArgs ha;
+            ha.X = X->dptr; ha.n = n; ha.d = d; ha.P = P; ha.m = m; ha.out = jsplit > 1 ? slab : y_dev; ha.Dpad = D; ha.jchunk = jchunk; ha.jsplit = jsplit;
+            ha.C = Cn; ha.alpha = alpha_eff; ha.beta = beta; ha.hk = &hk; ha.stream = ctx->stream;
+            auto* tm = timer_next(ctx);
+            if (tm) (void)hipEventRecord(tm->first, ctx->stream);
+            rc = launch(ha, dtype); if (rc) return rc;
+            if (tm) (void)hipEventRecord(tm->second, ctx->stream);
+            ctx->last_hess_path = 1;
+        }
+        if (jsplit != 1) {   // several column chunks: fixed-order sum of their slabs; no columns: y <- beta y
+            const dim3 rg((unsigned)((total + 255) / 256));
+            if (dtype == COVGRAM_F32)
+                hipLaunchKernelGGL(hess_reduce_kernel<float>, rg, dim3(256), 0, ctx->stream, (const float*)slab, jsplit, total, (float*)y_dev, (float)alpha_eff, (float)beta);
+            else
+                hipLaunchKernelGGL(hess_reduce_kernel<double>, rg, dim3(256), 0, ctx->stream, (const double*)slab, jsplit, total, (double*)y_dev, alpha_eff, beta);
+        }
+    }
+    CG_CHECK_HIP(hipGetLastError());
+    if (loc == COVGRAM_HOST) {
+        CG_CHECK_HIP(hipMemcpy2DAsync(y, (size_t)ldy * ts, y_all, (size_t)n * bd * ts, (size_t)n * bd * ts, nrhs, hipMemcpyDeviceToHost, ctx->stream));
+        CG_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return COVGRAM_OK;
 }
 
 // debugging / test hook: the double-precision parameter block the device kernels receive.

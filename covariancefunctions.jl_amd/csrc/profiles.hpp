@@ -749,6 +749,56 @@ struct DPhi<COVGRAM_EXPDOT, T> {
     }
 };
 
+// ---- (phi'', phi''', phi'''') w.r.t. the pre-scaled argument: the jet of the Hessian-kernel blocks (hess_mvm.hpp) ----------
+// Only the profiles whose derivatives up to the fourth have short closed forms; every other family has no Hessian MVM.
+template <int FAM, typename T>
+struct DPhi4;
+
+template <typename T>
+struct DPhi4<COVGRAM_EQ, T> {
+    static __device__ __forceinline__ void eval(T s, const KParams<T>&, T& f2, T& f3, T& f4) {
+        T v;
+        if constexpr (sizeof(T) == 8) v = eq_exp_neg_half(s);
+        else v = cg_exp2(s * (T)-0.72134752044448170368);
+        f2 = (T)0.25 * v; f3 = (T)-0.125 * v; f4 = (T)0.0625 * v;
+    }
+};
+template <typename T>
+struct DPhi4<COVGRAM_RQ, T> {
+    static __device__ __forceinline__ void eval(T s, const KParams<T>& kp, T& f2, T& f3, T& f4) {
+        const T a = kp.param, h = (T)0.5 * kp.c0;            // c0 = 1 / (2 alpha)
+        const T u = cg_fma(s, kp.c0, (T)1);
+        const T iu = cg_rcp(u);
+        const T v = rq_pow(u, a);
+        f2 = (a + (T)1) * h * v * iu * iu;                    // (a+1)/(4a) u^(-a-2)
+        f3 = -(a + (T)2) * kp.c0 * f2 * iu;                   // -(a+1)(a+2)/(8a^2) u^(-a-3)
+        f4 = -(a + (T)3) * kp.c0 * f3 * iu;                   // (a+1)(a+2)(a+3)/(16a^3) u^(-a-4)
+    }
+};
+template <typename T>
+struct DPhi4<COVGRAM_CAUCHY, T> {
+    static __device__ __forceinline__ void eval(T s, const KParams<T>&, T& f2, T& f3, T& f4) {
+        const T v = cg_rcp((T)1 + s);
+        f2 = (T)2 * v * v * v; f3 = (T)-3 * f2 * v; f4 = (T)-4 * f3 * v;
+    }
+};
+template <typename T>
+struct DPhi4<COVGRAM_IMQ, T> {
+    static __device__ __forceinline__ void eval(T s, const KParams<T>& kp, T& f2, T& f3, T& f4) {
+        const T iu = cg_rcp(s + kp.param);
+        const T v = cg_rsqrt(s + kp.param);
+        f2 = (T)0.75 * v * iu * iu; f3 = (T)-2.5 * f2 * iu; f4 = (T)-3.5 * f3 * iu;   // 3/4, -15/8, 105/16
+    }
+};
+template <typename T>
+struct DPhi4<COVGRAM_DOT, T> {
+    static __device__ __forceinline__ void eval(T, const KParams<T>&, T& f2, T& f3, T& f4) { f2 = (T)0; f3 = (T)0; f4 = (T)0; }
+};
+template <typename T>
+struct DPhi4<COVGRAM_EXPDOT, T> {
+    static __device__ __forceinline__ void eval(T s, const KParams<T>&, T& f2, T& f3, T& f4) { f2 = cg_exp(s); f3 = f2; f4 = f2; }
+};
+
 // (phi^q, (phi^q)', (phi^q)'') from (phi, phi', phi'')
 template <typename T>
 __device__ __forceinline__ void power_jet(int q, T& v, T& d1, T& d2) {

@@ -21,7 +21,7 @@ module CovGram
 
 using LinearAlgebra
 using CovarianceFunctions
-using CovarianceFunctions: Gramian, GradientKernel, ValueGradientKernel, IsotropicInput, DotProductInput, StationaryInput,
+using CovarianceFunctions: Gramian, GradientKernel, ValueGradientKernel, HessianKernel, IsotropicInput, DotProductInput, StationaryInput,
                            GenericInput, input_trait, EQ, RQ, Exp, γExp, Cauchy, InverseMultiQuadratic, MaternP, Dot,
                            ExponentialDot, Lengthscale, Power, Product, Sum, Constant, SeparableProduct, SeparableKernel, LazyGrid, FiniteBasis
 import CovarianceFunctions: gramian
@@ -229,6 +229,10 @@ function device_blockmul!(sym::Symbol, y::StridedVecOrMat{T}, G::Gramian, a::Str
         check(ccall((:covgram_grad_mvm, libcovgram), Cint,
                     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int32, Float64, Float64, Int32),
                     ctx(), kref(spec), X.handle, Y.handle, a, lda, y, ldy, nrhs, Float64(α), Float64(β), HOST))
+    elseif sym === :hess   # src/hessian.jl:33-41, element mul! :125-190 / :227-275: blocks of d^2, entry a + b d (vec of a d x d matrix)
+        check(ccall((:covgram_hess_mvm, libcovgram), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int32, Float64, Float64, Int32),
+                    ctx(), kref(spec), X.handle, Y.handle, a, lda, y, ldy, nrhs, Float64(α), Float64(β), HOST))
     else   # src/gradient.jl:400-474 (ValueGradientKernel), block mul! :319-351: blocks of d+1, value component first
         check(ccall((:covgram_valgrad_mvm, libcovgram), Cint,
                     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int32, Float64, Float64, Int32),
@@ -264,6 +268,27 @@ function LinearAlgebra.mul!(Y::StridedMatrix{T}, B::BlockFactorizations.BlockFac
     spec = device_kernel_for(G.k.k)
     spec === nothing ? invoke(mul!, Tuple{AbstractMatrix, BlockFactorizations.BlockFactorization, AbstractMatrix, Real, Real}, Y, B, A, α, β) :
                        device_blockmul!(:valgrad, Y, G, A, α, β, spec)
+end
+
+# --- src/hessian.jl: HessianKernel Gramians -> covgram_hess_mvm.  Device path: ONE profile of EQ / RQ / Cauchy / IMQ / Dot / ExponentialDot
+# without a Power wrapper and d <= 32 (include/covgram.h); everything else keeps the reference's own blockmul!
+hessian_spec(k, d::Integer) = begin
+    spec = device_kernel_for(k)
+    (spec isa CKernel && spec.family in (Int32(0), Int32(2), Int32(4), Int32(5), Int32(7), Int32(8)) && spec.power == 1 && d <= 32) ? spec : nothing
+end
+function LinearAlgebra.mul!(y::StridedVector{T}, B::BlockFactorizations.BlockFactorization{T, <:Gramian{<:Any, <:HessianKernel}},
+                            a::StridedVector{T}, α::Real = 1, β::Real = 0) where {T <: DevFloat}
+    G = B.A
+    spec = hessian_spec(G.k.k, length(first(G.x)))
+    spec === nothing ? invoke(mul!, Tuple{AbstractVector, BlockFactorizations.BlockFactorization, AbstractVector, Real, Real}, y, B, a, α, β) :
+                       device_blockmul!(:hess, y, G, a, α, β, spec)
+end
+function LinearAlgebra.mul!(Y::StridedMatrix{T}, B::BlockFactorizations.BlockFactorization{T, <:Gramian{<:Any, <:HessianKernel}},
+                            A::StridedMatrix{T}, α::Real = 1, β::Real = 0) where {T <: DevFloat}
+    G = B.A
+    spec = hessian_spec(G.k.k, length(first(G.x)))
+    spec === nothing ? invoke(mul!, Tuple{AbstractMatrix, BlockFactorizations.BlockFactorization, AbstractMatrix, Real, Real}, Y, B, A, α, β) :
+                       device_blockmul!(:hess, Y, G, A, α, β, spec)
 end
 
 # --- src/separable.jl:38-42: mul!(y, G::Gramian{<:AbstractMatrix, <:SeparableKernel}, x) on vectors of vectors -----------------

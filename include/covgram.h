@@ -14,6 +14,7 @@
  *   covgram_grad_mvm       replaces  BlockFactorizations.blockmul!(y, G::Gramian, x, α, β)        src/gramian.jl:241-257
  *                          with the  GradientKernelElement mul! (isotropic / dot-product)         src/gradient.jl:86-92, 109-115
  *   covgram_valgrad_mvm    the same  blockmul! with the ValueGradientKernel element                       src/gradient.jl:319-351, 400-474
+ *   covgram_hess_mvm       the same  blockmul! with the HessianKernel elements' O(d^2) mul!             src/hessian.jl:125-190, 227-275
  *   covgram_toeplitz_*     replaces  mul!(y, ::SymmetricToeplitz/Toeplitz/Circulant, a, α, β) of ToeplitzMatrices 0.7.1 as
  *                          constructed by gramian(k, x::StepRangeLen, y::StepRangeLen)            src/gramian.jl:167-189
  *   covgram_toeplitz_durbin / _levinson / _trench  replace durbin! / levinson! / trench!             src/toeplitz.jl:12-111
@@ -48,7 +49,8 @@ extern "C" {
 #define COVGRAM_VERSION 113 /* 0.1.1: covgram_kron_mvm, covgram_grad_mvm and covgram_valgrad_mvm take (lda, ldy, nrhs); 111 adds
                                covgram_cg_step_shifted; 112: covgram_mvm_sym_supported takes `world` (the symmetric partial form's
                                column-sum slab depends on it), fp32 direct-difference symmetric partials; 113: the communicator
-                               (covgram_comm_*), covgram_mvm_sharded, covgram_mvm_sym_allreduce.
+                               (covgram_comm_*), covgram_mvm_sharded, covgram_mvm_sym_allreduce.  Added since, backward
+                               compatibly (no version step): covgram_hess_mvm and the info key "last_hess_path".
                                A binding checks covgram_version() against the header it mirrors at load time */
 
 typedef enum covgram_status {
@@ -185,7 +187,7 @@ int covgram_ctx_get_stream(covgram_ctx* ctx, void** hip_stream);
 int covgram_ctx_set_option(covgram_ctx* ctx, const char* key, int64_t value);
 /* read-only facts: "last_dense_path" (which kernel the last covgram_mvm ran: 0 none yet, 1 lane-per-row direct differences,
  * 2 matrix cores, 3 wide rows, 4 Gramian(Dot(), x, y) factored as X (Y' a)), "last_mfma_lds" (1: that matrix-core MVM shared its column tiles through LDS), "last_mfma_sym" (1: the last dense
- * MVM ran the symmetric upper-triangle kernel), "last_dense_sym" (1: it ran a direct-difference symmetric kernel, fp64 or fp32), "last_inkernel_reduce" (1: the last dense kernel summed its own split-J slab), "last_grad_expand" (1: the last gradient MVM ran the expanded form), "last_grad_bcast" (waves per workgroup of the broadcast kernel if the last gradient MVM ran it, else 0), "last_grad_path" (which kernels the last gradient or value-gradient MVM ran, as bits: 1 = the lane-per-row kernel, 2 = its two-column pass, 4 = the panel path (grad_wide), 8 = more than one panel, 16 = the panel path split over z slices with the separate reduce, 32 = the lane-per-row kernel with a column split > 1 and the slab reduce; 0 = no block kernel (n = 0 or m = 0); a Sum split term by term reports its last term), "last_grad_jsplit" (the column split of the last gradient MVM's lane-per-row launch, 0 if it did not run one), "last_sum_fused" (1: the last covgram_mvm ran a Sum on the one-pass kernels), "last_mfma_instance" (which instance of the matrix-core EQ kernels the last launch was: the template arguments of dense_mfma_eq_kernel as K2 1e5 + RT 1e4 + WPB 1e3 + LDS 100 + STAMP 10 + FMT, -(K2 10 + FMT) for the symmetric kernel, 0 otherwise — bench.py checks its recorded PMC pass against it), "last_dense_bcast" (1: the last fp64 dense MVM ran a register-broadcast kernel), "last_mfma_f16" (1: the last general matrix-core EQ MVM ran the fp16 two-way split), "last_jsplit" (the column split of the last lane-per-row dense launch), "last_kron_path" (which kernels the last covgram_kron_mvm ran, as bits: 1 = the fused last-two-modes pass, 2 = the single-mode kernel, 4 = the last-mode kernel, 8 = a rocBLAS GEMM (a factor side >= 1024, >= 256 with >= 2 GFLOP, or a shape the kernels refuse), 16 = two small trailing factors multiplied out first), "num_cus", "last_clock_khz" (median shader clock over the workgroups of the last
+ * MVM ran the symmetric upper-triangle kernel), "last_dense_sym" (1: it ran a direct-difference symmetric kernel, fp64 or fp32), "last_inkernel_reduce" (1: the last dense kernel summed its own split-J slab), "last_grad_expand" (1: the last gradient MVM ran the expanded form), "last_grad_bcast" (waves per workgroup of the broadcast kernel if the last gradient MVM ran it, else 0), "last_grad_path" (which kernels the last gradient or value-gradient MVM ran, as bits: 1 = the lane-per-row kernel, 2 = its two-column pass, 4 = the panel path (grad_wide), 8 = more than one panel, 16 = the panel path split over z slices with the separate reduce, 32 = the lane-per-row kernel with a column split > 1 and the slab reduce; 0 = no block kernel (n = 0 or m = 0); a Sum split term by term reports its last term), "last_grad_jsplit" (the column split of the last gradient MVM's lane-per-row launch, 0 if it did not run one), "last_hess_path" (0 = no Hessian MVM yet or one without rows / columns, 1 = the last covgram_hess_mvm ran its block kernel, csrc/hess_mvm.hpp), "last_sum_fused" (1: the last covgram_mvm ran a Sum on the one-pass kernels), "last_mfma_instance" (which instance of the matrix-core EQ kernels the last launch was: the template arguments of dense_mfma_eq_kernel as K2 1e5 + RT 1e4 + WPB 1e3 + LDS 100 + STAMP 10 + FMT, -(K2 10 + FMT) for the symmetric kernel, 0 otherwise — bench.py checks its recorded PMC pass against it), "last_dense_bcast" (1: the last fp64 dense MVM ran a register-broadcast kernel), "last_mfma_f16" (1: the last general matrix-core EQ MVM ran the fp16 two-way split), "last_jsplit" (the column split of the last lane-per-row dense launch), "last_kron_path" (which kernels the last covgram_kron_mvm ran, as bits: 1 = the fused last-two-modes pass, 2 = the single-mode kernel, 4 = the last-mode kernel, 8 = a rocBLAS GEMM (a factor side >= 1024, >= 256 with >= 2 GFLOP, or a shape the kernels refuse), 16 = two small trailing factors multiplied out first), "num_cus", "last_clock_khz" (median shader clock over the workgroups of the last
  * launch made with "mfma_stamp" = 1; synchronises the stream; 0 = no stamped launch yet). */
 int covgram_ctx_get_info(covgram_ctx* ctx, const char* key, int64_t* value);
 int covgram_sync(covgram_ctx* ctx);
@@ -281,6 +283,18 @@ int covgram_grad_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram_po
  * Aliasing (covgram_grad_mvm and covgram_valgrad_mvm): a and y may overlap in any way; a is then read from a private copy. */
 int covgram_valgrad_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, const void* a,
                         int64_t lda, void* y, int64_t ldy, int32_t nrhs, double alpha, double beta, int32_t loc);
+
+/* Hessian-kernel Gramian (n d^2 × m d^2), src/hessian.jl:33-41: block (i,j) is the d^2 × d^2 matrix
+ *     T[(a,b),(c,e)] = d^4 k(x_i, y_j) / dx_a dx_b dy_c dy_e,
+ * applied in O(d^2) per pair (src/hessian.jl:125-190 isotropic, :227-275 dot product), never formed.  Flat point-major block vectors:
+ * entry i*d^2 + a + b*d is component (a, b) of point i (the reference's vec of a d × d matrix); right-hand sides as for covgram_grad_mvm
+ * (lda >= m*d^2, ldy >= n*d^2, nrhs columns).  Device path: single profiles whose derivatives up to the fourth have closed forms —
+ * EQ, RQ, Cauchy, IMQ with lengthscale and scale; ExponentialDot and Dot (a zero matrix: y <- beta y) — and d <= 32.  A Power wrapper,
+ * composites and every other family return COVGRAM_EUNSUPPORTED with a message that names the kernel.  Option "time_kernels" brackets
+ * the block kernel; info key "last_hess_path" reports it.
+ * Aliasing: a and y may overlap in any way; a is then read from a private copy. */
+int covgram_hess_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, const void* a,
+                     int64_t lda, void* y, int64_t ldy, int32_t nrhs, double alpha, double beta, int32_t loc);
 
 /* Toeplitz T[i,j] = vc[i-j] (i >= j), vr[j-i] (i < j); vr == NULL: symmetric (vr = vc, m = n).
  * circulant != 0: T[i,j] = vc[(i-j) mod n] (vr must be NULL).  The spectrum of the circulant embedding
