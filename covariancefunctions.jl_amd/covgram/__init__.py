@@ -15,11 +15,11 @@ from .kernels import (AbstractKernel, MercerKernel, StationaryKernel, IsotropicK
                       ExponentiatedQuadratic, EQ, RationalQuadratic, RQ, Exponential, Exp, GammaExponential, GammaExp,
                       Cauchy, InverseMultiQuadratic, MaternP, Matern, Dot, ExponentialDot, FiniteBasis, Product, Sum, Power,
                       Lengthscale, ARD, ScaledInputKernel, Warped, Periodic, VerticalRescaling, CosineKernel, Cosine, Cos, Line, Polynomial, Poly, NeuralNetwork, NN, AsinDot,
-                      SeparableProduct, separable, SeparableKernel, Separable, GradientKernel, ValueGradientKernel, HessianKernel, InputTrait,
+                      SeparableProduct, separable, SeparableKernel, Separable, GradientKernel, ValueGradientKernel, HessianKernel, ValueGradientHessianKernel, InputTrait,
                       GenericInput, IsotropicInput, DotProductInput, StationaryInput, StationaryLinearFunctionalInput,
                       PeriodicInput, input_trait, register_input_trait, ismercer, isstationary, isisotropic, isdot,
-                      device_spec, require_hessian_spec, DomainError)
-from .gramian import (Gramian, BlockGramian, HessianGramian, SymmetricToeplitz, Toeplitz, Circulant, KroneckerProduct, kronecker,
+                      device_spec, require_hessian_spec, require_vgh_spec, DomainError)
+from .gramian import (Gramian, BlockGramian, HessianGramian, ValueGradientHessianGramian, SymmetricToeplitz, Toeplitz, Circulant, KroneckerProduct, kronecker,
                       SeparableGramian, LazyMatrixProduct, LazyMatrixSum, ScaledOperator, LinearMapBlockGramian, CosineBlockGramian, PointJacobianBlockGramian, Fill, LazyOperator, LazyGrid, StepRangeLen,
                       srange, gramian, mul_, get_ctx, set_option, get_info, kernel_time)
 from .dist import ShardedGramian, shard_bounds

@@ -101,6 +101,7 @@ PROTOTYPES = {
     "covgram_grad_mvm": (C.c_int, [_P, _KP, _P, _P, _P, _I64, _P, _I64, _I32, _D, _D, _I32]),
     "covgram_valgrad_mvm": (C.c_int, [_P, _KP, _P, _P, _P, _I64, _P, _I64, _I32, _D, _D, _I32]),
     "covgram_hess_mvm": (C.c_int, [_P, _KP, _P, _P, _P, _I64, _P, _I64, _I32, _D, _D, _I32]),
+    "covgram_valgradhess_mvm": (C.c_int, [_P, _KP, _P, _P, _P, _I64, _P, _I64, _I32, _D, _D, _I32]),
     "covgram_mvm_sym_supported": (C.c_int, [_P, _KP, _P, _I32, C.POINTER(C.c_int32)]),
     "covgram_mvm_sym_partial": (C.c_int, [_P, _KP, _P, _P, _P, _I32, _I32]),
     "covgram_comm_unique_id": (C.c_int, [_P, _I64]),

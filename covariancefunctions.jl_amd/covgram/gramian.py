@@ -459,6 +459,28 @@ class HessianGramian(BlockGramian):
         return _ffi.lib().covgram_hess_mvm
 
 
+class ValueGradientHessianGramian(BlockGramian):
+    """Gramian of a ValueGradientHessianKernel: the lazy n(1+d+d²)×m(1+d+d²) BlockFactorization whose blocks are the joint covariance of
+    [f, ∂f, vec ∂²f] (src/hessian.jl:301-325), applied in O(d²) per pair by covgram_valgradhess_mvm.  Block vectors are point-major:
+    entry i(1+d+d²) the value, then the d gradient components, then Hessian component (a, b) at 1 + d + a + b d."""
+
+    def __init__(self, g, x, y=None):
+        self.g = g
+        self.value = False
+        self.inner = Gramian(g.k, x, y)
+        n, m = self.inner.shape
+        self.d = d = self.inner.x.shape[1]
+        self.block = 1 + d + d * d
+        self.shape = (n * self.block, m * self.block)
+        self.dtype, self.device = self.inner.dtype, self.inner.device
+
+    def _lower(self):
+        return K.require_vgh_spec(self.g.k, self.d)
+
+    def _entry(self):
+        return _ffi.lib().covgram_valgradhess_mvm
+
+
 class _ToeplitzBase(LazyOperator):
     def __init__(self, vc: torch.Tensor, vr: Optional[torch.Tensor], circulant: bool):
         self.vc = vc.contiguous()
@@ -920,6 +942,8 @@ def gramian(k, x=None, y=None, trait: Optional[K.InputTrait] = None):
         return BlockGramian(k, x, None if same else y)
     if isinstance(k, K.HessianKernel):
         return HessianGramian(k, x, None if same else y)
+    if isinstance(k, K.ValueGradientHessianKernel):
+        return ValueGradientHessianGramian(k, x, None if same else y)
     if isinstance(k, K.SeparableKernel):
         return SeparableGramian(k, x, None if same else y)
 

@@ -528,6 +528,14 @@ class HessianKernel(MultiKernel):
         self.input_trait = input_trait(k) if it is None else it
 
 
+class ValueGradientHessianKernel(MultiKernel):
+    """src/hessian.jl:279-299: the (1+d+d²)×(1+d+d²) block kernel of [f, ∂f, vec ∂²f]; carries input_trait(k) (src/hessian.jl:283)."""
+
+    def __init__(self, k, it: Optional[InputTrait] = None):
+        self.k = k
+        self.input_trait = input_trait(k) if it is None else it
+
+
 # ----------------------------------------------------------------------------------------------
 # input_trait (src/properties.jl:39-45, gradient.jl:16) — user-extensible like the reference
 # ----------------------------------------------------------------------------------------------
@@ -545,7 +553,7 @@ def input_trait(k) -> InputTrait:
     for t, tr in _USER_TRAITS.items():
         if isinstance(t, type) and isinstance(k, t):
             return tr
-    if isinstance(k, (Product, Sum, Power, GradientKernel, ValueGradientKernel, HessianKernel)):
+    if isinstance(k, (Product, Sum, Power, GradientKernel, ValueGradientKernel, HessianKernel, ValueGradientHessianKernel)):
         return k.input_trait
     if isinstance(k, (Dot, ExponentialDot, AsinDot)):
         return DotProductInput()
@@ -752,4 +760,23 @@ def require_hessian_spec(k, d: Optional[int] = None):
         raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"HessianKernel({name}): Power wrappers (exponent {spec.power}) have no Hessian device path")
     if d is not None and d > HESSIAN_MAX_D:
         raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"HessianKernel({name}): d = {d} exceeds the compiled maximum {HESSIAN_MAX_D}")
+    return spec
+
+
+def require_vgh_spec(k, d: Optional[int] = None):
+    """The covgram_kernel that covgram_valgradhess_mvm runs for ValueGradientHessianKernel(k), checked on the host before any device
+    call: the kernels and the bound on d of require_hessian_spec.  Everything else raises UnsupportedKernel naming the kernel."""
+    name = type(k).__name__
+    spec = device_spec(k)
+    if spec is None or not isinstance(spec, _ffi.covgram_kernel):
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"ValueGradientHessianKernel({name}): only single profiles have a device path, "
+                                                        "not composites or GenericInput kernels")
+    if spec.family not in _HESSIAN_FAMILIES:
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"ValueGradientHessianKernel({name}): no closed-form fourth derivative is compiled for this "
+                                                        "profile (supported: EQ, RQ, Cauchy, InverseMultiQuadratic, ExponentialDot, Dot)")
+    if spec.power != 1:
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"ValueGradientHessianKernel({name}): Power wrappers (exponent {spec.power}) have no "
+                                                        "device path")
+    if d is not None and d > HESSIAN_MAX_D:
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"ValueGradientHessianKernel({name}): d = {d} exceeds the compiled maximum {HESSIAN_MAX_D}")
     return spec

@@ -15,6 +15,7 @@
 #include "grad_bcast.hpp"
 #include "grad_wide.hpp"
 #include "hess_mvm.hpp"
+#include "vgh_mvm.hpp"
 
 namespace covgram {
 
@@ -73,6 +74,24 @@ hess_launch_fn hess_launcher(int family) {
         case COVGRAM_IMQ: return launch_hess_family_5;
         case COVGRAM_DOT: return launch_hess_family_7;
         case COVGRAM_EXPDOT: return launch_hess_family_8;
+        default: return nullptr;
+    }
+}
+// value-gradient-Hessian-kernel MVM (vgh_fam.hip: the same families)
+int launch_vgh_family_0(const VghArgs&, int dtype);
+int launch_vgh_family_2(const VghArgs&, int dtype);
+int launch_vgh_family_4(const VghArgs&, int dtype);
+int launch_vgh_family_5(const VghArgs&, int dtype);
+int launch_vgh_family_7(const VghArgs&, int dtype);
+int launch_vgh_family_8(const VghArgs&, int dtype);
+vgh_launch_fn vgh_launcher(int family) {
+    switch (family) {
+        case COVGRAM_EQ: return launch_vgh_family_0;
+        case COVGRAM_RQ: return launch_vgh_family_2;
+        case COVGRAM_CAUCHY: return launch_vgh_family_4;
+        case COVGRAM_IMQ: return launch_vgh_family_5;
+        case COVGRAM_DOT: return launch_vgh_family_7;
+        case COVGRAM_EXPDOT: return launch_vgh_family_8;
         default: return nullptr;
     }
 }
@@ -637,6 +656,7 @@ int covgram_ctx_get_info(covgram_ctx* ctx, const char* key, int64_t* value) {
     else if (!strcmp(key, "last_grad_path")) *value = ctx->last_grad_path;
     else if (!strcmp(key, "last_grad_jsplit")) *value = ctx->last_grad_jsplit;
     else if (!strcmp(key, "last_hess_path")) *value = ctx->last_hess_path;
+    else if (!strcmp(key, "last_vgh_path")) *value = ctx->last_vgh_path;
     else if (!strcmp(key, "last_sum_fused")) *value = ctx->last_sum_fused;
     else if (!strcmp(key, "last_mfma_instance")) *value = ctx->last_mfma_instance;
     else if (!strcmp(key, "last_mfma_sym_rt")) *value = ctx->last_mfma_sym_rt;
@@ -1693,6 +1713,110 @@ int covgram_hess_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram_po
             rc = launch(ha, dtype); if (rc) return rc;
             if (tm) (void)hipEventRecord(tm->second, ctx->stream);
             ctx->last_hess_path = 1;
+        }
+        if (jsplit != 1) {   // several column chunks: fixed-order sum of their slabs; no columns: y <- beta y
+            const dim3 rg((unsigned)((total + 255) / 256));
+            if (dtype == COVGRAM_F32)
+                hipLaunchKernelGGL(hess_reduce_kernel<float>, rg, dim3(256), 0, ctx->stream, (const float*)slab, jsplit, total, (float*)y_dev, (float)alpha_eff, (float)beta);
+            else
+                hipLaunchKernelGGL(hess_reduce_kernel<double>, rg, dim3(256), 0, ctx->stream, (const double*)slab, jsplit, total, (double*)y_dev, alpha_eff, beta);
+        }
+    }
+    CG_CHECK_HIP(hipGetLastError());
+    if (loc == COVGRAM_HOST) {
+        CG_CHECK_HIP(hipMemcpy2DAsync(y, (size_t)ldy * ts, y_all, (size_t)n * bd * ts, (size_t)n * bd * ts, nrhs, hipMemcpyDeviceToHost, ctx->stream));
+        CG_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return COVGRAM_OK;
+}
+
+// Value-gradient-Hessian-kernel Gramian (n (1 + d + d^2) x m (1 + d + d^2)): vgh_mvm.hpp.  The kernels, the argument checks, the column
+// split and the slab reduce of covgram_hess_mvm; the powers of gamma are applied per part of the block by the pack launch and the
+// kernel's epilogue, so only the constant factor goes into alpha.
+int covgram_valgradhess_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, const void* a, int64_t lda,
+                            void* y, int64_t ldy, int32_t nrhs, double alpha, double beta, int32_t loc) {
+    int rc = check_pair(ctx, X, Y);
+    if (rc) return rc;
+    CG_REQUIRE(k != nullptr, COVGRAM_EINVAL, "kernel is NULL");
+    static const char* const names[COVGRAM_NFAMILY] = {"ExponentiatedQuadratic", "Exponential", "RationalQuadratic", "GammaExponential", "Cauchy",
+                                                       "InverseMultiQuadratic", "MaternP", "Dot", "ExponentialDot", "Matern", "AsinDot"};
+    CG_REQUIRE(k->family != COVGRAM_COMPOSITE, COVGRAM_EUNSUPPORTED,
+               "ValueGradientHessianKernel of a composite kernel (Sum / Product / Power) has no device path");
+    CG_REQUIRE(k->family >= 0 && k->family < COVGRAM_NFAMILY, COVGRAM_EUNSUPPORTED, "unknown kernel family %d", k->family);
+    CG_REQUIRE(hess_family_ok(k->family), COVGRAM_EUNSUPPORTED,
+               "ValueGradientHessianKernel(%s) has no device path (no closed-form fourth derivative compiled)", names[k->family]);
+    CG_REQUIRE(k->power == 1, COVGRAM_EUNSUPPORTED, "ValueGradientHessianKernel(%s^%d): Power wrappers have no device path", names[k->family], k->power);
+    const int d = X->d;
+    CG_REQUIRE(d <= HESS_MAX_D, COVGRAM_EUNSUPPORTED, "ValueGradientHessianKernel(%s): d = %d exceeds the compiled maximum %d", names[k->family], d,
+               HESS_MAX_D);
+    CG_REQUIRE(nrhs >= 1, COVGRAM_EINVAL, "nrhs must be >= 1");
+    const int64_t n = X->n, m = Y->n, bd = 1 + (int64_t)d + (int64_t)d * d;
+    CG_REQUIRE(lda >= m * bd && ldy >= n * bd, COVGRAM_EINVAL, "lda / ldy smaller than the block vectors (%lld, %lld)", (long long)(m * bd), (long long)(n * bd));
+    CG_REQUIRE((a != nullptr || m == 0) && (y != nullptr || n == 0), COVGRAM_EINVAL, "a or y is NULL");
+    const int dtype = X->dtype;
+    const size_t ts = dtype_size(dtype);
+    HostKernel hk;
+    rc = make_host_kernel(k, dtype, true, &hk);
+    if (rc) return rc;
+    vgh_launch_fn launch = vgh_launcher(hk.tu_family);
+    CG_REQUIRE(launch != nullptr, COVGRAM_EUNSUPPORTED, "ValueGradientHessianKernel(%s) has no device path", names[k->family]);
+    if (loc == COVGRAM_DEVICE) {   // a and y may overlap (include/covgram.h): everything below reads a private copy of a
+        rc = unalias_input(ctx, &a, &lda, m * bd, nrhs, y, ldy, n * bd, ts);
+        if (rc) return rc;
+    }
+    CG_DEVICE(ctx);
+    ctx->last_vgh_path = 0;
+    if (n == 0) return COVGRAM_OK;
+
+    const void* a_all = a;
+    void* y_all = y;
+    int64_t lda_d = lda, ldy_d = ldy;
+    if (loc == COVGRAM_HOST) {
+        void *sa, *sy;
+        rc = ws_reserve(ctx, 2, (size_t)std::max<int64_t>(m, 1) * bd * nrhs * ts, &sa); if (rc) return rc;
+        rc = ws_reserve(ctx, 3, (size_t)n * bd * nrhs * ts, &sy); if (rc) return rc;
+        if (m > 0) CG_CHECK_HIP(hipMemcpy2DAsync(sa, (size_t)m * bd * ts, a, (size_t)lda * ts, (size_t)m * bd * ts, nrhs, hipMemcpyHostToDevice, ctx->stream));
+        if (beta != 0.0) CG_CHECK_HIP(hipMemcpy2DAsync(sy, (size_t)n * bd * ts, y, (size_t)ldy * ts, (size_t)n * bd * ts, nrhs, hipMemcpyHostToDevice, ctx->stream));
+        a_all = sa; y_all = sy; lda_d = m * bd; ldy_d = n * bd;
+    }
+    const bool iso = (k->trait == COVGRAM_ISOTROPIC);
+    const int D = hess_pad_dim(d);
+    const int rec = vgh_rec(D);
+    const double alpha_eff = alpha * hk.kp.scale;
+    const int64_t total = n * bd;
+    // the column split of covgram_hess_mvm: up to ~8 workgroups per CU, at least 4 staged chunks each, partial slabs within 256 MB
+    const int ppw = HESS_THREADS / D;
+    const int64_t rowwgs = (n + ppw - 1) / ppw;
+    const int64_t minchunk = 4 * (int64_t)vgh_jc(D, (int)ts);
+    int64_t split = std::max<int64_t>(1, ((int64_t)ctx->num_cus * 8 + rowwgs - 1) / rowwgs);
+    split = std::min(split, std::max<int64_t>(1, m / minchunk));
+    split = std::min(split, std::max<int64_t>(1, (int64_t)(256.0e6 / ((double)total * ts))));
+    if (ctx->jsplit > 0) split = std::min<int64_t>(ctx->jsplit, std::max<int64_t>(1, m));
+    int64_t jchunk = std::max<int64_t>(1, (m + split - 1) / split);
+    const int jsplit = m > 0 ? (int)((m + jchunk - 1) / jchunk) : 0;
+    void *P = nullptr, *slab = nullptr;
+    if (m > 0) { rc = ws_reserve(ctx, 0, (size_t)m * rec * ts, &P); if (rc) return rc; }
+    if (jsplit > 1) { rc = ws_reserve(ctx, 1, (size_t)jsplit * total * ts, &slab); if (rc) return rc; }
+    const void* Cn = iso ? Y->center : nullptr;
+    for (int c0 = 0; c0 < nrhs; ++c0) {
+        const void* a_dev = (const char*)a_all + (size_t)c0 * lda_d * ts;
+        void* y_dev = (char*)y_all + (size_t)c0 * ldy_d * ts;
+        if (m > 0) {
+            const int64_t pe = m * (int64_t)rec;
+            if (dtype == COVGRAM_F32)
+                hipLaunchKernelGGL(vgh_pack_kernel<float>, dim3((unsigned)((pe + 255) / 256)), dim3(256), 0, ctx->stream, (const float*)Y->dptr, m, d,
+                                   (const float*)a_dev, (float*)P, D, (float)hk.kp.gamma, (const float*)Cn);
+            else
+                hipLaunchKernelGGL(vgh_pack_kernel<double>, dim3((unsigned)((pe + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)Y->dptr, m, d,
+                                   (const double*)a_dev, (double*)P, D, hk.kp.gamma, (const double*)Cn);
+            VghArgs va;
+            va.X = X->dptr; va.n = n; va.d = d; va.P = P; va.m = m; va.out = jsplit > 1 ? slab : y_dev; va.Dpad = D; va.jchunk = jchunk; va.jsplit = jsplit;
+            va.C = Cn; va.alpha = alpha_eff; va.beta = beta; va.hk = &hk; va.stream = ctx->stream;
+            auto* tm = timer_next(ctx);
+            if (tm) (void)hipEventRecord(tm->first, ctx->stream);
+            rc = launch(va, dtype); if (rc) return rc;
+            if (tm) (void)hipEventRecord(tm->second, ctx->stream);
+            ctx->last_vgh_path = 1;
         }
         if (jsplit != 1) {   // several column chunks: fixed-order sum of their slabs; no columns: y <- beta y
             const dim3 rg((unsigned)((total + 255) / 256));

@@ -799,6 +799,60 @@ struct DPhi4<COVGRAM_EXPDOT, T> {
     static __device__ __forceinline__ void eval(T s, const KParams<T>&, T& f2, T& f3, T& f4) { f2 = cg_exp(s); f3 = f2; f4 = f2; }
 };
 
+// ---- (phi, phi', ..., phi'''') w.r.t. the pre-scaled argument: the full jet of the value-gradient-Hessian blocks (vgh_mvm.hpp), the
+// profile's transcendentals evaluated once.  The families of DPhi4.
+template <int FAM, typename T>
+struct DPhi5;
+
+template <typename T>
+struct DPhi5<COVGRAM_EQ, T> {
+    static __device__ __forceinline__ void eval(T s, const KParams<T>&, T& f0, T& f1, T& f2, T& f3, T& f4) {
+        if constexpr (sizeof(T) == 8) f0 = eq_exp_neg_half(s);
+        else f0 = cg_exp2(s * (T)-0.72134752044448170368);
+        f1 = (T)-0.5 * f0; f2 = (T)0.25 * f0; f3 = (T)-0.125 * f0; f4 = (T)0.0625 * f0;
+    }
+};
+template <typename T>
+struct DPhi5<COVGRAM_RQ, T> {
+    static __device__ __forceinline__ void eval(T s, const KParams<T>& kp, T& f0, T& f1, T& f2, T& f3, T& f4) {
+        const T a = kp.param, h = (T)0.5 * kp.c0;            // c0 = 1 / (2 alpha)
+        const T u = cg_fma(s, kp.c0, (T)1);
+        const T iu = cg_rcp(u);
+        f0 = rq_pow(u, a);
+        f1 = (T)-0.5 * f0 * iu;                               // -1/2 u^(-a-1)
+        f2 = (a + (T)1) * h * f0 * iu * iu;                   // (a+1)/(4a) u^(-a-2)
+        f3 = -(a + (T)2) * kp.c0 * f2 * iu;                   // -(a+1)(a+2)/(8a^2) u^(-a-3)
+        f4 = -(a + (T)3) * kp.c0 * f3 * iu;                   // (a+1)(a+2)(a+3)/(16a^3) u^(-a-4)
+    }
+};
+template <typename T>
+struct DPhi5<COVGRAM_CAUCHY, T> {
+    static __device__ __forceinline__ void eval(T s, const KParams<T>&, T& f0, T& f1, T& f2, T& f3, T& f4) {
+        f0 = cg_rcp((T)1 + s);
+        f1 = -f0 * f0; f2 = (T)-2 * f1 * f0; f3 = (T)-3 * f2 * f0; f4 = (T)-4 * f3 * f0;
+    }
+};
+template <typename T>
+struct DPhi5<COVGRAM_IMQ, T> {
+    static __device__ __forceinline__ void eval(T s, const KParams<T>& kp, T& f0, T& f1, T& f2, T& f3, T& f4) {
+        const T iu = cg_rcp(s + kp.param);
+        f0 = cg_rsqrt(s + kp.param);
+        f1 = (T)-0.5 * f0 * iu; f2 = (T)0.75 * f0 * iu * iu; f3 = (T)-2.5 * f2 * iu; f4 = (T)-3.5 * f3 * iu;   // -1/2, 3/4, -15/8, 105/16
+    }
+};
+template <typename T>
+struct DPhi5<COVGRAM_DOT, T> {
+    static __device__ __forceinline__ void eval(T s, const KParams<T>&, T& f0, T& f1, T& f2, T& f3, T& f4) {
+        f0 = s; f1 = (T)1; f2 = (T)0; f3 = (T)0; f4 = (T)0;
+    }
+};
+template <typename T>
+struct DPhi5<COVGRAM_EXPDOT, T> {
+    static __device__ __forceinline__ void eval(T s, const KParams<T>&, T& f0, T& f1, T& f2, T& f3, T& f4) {
+        f0 = cg_exp(s); f1 = f0; f2 = f0; f3 = f0; f4 = f0;
+    }
+};
+
 // (phi^q, (phi^q)', (phi^q)'') from (phi, phi', phi'')
 template <typename T>
 __device__ __forceinline__ void power_jet(int q, T& v, T& d1, T& d2) {

@@ -21,7 +21,7 @@ module CovGram
 
 using LinearAlgebra
 using CovarianceFunctions
-using CovarianceFunctions: Gramian, GradientKernel, ValueGradientKernel, HessianKernel, IsotropicInput, DotProductInput, StationaryInput,
+using CovarianceFunctions: Gramian, GradientKernel, ValueGradientKernel, HessianKernel, ValueGradientHessianKernel, IsotropicInput, DotProductInput, StationaryInput,
                            GenericInput, input_trait, EQ, RQ, Exp, γExp, Cauchy, InverseMultiQuadratic, MaternP, Dot,
                            ExponentialDot, Lengthscale, Power, Product, Sum, Constant, SeparableProduct, SeparableKernel, LazyGrid, FiniteBasis
 import CovarianceFunctions: gramian
@@ -233,6 +233,10 @@ function device_blockmul!(sym::Symbol, y::StridedVecOrMat{T}, G::Gramian, a::Str
         check(ccall((:covgram_hess_mvm, libcovgram), Cint,
                     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int32, Float64, Float64, Int32),
                     ctx(), kref(spec), X.handle, Y.handle, a, lda, y, ldy, nrhs, Float64(α), Float64(β), HOST))
+    elseif sym === :valgradhess   # src/hessian.jl:301-325: blocks of 1 + d + d^2: value, gradient, then entry a + b d of the Hessian
+        check(ccall((:covgram_valgradhess_mvm, libcovgram), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int32, Float64, Float64, Int32),
+                    ctx(), kref(spec), X.handle, Y.handle, a, lda, y, ldy, nrhs, Float64(α), Float64(β), HOST))
     else   # src/gradient.jl:400-474 (ValueGradientKernel), block mul! :319-351: blocks of d+1, value component first
         check(ccall((:covgram_valgrad_mvm, libcovgram), Cint,
                     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int32, Float64, Float64, Int32),
@@ -289,6 +293,22 @@ function LinearAlgebra.mul!(Y::StridedMatrix{T}, B::BlockFactorizations.BlockFac
     spec = hessian_spec(G.k.k, length(first(G.x)))
     spec === nothing ? invoke(mul!, Tuple{AbstractMatrix, BlockFactorizations.BlockFactorization, AbstractMatrix, Real, Real}, Y, B, A, α, β) :
                        device_blockmul!(:hess, Y, G, A, α, β, spec)
+end
+
+# --- src/hessian.jl:279-479: ValueGradientHessianKernel Gramians -> covgram_valgradhess_mvm; the kernels and the bound on d of hessian_spec
+function LinearAlgebra.mul!(y::StridedVector{T}, B::BlockFactorizations.BlockFactorization{T, <:Gramian{<:Any, <:ValueGradientHessianKernel}},
+                            a::StridedVector{T}, α::Real = 1, β::Real = 0) where {T <: DevFloat}
+    G = B.A
+    spec = hessian_spec(G.k.k, length(first(G.x)))
+    spec === nothing ? invoke(mul!, Tuple{AbstractVector, BlockFactorizations.BlockFactorization, AbstractVector, Real, Real}, y, B, a, α, β) :
+                       device_blockmul!(:valgradhess, y, G, a, α, β, spec)
+end
+function LinearAlgebra.mul!(Y::StridedMatrix{T}, B::BlockFactorizations.BlockFactorization{T, <:Gramian{<:Any, <:ValueGradientHessianKernel}},
+                            A::StridedMatrix{T}, α::Real = 1, β::Real = 0) where {T <: DevFloat}
+    G = B.A
+    spec = hessian_spec(G.k.k, length(first(G.x)))
+    spec === nothing ? invoke(mul!, Tuple{AbstractMatrix, BlockFactorizations.BlockFactorization, AbstractMatrix, Real, Real}, Y, B, A, α, β) :
+                       device_blockmul!(:valgradhess, Y, G, A, α, β, spec)
 end
 
 # --- src/separable.jl:38-42: mul!(y, G::Gramian{<:AbstractMatrix, <:SeparableKernel}, x) on vectors of vectors -----------------

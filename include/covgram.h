@@ -15,6 +15,7 @@
  *                          with the  GradientKernelElement mul! (isotropic / dot-product)         src/gradient.jl:86-92, 109-115
  *   covgram_valgrad_mvm    the same  blockmul! with the ValueGradientKernel element                       src/gradient.jl:319-351, 400-474
  *   covgram_hess_mvm       the same  blockmul! with the HessianKernel elements' O(d^2) mul!             src/hessian.jl:125-190, 227-275
+ *   covgram_valgradhess_mvm the same blockmul! with the ValueGradientHessianKernel elements, in O(d^2)           src/hessian.jl:279-325, 392-479
  *   covgram_toeplitz_*     replaces  mul!(y, ::SymmetricToeplitz/Toeplitz/Circulant, a, α, β) of ToeplitzMatrices 0.7.1 as
  *                          constructed by gramian(k, x::StepRangeLen, y::StepRangeLen)            src/gramian.jl:167-189
  *   covgram_toeplitz_durbin / _levinson / _trench  replace durbin! / levinson! / trench!             src/toeplitz.jl:12-111
@@ -50,7 +51,8 @@ extern "C" {
                                covgram_cg_step_shifted; 112: covgram_mvm_sym_supported takes `world` (the symmetric partial form's
                                column-sum slab depends on it), fp32 direct-difference symmetric partials; 113: the communicator
                                (covgram_comm_*), covgram_mvm_sharded, covgram_mvm_sym_allreduce.  Added since, backward
-                               compatibly (no version step): covgram_hess_mvm and the info key "last_hess_path".
+                               compatibly (no version step): covgram_hess_mvm and the info key "last_hess_path";
+                               covgram_valgradhess_mvm and the info key "last_vgh_path".
                                A binding checks covgram_version() against the header it mirrors at load time */
 
 typedef enum covgram_status {
@@ -295,6 +297,19 @@ int covgram_valgrad_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram
  * Aliasing: a and y may overlap in any way; a is then read from a private copy. */
 int covgram_hess_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, const void* a,
                      int64_t lda, void* y, int64_t ldy, int32_t nrhs, double alpha, double beta, int32_t loc);
+
+/* Value-gradient-Hessian-kernel Gramian (n(1+d+d^2) × m(1+d+d^2)), src/hessian.jl:279-325: block (i,j) is the joint covariance of
+ * [f, grad f, vec hess f], entry (row functional on x_i, column functional on y_j) of k(x_i, y_j) with the functionals id, d/d._a,
+ * d^2/d._a d._b; applied in O(d^2) per pair for isotropic AND dot-product kernels (the reference: :392-479, isotropic only), never
+ * formed.  Flat point-major block vectors, block of point i at offset i*(1+d+d^2): entry 0 the value, entries 1..d the gradient, entry
+ * 1 + d + a + b*d the Hessian component (a, b) (the order of covgram_hess_mvm); right-hand sides as for covgram_grad_mvm
+ * (lda >= m*(1+d+d^2), ldy >= n*(1+d+d^2), nrhs columns).  Device path: the kernels of covgram_hess_mvm — EQ, RQ, Cauchy, IMQ with
+ * lengthscale and scale; ExponentialDot and Dot (NOT a zero matrix here: its value and gradient rows and columns are non-zero) — and
+ * d <= 32; a Power wrapper, composites and every other family return COVGRAM_EUNSUPPORTED with a message that names the kernel.
+ * Option "time_kernels" brackets the block kernel; info key "last_vgh_path" reports it ("last_hess_path" is left alone).
+ * Aliasing: a and y may overlap in any way; a is then read from a private copy. */
+int covgram_valgradhess_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, const void* a,
+                            int64_t lda, void* y, int64_t ldy, int32_t nrhs, double alpha, double beta, int32_t loc);
 
 /* Toeplitz T[i,j] = vc[i-j] (i >= j), vr[j-i] (i < j); vr == NULL: symmetric (vr = vc, m = n).
  * circulant != 0: T[i,j] = vc[(i-j) mod n] (vr must be NULL).  The spectrum of the circulant embedding
