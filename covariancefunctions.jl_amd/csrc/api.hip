@@ -394,11 +394,12 @@ __global__ __launch_bounds__(256) void matrix_kernel(const T* __restrict__ X, in
                                                      int32_t d, T* __restrict__ out, int64_t ldo, int family, T scale,
                                                      const KParams<T> kp) {
     // block = 256 rows × 1 column strip of 16 columns; lanes along rows -> coalesced column-major stores
+    // (the grid's y extent is capped at MATRIX_MAX_GRID_Y: with more strips than that a block walks several)
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t jb = (int64_t)blockIdx.y * 16;
     if (i >= n) return;
     const bool iso = (family != COVGRAM_DOT && family != COVGRAM_EXPDOT && family != COVGRAM_ASINDOT);
     const T* xi = X + i * (int64_t)d;
+    for (int64_t jb = (int64_t)blockIdx.y * 16; jb < m; jb += (int64_t)gridDim.y * 16)
     for (int64_t j = jb; j < jb + 16 && j < m; ++j) {
         const T* yj = Y + j * (int64_t)d;
         T s = (T)0;
@@ -420,7 +421,6 @@ __global__ __launch_bounds__(256) void matrix_reg_kernel(const T* __restrict__ X
     // VR consecutive rows per thread (round 5): one 16-byte streaming store per column instead of VR narrow ones — Matrix(G) is a gigabyte written once
     // (fp32, n = 16384: 3.7 -> TB/s figures in profiles/r05_matrix_bench.txt); VR > 1 needs n, ldo multiples of VR and a 16-byte aligned out
     const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * VR;
-    const int64_t jb = (int64_t)blockIdx.y * 64;
     if (i >= n) return;
     const bool iso = EXPR ? (family_or_iso != 0)
                           : (family_or_iso != COVGRAM_DOT && family_or_iso != COVGRAM_EXPDOT && family_or_iso != COVGRAM_ASINDOT);
@@ -429,7 +429,7 @@ __global__ __launch_bounds__(256) void matrix_reg_kernel(const T* __restrict__ X
     for (int r = 0; r < VR; ++r)
 #pragma unroll
         for (int l = 0; l < DM; ++l) x[r][l] = (l < d) ? X[(i + r) * (int64_t)d + l] : (T)0;
-    const int64_t jend = (jb + 64 < m) ? jb + 64 : m;
+    int64_t jb = (int64_t)blockIdx.y * 64, jend = 0;          // the strip at hand (set per strip below)
     T gam = (T)1;
     if constexpr (!EXPR) gam = kp.gamma;
     // the padded dimensions l >= d contribute exact zeros (x = y = 0: r = 0, fma(0, 0, s) = s): no branch inside the entry loop;
@@ -479,13 +479,17 @@ __global__ __launch_bounds__(256) void matrix_reg_kernel(const T* __restrict__ X
         }
     };
     auto run = [&](auto famc) { if (d == DM) strip(famc, std::true_type()); else strip(famc, std::false_type()); };
-    if constexpr (EXPR) run(std::integral_constant<int, 0>());
-    else switch (family_or_iso) {
+    // one strip per block, unless there are more strips than the grid's y extent may hold (MATRIX_MAX_GRID_Y): then a block walks several
+    for (; jb < m; jb += (int64_t)gridDim.y * 64) {
+        jend = (jb + 64 < m) ? jb + 64 : m;
+        if constexpr (EXPR) run(std::integral_constant<int, 0>());
+        else switch (family_or_iso) {
 #define CG_FAMCASE(F) case F: run(std::integral_constant<int, F>()); break;
-        CG_FAMCASE(COVGRAM_EQ) CG_FAMCASE(COVGRAM_EXP) CG_FAMCASE(COVGRAM_RQ) CG_FAMCASE(COVGRAM_GAMMAEXP) CG_FAMCASE(COVGRAM_CAUCHY)
-        CG_FAMCASE(COVGRAM_IMQ) CG_FAMCASE(COVGRAM_MATERNP) CG_FAMCASE(COVGRAM_DOT) CG_FAMCASE(COVGRAM_EXPDOT) CG_FAMCASE(COVGRAM_MATERN)
-        CG_FAMCASE(COVGRAM_ASINDOT)
+            CG_FAMCASE(COVGRAM_EQ) CG_FAMCASE(COVGRAM_EXP) CG_FAMCASE(COVGRAM_RQ) CG_FAMCASE(COVGRAM_GAMMAEXP) CG_FAMCASE(COVGRAM_CAUCHY)
+            CG_FAMCASE(COVGRAM_IMQ) CG_FAMCASE(COVGRAM_MATERNP) CG_FAMCASE(COVGRAM_DOT) CG_FAMCASE(COVGRAM_EXPDOT) CG_FAMCASE(COVGRAM_MATERN)
+            CG_FAMCASE(COVGRAM_ASINDOT)
 #undef CG_FAMCASE
+        }
     }
 }
 
@@ -494,9 +498,9 @@ __global__ __launch_bounds__(256) void matrix_expr_kernel(const T* __restrict__ 
                                                           int32_t d, T* __restrict__ out, int64_t ldo, int iso, T scale,
                                                           const ExprParams<T> ep) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t jb = (int64_t)blockIdx.y * 16;
     if (i >= n) return;
     const T* xi = X + i * (int64_t)d;
+    for (int64_t jb = (int64_t)blockIdx.y * 16; jb < m; jb += (int64_t)gridDim.y * 16)
     for (int64_t j = jb; j < jb + 16 && j < m; ++j) {
         const T* yj = Y + j * (int64_t)d;
         T s = (T)0;
@@ -657,6 +661,7 @@ int covgram_ctx_get_info(covgram_ctx* ctx, const char* key, int64_t* value) {
     else if (!strcmp(key, "last_grad_jsplit")) *value = ctx->last_grad_jsplit;
     else if (!strcmp(key, "last_hess_path")) *value = ctx->last_hess_path;
     else if (!strcmp(key, "last_vgh_path")) *value = ctx->last_vgh_path;
+    else if (!strcmp(key, "last_matrix_path")) *value = ctx->last_matrix_path;
     else if (!strcmp(key, "last_sum_fused")) *value = ctx->last_sum_fused;
     else if (!strcmp(key, "last_mfma_instance")) *value = ctx->last_mfma_instance;
     else if (!strcmp(key, "last_mfma_sym_rt")) *value = ctx->last_mfma_sym_rt;
@@ -1249,13 +1254,19 @@ int covgram_matrix(covgram_ctx* ctx, const covgram_kernel* k, const covgram_poin
     rc = make_host_kernel(k, dtype, true, &hk);   // gamma = 1/l, unfolded EQ
     if (rc) return rc;
     CG_DEVICE(ctx);
+    ctx->last_matrix_path = 0;
     if (n == 0 || m == 0) return COVGRAM_OK;
     void* o = out;
     int64_t ld = ldo;
     if (loc == COVGRAM_HOST) { rc = ws_reserve(ctx, 3, (size_t)n * m * ts, &o); if (rc) return rc; ld = n; }
-    dim3 grid((unsigned)((n + 255) / 256), (unsigned)((m + 15) / 16));
+    // a grid's y extent is limited (65535 is what every HIP device accepts): beyond it the kernels walk several strips per block
+    constexpr int64_t MATRIX_MAX_GRID_Y = 65535;
+    auto strips = [](int64_t mm, int64_t w) { const int64_t c = (mm + w - 1) / w; return (unsigned)(c < MATRIX_MAX_GRID_Y ? c : MATRIX_MAX_GRID_Y); };
+    dim3 grid((unsigned)((n + 255) / 256), strips(m, 16));
+    const bool composite = hk.tu_family >= COVGRAM_NFAMILY;
+    ctx->last_matrix_path = composite ? 1002 : 1001;                // route + 10 DM + 1000 VR (include/covgram.h); the register routes set theirs below
     if (X->d <= 64 && ctx->matrix_variant != 1) {                  // x_i in registers, 64-column strips (option matrix_variant = 1: the generic kernel)
-        const dim3 g2((unsigned)((n + 255) / 256), (unsigned)((m + 63) / 64));
+        const dim3 g2((unsigned)((n + 255) / 256), strips(m, 64));
         const int dd = X->d;
         const bool expr = hk.tu_family >= COVGRAM_NFAMILY;
         const int fam_or_iso = expr ? (hk.tu_family == FAM_EXPR_ISO ? 1 : 0) : k->family;
@@ -1265,7 +1276,8 @@ int covgram_matrix(covgram_ctx* ctx, const covgram_kernel* k, const covgram_poin
         do {                                                                                                                              \
             constexpr int VRV = 16 / (int)sizeof(TT);                                                                                     \
             const bool vr = !expr && DMV <= 16 && n % VRV == 0 && ld % VRV == 0 && ((uintptr_t)o % 16) == 0;                                \
-            const dim3 g3((unsigned)((n / VRV + 255) / 256), (unsigned)((m + 63) / 64));                                                  \
+            const dim3 g3((unsigned)((n / VRV + 255) / 256), strips(m, 64));                                                              \
+            ctx->last_matrix_path = (expr ? 4 : 3) + 10 * DMV + 1000 * (vr ? VRV : 1);                                                    \
             if (expr) hipLaunchKernelGGL((matrix_reg_kernel<TT, DMV, true, ExprParams<TT>>), g2, dim3(256), 0, ctx->stream, (const TT*)X->dptr, n, \
                                          (const TT*)Y->dptr, m, dd, (TT*)o, ld, fam_or_iso, (TT)hk.kp.scale, make_params<FAM_EXPR_ISO, TT>(hk)); \
             else if (vr) hipLaunchKernelGGL((matrix_reg_kernel<TT, (DMV <= 16 ? DMV : 16), false, KParams<TT>, VRV>), g3, dim3(256), 0, ctx->stream, (const TT*)X->dptr, n,  \

@@ -52,7 +52,8 @@ extern "C" {
                                column-sum slab depends on it), fp32 direct-difference symmetric partials; 113: the communicator
                                (covgram_comm_*), covgram_mvm_sharded, covgram_mvm_sym_allreduce.  Added since, backward
                                compatibly (no version step): covgram_hess_mvm and the info key "last_hess_path";
-                               covgram_valgradhess_mvm and the info key "last_vgh_path".
+                               covgram_valgradhess_mvm and the info key "last_vgh_path";
+                               the info key "last_matrix_path".
                                A binding checks covgram_version() against the header it mirrors at load time */
 
 typedef enum covgram_status {
@@ -188,7 +189,10 @@ int covgram_ctx_get_stream(covgram_ctx* ctx, void** hip_stream);
  * around every workgroup's column loop, for bench.py's sustained-clock figure; never set in production). */
 int covgram_ctx_set_option(covgram_ctx* ctx, const char* key, int64_t value);
 /* read-only facts: "last_dense_path" (which kernel the last covgram_mvm ran: 0 none yet, 1 lane-per-row direct differences,
- * 2 matrix cores, 3 wide rows, 4 Gramian(Dot(), x, y) factored as X (Y' a)), "last_mfma_lds" (1: that matrix-core MVM shared its column tiles through LDS), "last_mfma_sym" (1: the last dense
+ * 2 matrix cores, 3 wide rows, 4 Gramian(Dot(), x, y) factored as X (Y' a)), "last_matrix_path" (which kernel the last covgram_matrix
+ * ran: 0 none yet or n m == 0, otherwise route + 10 DM + 1000 VR with route 1 = generic single profile, 2 = generic composite,
+ * 3 = registers single profile, 4 = registers composite; DM the compiled dimension bucket, 0 for the generic kernels; VR rows per
+ * thread, 1 where not applicable), "last_mfma_lds" (1: that matrix-core MVM shared its column tiles through LDS), "last_mfma_sym" (1: the last dense
  * MVM ran the symmetric upper-triangle kernel), "last_dense_sym" (1: it ran a direct-difference symmetric kernel, fp64 or fp32), "last_inkernel_reduce" (1: the last dense kernel summed its own split-J slab), "last_grad_expand" (1: the last gradient MVM ran the expanded form), "last_grad_bcast" (waves per workgroup of the broadcast kernel if the last gradient MVM ran it, else 0), "last_grad_path" (which kernels the last gradient or value-gradient MVM ran, as bits: 1 = the lane-per-row kernel, 2 = its two-column pass, 4 = the panel path (grad_wide), 8 = more than one panel, 16 = the panel path split over z slices with the separate reduce, 32 = the lane-per-row kernel with a column split > 1 and the slab reduce; 0 = no block kernel (n = 0 or m = 0); a Sum split term by term reports its last term), "last_grad_jsplit" (the column split of the last gradient MVM's lane-per-row launch, 0 if it did not run one), "last_hess_path" (0 = no Hessian MVM yet or one without rows / columns, 1 = the last covgram_hess_mvm ran its block kernel, csrc/hess_mvm.hpp), "last_sum_fused" (1: the last covgram_mvm ran a Sum on the one-pass kernels), "last_mfma_instance" (which instance of the matrix-core EQ kernels the last launch was: the template arguments of dense_mfma_eq_kernel as K2 1e5 + RT 1e4 + WPB 1e3 + LDS 100 + STAMP 10 + FMT, -(K2 10 + FMT) for the symmetric kernel, 0 otherwise — bench.py checks its recorded PMC pass against it), "last_dense_bcast" (1: the last fp64 dense MVM ran a register-broadcast kernel), "last_mfma_f16" (1: the last general matrix-core EQ MVM ran the fp16 two-way split), "last_jsplit" (the column split of the last lane-per-row dense launch), "last_kron_path" (which kernels the last covgram_kron_mvm ran, as bits: 1 = the fused last-two-modes pass, 2 = the single-mode kernel, 4 = the last-mode kernel, 8 = a rocBLAS GEMM (a factor side >= 1024, >= 256 with >= 2 GFLOP, or a shape the kernels refuse), 16 = two small trailing factors multiplied out first), "num_cus", "last_clock_khz" (median shader clock over the workgroups of the last
  * launch made with "mfma_stamp" = 1; synchronises the stream; 0 = no stamped launch yet). */
 int covgram_ctx_get_info(covgram_ctx* ctx, const char* key, int64_t* value);
@@ -217,7 +221,14 @@ int covgram_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points*
                 const void* a, int64_t lda, void* y, int64_t ldy, int32_t nrhs, double alpha, double beta,
                 int32_t loc);
 
-/* out[i + j*ldo] = k(x_i, y_j): dense instantiation of the n×m Gramian (column-major). */
+/* out[i + j*ldo] = k(x_i, y_j): dense instantiation of the n×m Gramian (column-major), for any n and m (more column strips than a
+ * grid's y extent holds are walked inside the kernels).  Only the entries i < n of every column are written: rows n <= i < ldo of out
+ * are never touched, with loc == HOST (the staged tile is copied back column by column) as with loc == DEVICE.
+ * Routes (info key "last_matrix_path"): d <= 64 keeps x_i in registers (compiled buckets DM = 4, 8, 16, 32, 64; option
+ * "matrix_variant" = 1 or d > 64: the generic kernels).  A single profile with d <= 16 writes VR = 4 (fp32) / 2 (fp64) consecutive
+ * rows per thread with one 16-byte streaming store per column when n and the leading dimension are multiples of VR and out is
+ * 16-byte aligned (loc == HOST: the staged tile has leading dimension n, so only n counts); otherwise one row per thread (VR = 1)
+ * with the same arithmetic — the entries do not depend on ldo or on the alignment of out. */
 int covgram_matrix(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y,
                    void* out, int64_t ldo, int32_t loc);
 
