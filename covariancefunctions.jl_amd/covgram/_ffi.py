@@ -23,6 +23,7 @@ HOST, DEVICE = 0, 1
 OK, EINVAL, EUNSUPPORTED, EHIP, ENODEVICE, ENOMEM = 0, -1, -2, -3, -4, -5
 MATERNP_MAX_P = 8
 COMM_ID_BYTES = 128
+BLOCK_GRADIENT, BLOCK_VALUE_GRADIENT, BLOCK_HESSIAN, BLOCK_VALUE_GRADIENT_HESSIAN = range(4)   # kinds of covgram_block_matrix
 ABI_VERSION = 113   # COVGRAM_VERSION of the include/covgram.h these prototypes mirror
 
 
@@ -102,6 +103,7 @@ PROTOTYPES = {
     "covgram_valgrad_mvm": (C.c_int, [_P, _KP, _P, _P, _P, _I64, _P, _I64, _I32, _D, _D, _I32]),
     "covgram_hess_mvm": (C.c_int, [_P, _KP, _P, _P, _P, _I64, _P, _I64, _I32, _D, _D, _I32]),
     "covgram_valgradhess_mvm": (C.c_int, [_P, _KP, _P, _P, _P, _I64, _P, _I64, _I32, _D, _D, _I32]),
+    "covgram_block_matrix": (C.c_int, [_P, _I32, _KP, _P, _P, _P, _I64, _I32]),
     "covgram_mvm_sym_supported": (C.c_int, [_P, _KP, _P, _I32, C.POINTER(C.c_int32)]),
     "covgram_mvm_sym_partial": (C.c_int, [_P, _KP, _P, _P, _P, _I32, _I32]),
     "covgram_comm_unique_id": (C.c_int, [_P, _I64]),

@@ -388,6 +388,29 @@ class Gramian(LazyOperator):
         return sub
 
 
+BLOCK_MATRIX_MAX_D = 64     # covgram_block_matrix, gradient kinds: rows in registers (include/covgram.h)
+
+
+def flat_cover(I, size, B):
+    """A flat index (int or slice) into a point-major block vector of `size` = (points) B entries -> (p0, p1, rel): the points
+    [p0, p1) that cover it and the same index relative to entry p0 B (flat index I = point I // B, component I % B)."""
+    if isinstance(I, slice):
+        idx = range(*I.indices(size))
+        if len(idx) == 0:
+            return 0, 0, slice(0, 0)
+        lo, hi = min(idx[0], idx[-1]), max(idx[0], idx[-1])
+        p0, p1 = lo // B, hi // B + 1
+        if idx.step < 0:                                     # torch has no negative strides: an index list
+            return p0, p1, [v - p0 * B for v in idx]
+        return p0, p1, slice(idx[0] - p0 * B, idx[-1] + 1 - p0 * B, idx.step)
+    I = int(I)
+    if I < 0:
+        I += size
+    if not 0 <= I < size:
+        raise IndexError(f"index {I} out of range for {size} entries")
+    return I // B, I // B + 1, I % B
+
+
 class BlockGramian(LazyOperator):
     """Gramian of a GradientKernel: the lazy (n d)×(m d) BlockFactorization of src/gramian.jl:120-123 whose
     `mul!` is blockmul! (src/gramian.jl:241-257) with the O(d) block product of src/gradient.jl:86-115."""
@@ -399,8 +422,8 @@ class BlockGramian(LazyOperator):
         n, m = self.inner.shape
         d = self.inner.x.shape[1]
         self.d = d
-        self.block = d + 1 if self.value else d
-        self.shape = (n * self.block, m * self.block)
+        self.block_size = d + 1 if self.value else d
+        self.shape = (n * self.block_size, m * self.block_size)
         self.dtype, self.device = self.inner.dtype, self.inner.device
 
     def issymmetric(self):
@@ -411,6 +434,47 @@ class BlockGramian(LazyOperator):
 
     def _entry(self):
         return _ffi.lib().covgram_valgrad_mvm if self.value else _ffi.lib().covgram_grad_mvm
+
+    def _kind(self):
+        return _ffi.BLOCK_VALUE_GRADIENT if self.value else _ffi.BLOCK_GRADIENT
+
+    # -- dense instantiation and indexing -----------------------------------------------------------
+    def _dense(self, inner):
+        """The dense block matrix of `inner`'s point sets: ONE covgram_block_matrix call into a column-major buffer."""
+        B = self.block_size
+        if self.d > BLOCK_MATRIX_MAX_D and self._kind() in (_ffi.BLOCK_GRADIENT, _ffi.BLOCK_VALUE_GRADIENT):
+            # wider points than covgram_block_matrix keeps in registers: the MVM (its panel path) applied to an identity, as before
+            sub = self if inner is self.inner else type(self)(self.g, inner.x, None if inner.y is inner.x else inner.y)
+            return LazyOperator.to_dense(sub)
+        nb, mb = inner.shape[0] * B, inner.shape[1] * B
+        buf = torch.empty((mb, nb), dtype=self.dtype, device=self.device)   # column-major (n B) x (m B)
+        if nb * mb:
+            ctx = inner._px.ctx.bind_stream()
+            _ffi.check(_ffi.lib().covgram_block_matrix(ctx, self._kind(), _ffi.kref(self._lower()), inner._px.handle, inner._py.handle,
+                                                       _ffi._P(buf.data_ptr()), nb, _ffi.DEVICE))
+        return buf.t()
+
+    def to_dense(self):
+        """Matrix(G) of the block Gramian (the reference's gramian(k, x, y, Val(false)), src/gramian.jl:125-130) on the device: one
+        store-bound pass, every pair's jet evaluated once."""
+        return self._dense(self.inner)
+
+    def block(self, i, j):
+        """The dense (|i| B) x (|j| B) sub-matrix of the blocks of the points i x j (ints, slices or index tensors OVER POINTS; two ints: one
+        B x B block), evaluated from the sliced point sets, never from the full matrix."""
+        x, y = self.inner.x, self.inner.y
+        d = x.shape[1]
+        xi = x[i % x.shape[0]].reshape(1, d) if isinstance(i, int) else x[i]
+        yj = y[j % y.shape[0]].reshape(1, d) if isinstance(j, int) else y[j]
+        return self._dense(Gramian(self.g.k, xi.reshape(-1, d), yj.reshape(-1, d)))
+
+    def __getitem__(self, IJ):
+        """G[I, J] over the flat (n B) x (m B) indices, ints and slices (getindex of the reference's BlockFactorization): the entries
+        are taken from block() of the points that cover them."""
+        I, J = IJ
+        (p0, p1, ri), (q0, q1, rj) = flat_cover(I, self.shape[0], self.block_size), flat_cover(J, self.shape[1], self.block_size)
+        sub = self.block(slice(p0, p1), slice(q0, q1))
+        return sub[ri][..., rj]
 
     def mul_(self, y, a, alpha=1.0, beta=0.0):
         spec = self._lower()
@@ -448,8 +512,8 @@ class HessianGramian(BlockGramian):
         self.inner = Gramian(g.k, x, y)
         n, m = self.inner.shape
         self.d = d = self.inner.x.shape[1]
-        self.block = d * d
-        self.shape = (n * self.block, m * self.block)
+        self.block_size = d * d
+        self.shape = (n * self.block_size, m * self.block_size)
         self.dtype, self.device = self.inner.dtype, self.inner.device
 
     def _lower(self):
@@ -457,6 +521,9 @@ class HessianGramian(BlockGramian):
 
     def _entry(self):
         return _ffi.lib().covgram_hess_mvm
+
+    def _kind(self):
+        return _ffi.BLOCK_HESSIAN
 
 
 class ValueGradientHessianGramian(BlockGramian):
@@ -470,8 +537,8 @@ class ValueGradientHessianGramian(BlockGramian):
         self.inner = Gramian(g.k, x, y)
         n, m = self.inner.shape
         self.d = d = self.inner.x.shape[1]
-        self.block = 1 + d + d * d
-        self.shape = (n * self.block, m * self.block)
+        self.block_size = 1 + d + d * d
+        self.shape = (n * self.block_size, m * self.block_size)
         self.dtype, self.device = self.inner.dtype, self.inner.device
 
     def _lower(self):
@@ -479,6 +546,9 @@ class ValueGradientHessianGramian(BlockGramian):
 
     def _entry(self):
         return _ffi.lib().covgram_valgradhess_mvm
+
+    def _kind(self):
+        return _ffi.BLOCK_VALUE_GRADIENT_HESSIAN
 
 
 class _ToeplitzBase(LazyOperator):

@@ -16,6 +16,7 @@
 #include "grad_wide.hpp"
 #include "hess_mvm.hpp"
 #include "vgh_mvm.hpp"
+#include "block_matrix.hpp"
 
 namespace covgram {
 
@@ -92,6 +93,30 @@ vgh_launch_fn vgh_launcher(int family) {
         case COVGRAM_IMQ: return launch_vgh_family_5;
         case COVGRAM_DOT: return launch_vgh_family_7;
         case COVGRAM_EXPDOT: return launch_vgh_family_8;
+        default: return nullptr;
+    }
+}
+// dense block Gramians (block_fam.hip: one translation unit per family)
+#define CG_DECL(n) int launch_bm_family_##n(const BlockMatArgs&, int dtype);
+CG_DECL(0) CG_DECL(1) CG_DECL(2) CG_DECL(3) CG_DECL(4) CG_DECL(5) CG_DECL(6) CG_DECL(7) CG_DECL(8) CG_DECL(9) CG_DECL(10) CG_DECL(11) CG_DECL(12)
+#undef CG_DECL
+#define CG_DECL(n) int launch_bmh_family_##n(const BlockMatArgs&, int dtype);
+CG_DECL(0) CG_DECL(2) CG_DECL(4) CG_DECL(5) CG_DECL(7) CG_DECL(8)
+#undef CG_DECL
+bm_launch_fn block_matrix_launcher(int family) {
+    static const bm_launch_fn t[NUM_TU_FAMILIES] = {
+        launch_bm_family_0, launch_bm_family_1, launch_bm_family_2, launch_bm_family_3, launch_bm_family_4, launch_bm_family_5, launch_bm_family_6,
+        launch_bm_family_7, launch_bm_family_8, launch_bm_family_9, launch_bm_family_10, launch_bm_family_11, launch_bm_family_12};
+    return (family >= 0 && family < NUM_TU_FAMILIES) ? t[family] : nullptr;
+}
+bm_launch_fn block_matrix_hess_launcher(int family) {
+    switch (family) {
+        case COVGRAM_EQ: return launch_bmh_family_0;
+        case COVGRAM_RQ: return launch_bmh_family_2;
+        case COVGRAM_CAUCHY: return launch_bmh_family_4;
+        case COVGRAM_IMQ: return launch_bmh_family_5;
+        case COVGRAM_DOT: return launch_bmh_family_7;
+        case COVGRAM_EXPDOT: return launch_bmh_family_8;
         default: return nullptr;
     }
 }
@@ -662,6 +687,7 @@ int covgram_ctx_get_info(covgram_ctx* ctx, const char* key, int64_t* value) {
     else if (!strcmp(key, "last_hess_path")) *value = ctx->last_hess_path;
     else if (!strcmp(key, "last_vgh_path")) *value = ctx->last_vgh_path;
     else if (!strcmp(key, "last_matrix_path")) *value = ctx->last_matrix_path;
+    else if (!strcmp(key, "last_block_matrix_path")) *value = ctx->last_block_matrix_path;
     else if (!strcmp(key, "last_sum_fused")) *value = ctx->last_sum_fused;
     else if (!strcmp(key, "last_mfma_instance")) *value = ctx->last_mfma_instance;
     else if (!strcmp(key, "last_mfma_sym_rt")) *value = ctx->last_mfma_sym_rt;
@@ -1841,6 +1867,72 @@ int covgram_valgradhess_mvm(covgram_ctx* ctx, const covgram_kernel* k, const cov
     CG_CHECK_HIP(hipGetLastError());
     if (loc == COVGRAM_HOST) {
         CG_CHECK_HIP(hipMemcpy2DAsync(y, (size_t)ldy * ts, y_all, (size_t)n * bd * ts, (size_t)n * bd * ts, nrhs, hipMemcpyDeviceToHost, ctx->stream));
+        CG_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return COVGRAM_OK;
+}
+
+// Dense instantiation of a block Gramian (block_matrix.hpp): the matrix covgram_grad_mvm / covgram_valgrad_mvm / covgram_hess_mvm /
+// covgram_valgradhess_mvm apply.  The kernels each MVM accepts, with its refusals.
+int covgram_block_matrix(covgram_ctx* ctx, int32_t kind, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, void* out,
+                         int64_t ldo, int32_t loc) {
+    int rc = check_pair(ctx, X, Y);
+    if (rc) return rc;
+    CG_REQUIRE(k != nullptr, COVGRAM_EINVAL, "kernel is NULL");
+    CG_REQUIRE(kind >= COVGRAM_BLOCK_GRADIENT && kind <= COVGRAM_BLOCK_VALUE_GRADIENT_HESSIAN, COVGRAM_EINVAL, "unknown block kind %d", kind);
+    const bool hess = kind == COVGRAM_BLOCK_HESSIAN || kind == COVGRAM_BLOCK_VALUE_GRADIENT_HESSIAN;
+    const int vflag = (kind == COVGRAM_BLOCK_VALUE_GRADIENT || kind == COVGRAM_BLOCK_VALUE_GRADIENT_HESSIAN) ? 1 : 0;
+    const int d = X->d;
+    if (hess) {   // the refusals of covgram_hess_mvm / covgram_valgradhess_mvm, word for word
+        static const char* const names[COVGRAM_NFAMILY] = {"ExponentiatedQuadratic", "Exponential", "RationalQuadratic", "GammaExponential", "Cauchy",
+                                                           "InverseMultiQuadratic", "MaternP", "Dot", "ExponentialDot", "Matern", "AsinDot"};
+        const char* w = vflag ? "ValueGradientHessianKernel" : "HessianKernel";
+        CG_REQUIRE(k->family != COVGRAM_COMPOSITE, COVGRAM_EUNSUPPORTED, "%s of a composite kernel (Sum / Product / Power) has no device path", w);
+        CG_REQUIRE(k->family >= 0 && k->family < COVGRAM_NFAMILY, COVGRAM_EUNSUPPORTED, "unknown kernel family %d", k->family);
+        CG_REQUIRE(hess_family_ok(k->family), COVGRAM_EUNSUPPORTED, "%s(%s) has no device path (no closed-form fourth derivative compiled)", w, names[k->family]);
+        CG_REQUIRE(k->power == 1, COVGRAM_EUNSUPPORTED, "%s(%s^%d): Power wrappers have no device path", w, names[k->family], k->power);
+        CG_REQUIRE(d <= HESS_MAX_D, COVGRAM_EUNSUPPORTED, "%s(%s): d = %d exceeds the compiled maximum %d", w, names[k->family], d, HESS_MAX_D);
+    }
+    const int64_t n = X->n, m = Y->n;
+    const int64_t B = vflag + (kind == COVGRAM_BLOCK_HESSIAN ? 0 : (int64_t)d) + (hess ? (int64_t)d * d : 0);
+    const int64_t NB = n * B, MB = m * B;
+    CG_REQUIRE(ldo >= NB, COVGRAM_EINVAL, "ldo=%lld < n B=%lld", (long long)ldo, (long long)NB);
+    CG_REQUIRE(out != nullptr || NB * MB == 0, COVGRAM_EINVAL, "out is NULL");
+    const int dtype = X->dtype;
+    const size_t ts = dtype_size(dtype);
+    HostKernel hk;
+    // gamma = 1 / l, unfolded EQ: the parameter block of the block MVMs.  The gradient kinds evaluate their jets in fp64 whatever the
+    // dtype of the points (block_matrix.hpp: JT), so they take the fp64 block: the Taylor switches of the Matern profiles sit at
+    // eps(T)^(1/p), and the fp32 ones leave 5e-5 of a single pair's phi'' next to the switch
+    rc = make_host_kernel(k, hess ? dtype : COVGRAM_F64, true, &hk);
+    if (rc) return rc;
+    bm_launch_fn launch = hess ? block_matrix_hess_launcher(hk.tu_family) : block_matrix_launcher(hk.tu_family);
+    CG_REQUIRE(launch != nullptr, COVGRAM_EUNSUPPORTED, "block matrix: no kernel for family %d", hk.tu_family);
+    const int D = bm_pad_dim(d, hess);
+    CG_REQUIRE(D > 0, COVGRAM_EUNSUPPORTED, "block matrix: d = %d exceeds the compiled maximum %d (rows in registers)", d, hess ? 32 : 64);
+    CG_DEVICE(ctx);
+    ctx->last_block_matrix_path = 0;
+    if (n == 0 || m == 0) return COVGRAM_OK;
+    void* o = out;
+    int64_t ld = ldo;
+    if (loc == COVGRAM_HOST) { rc = ws_reserve(ctx, 3, (size_t)NB * MB * ts, &o); if (rc) return rc; ld = NB; }
+    // 16-byte streaming stores (4 fp32 / 2 fp64 consecutive rows per thread) when a thread's rows stay inside one point (VR | B), the
+    // leading dimension is a multiple of VR and out is 16-byte aligned: the rule of covgram_matrix.  One arithmetic either way.
+    const int VRW = 16 / (int)ts;
+    const bool wide = B % VRW == 0 && ld % VRW == 0 && ((uintptr_t)o % 16) == 0;
+    BlockMatArgs a;
+    a.X = X->dptr; a.n = n; a.Y = Y->dptr; a.m = m; a.d = d; a.parts = vflag | (kind == COVGRAM_BLOCK_HESSIAN ? 0 : 2); a.out = o; a.ldo = ld; a.Dpad = D; a.vr = wide ? VRW : 1;
+    a.hess = hess ? 1 : 0; a.hk = &hk; a.stream = ctx->stream;
+    a.W = (int32_t)std::max<int64_t>(1, 64 / B);        // a strip of about 64 columns per workgroup, as covgram_matrix
+    auto* tm = timer_next(ctx);
+    if (tm) (void)hipEventRecord(tm->first, ctx->stream);
+    rc = launch(a, dtype);
+    if (tm) (void)hipEventRecord(tm->second, ctx->stream);   // also after a refused launch: the bracket stays a pair
+    if (rc) return rc;
+    ctx->last_block_matrix_path = (kind + 1) + 10 * a.vr;
+    CG_CHECK_HIP(hipGetLastError());
+    if (loc == COVGRAM_HOST) {
+        CG_CHECK_HIP(hipMemcpy2DAsync(out, (size_t)ldo * ts, o, (size_t)NB * ts, (size_t)NB * ts, MB, hipMemcpyDeviceToHost, ctx->stream));
         CG_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     }
     return COVGRAM_OK;

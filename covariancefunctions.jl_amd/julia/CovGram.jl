@@ -311,6 +311,35 @@ function LinearAlgebra.mul!(Y::StridedMatrix{T}, B::BlockFactorizations.BlockFac
                        device_blockmul!(:valgradhess, Y, G, A, α, β, spec)
 end
 
+# --- src/gramian.jl:125-130, 192-199: Matrix of the four block Gramians -> covgram_block_matrix (one store-bound pass; the jet of a pair
+# evaluated once for its whole block).  Blocks are point-major with the ordering of the block mul!s above.
+const BLOCK_GRADIENT, BLOCK_VALUE_GRADIENT, BLOCK_HESSIAN, BLOCK_VALUE_GRADIENT_HESSIAN = Int32(0), Int32(1), Int32(2), Int32(3)
+function device_blockmatrix(kind::Int32, G::Gramian, ::Type{T}, bd::Integer, spec) where {T}
+    X = points(G.x, T); Y = G.x === G.y ? X : points(G.y, T)
+    n, m = size(G)
+    M = Matrix{T}(undef, n * bd, m * bd)
+    check(ccall((:covgram_block_matrix, libcovgram), Cint, (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32),
+                ctx(), kind, kref(spec), X.handle, Y.handle, M, Int64(n * bd), HOST))
+    return M
+end
+function Base.Matrix(B::BlockFactorizations.BlockFactorization{T, <:Gramian{<:Any, <:GradientKernel}}) where {T <: DevFloat}
+    G = B.A; spec = device_kernel_for(G.k.k); d = length(first(G.x))
+    (spec === nothing || d > 64) ? invoke(Matrix, Tuple{BlockFactorizations.BlockFactorization}, B) : device_blockmatrix(BLOCK_GRADIENT, G, T, d, spec)
+end
+function Base.Matrix(B::BlockFactorizations.BlockFactorization{T, <:Gramian{<:Any, <:ValueGradientKernel}}) where {T <: DevFloat}
+    G = B.A; spec = device_kernel_for(G.k.k); d = length(first(G.x))
+    (spec === nothing || d > 64) ? invoke(Matrix, Tuple{BlockFactorizations.BlockFactorization}, B) : device_blockmatrix(BLOCK_VALUE_GRADIENT, G, T, d + 1, spec)
+end
+function Base.Matrix(B::BlockFactorizations.BlockFactorization{T, <:Gramian{<:Any, <:HessianKernel}}) where {T <: DevFloat}
+    G = B.A; d = length(first(G.x)); spec = hessian_spec(G.k.k, d)
+    spec === nothing ? invoke(Matrix, Tuple{BlockFactorizations.BlockFactorization}, B) : device_blockmatrix(BLOCK_HESSIAN, G, T, d * d, spec)
+end
+function Base.Matrix(B::BlockFactorizations.BlockFactorization{T, <:Gramian{<:Any, <:ValueGradientHessianKernel}}) where {T <: DevFloat}
+    G = B.A; d = length(first(G.x)); spec = hessian_spec(G.k.k, d)
+    spec === nothing ? invoke(Matrix, Tuple{BlockFactorizations.BlockFactorization}, B) :
+                       device_blockmatrix(BLOCK_VALUE_GRADIENT_HESSIAN, G, T, 1 + d + d * d, spec)
+end
+
 # --- src/separable.jl:38-42: mul!(y, G::Gramian{<:AbstractMatrix, <:SeparableKernel}, x) on vectors of vectors -----------------
 # The reference multiplies by kronecker(G) = gramian(k.k, x, y) ⊗ k.B (:33-35): block i of the result is B Σ_j k(x_i, y_j) a_j.  With
 # the blocks of `a` as the ROWS of an m × q matrix that is (G_scalar A) Bᵀ: ONE covgram_mvm with q right-hand sides (every entry of

@@ -16,6 +16,7 @@
  *   covgram_valgrad_mvm    the same  blockmul! with the ValueGradientKernel element                       src/gradient.jl:319-351, 400-474
  *   covgram_hess_mvm       the same  blockmul! with the HessianKernel elements' O(d^2) mul!             src/hessian.jl:125-190, 227-275
  *   covgram_valgradhess_mvm the same blockmul! with the ValueGradientHessianKernel elements, in O(d^2)           src/hessian.jl:279-325, 392-479
+ *   covgram_block_matrix   replaces  Base.Matrix(G) of those four block Gramians (gramian(k, x, y, Val(false)))   src/gramian.jl:125-130, 192-199
  *   covgram_toeplitz_*     replaces  mul!(y, ::SymmetricToeplitz/Toeplitz/Circulant, a, α, β) of ToeplitzMatrices 0.7.1 as
  *                          constructed by gramian(k, x::StepRangeLen, y::StepRangeLen)            src/gramian.jl:167-189
  *   covgram_toeplitz_durbin / _levinson / _trench  replace durbin! / levinson! / trench!             src/toeplitz.jl:12-111
@@ -53,7 +54,8 @@ extern "C" {
                                (covgram_comm_*), covgram_mvm_sharded, covgram_mvm_sym_allreduce.  Added since, backward
                                compatibly (no version step): covgram_hess_mvm and the info key "last_hess_path";
                                covgram_valgradhess_mvm and the info key "last_vgh_path";
-                               the info key "last_matrix_path".
+                               the info key "last_matrix_path";
+                               covgram_block_matrix, the COVGRAM_BLOCK_* kinds and the info key "last_block_matrix_path".
                                A binding checks covgram_version() against the header it mirrors at load time */
 
 typedef enum covgram_status {
@@ -193,7 +195,7 @@ int covgram_ctx_set_option(covgram_ctx* ctx, const char* key, int64_t value);
  * ran: 0 none yet or n m == 0, otherwise route + 10 DM + 1000 VR with route 1 = generic single profile, 2 = generic composite,
  * 3 = registers single profile, 4 = registers composite; DM the compiled dimension bucket, 0 for the generic kernels; VR rows per
  * thread, 1 where not applicable), "last_mfma_lds" (1: that matrix-core MVM shared its column tiles through LDS), "last_mfma_sym" (1: the last dense
- * MVM ran the symmetric upper-triangle kernel), "last_dense_sym" (1: it ran a direct-difference symmetric kernel, fp64 or fp32), "last_inkernel_reduce" (1: the last dense kernel summed its own split-J slab), "last_grad_expand" (1: the last gradient MVM ran the expanded form), "last_grad_bcast" (waves per workgroup of the broadcast kernel if the last gradient MVM ran it, else 0), "last_grad_path" (which kernels the last gradient or value-gradient MVM ran, as bits: 1 = the lane-per-row kernel, 2 = its two-column pass, 4 = the panel path (grad_wide), 8 = more than one panel, 16 = the panel path split over z slices with the separate reduce, 32 = the lane-per-row kernel with a column split > 1 and the slab reduce; 0 = no block kernel (n = 0 or m = 0); a Sum split term by term reports its last term), "last_grad_jsplit" (the column split of the last gradient MVM's lane-per-row launch, 0 if it did not run one), "last_hess_path" (0 = no Hessian MVM yet or one without rows / columns, 1 = the last covgram_hess_mvm ran its block kernel, csrc/hess_mvm.hpp), "last_sum_fused" (1: the last covgram_mvm ran a Sum on the one-pass kernels), "last_mfma_instance" (which instance of the matrix-core EQ kernels the last launch was: the template arguments of dense_mfma_eq_kernel as K2 1e5 + RT 1e4 + WPB 1e3 + LDS 100 + STAMP 10 + FMT, -(K2 10 + FMT) for the symmetric kernel, 0 otherwise — bench.py checks its recorded PMC pass against it), "last_dense_bcast" (1: the last fp64 dense MVM ran a register-broadcast kernel), "last_mfma_f16" (1: the last general matrix-core EQ MVM ran the fp16 two-way split), "last_jsplit" (the column split of the last lane-per-row dense launch), "last_kron_path" (which kernels the last covgram_kron_mvm ran, as bits: 1 = the fused last-two-modes pass, 2 = the single-mode kernel, 4 = the last-mode kernel, 8 = a rocBLAS GEMM (a factor side >= 1024, >= 256 with >= 2 GFLOP, or a shape the kernels refuse), 16 = two small trailing factors multiplied out first), "num_cus", "last_clock_khz" (median shader clock over the workgroups of the last
+ * MVM ran the symmetric upper-triangle kernel), "last_dense_sym" (1: it ran a direct-difference symmetric kernel, fp64 or fp32), "last_inkernel_reduce" (1: the last dense kernel summed its own split-J slab), "last_grad_expand" (1: the last gradient MVM ran the expanded form), "last_grad_bcast" (waves per workgroup of the broadcast kernel if the last gradient MVM ran it, else 0), "last_grad_path" (which kernels the last gradient or value-gradient MVM ran, as bits: 1 = the lane-per-row kernel, 2 = its two-column pass, 4 = the panel path (grad_wide), 8 = more than one panel, 16 = the panel path split over z slices with the separate reduce, 32 = the lane-per-row kernel with a column split > 1 and the slab reduce; 0 = no block kernel (n = 0 or m = 0); a Sum split term by term reports its last term), "last_grad_jsplit" (the column split of the last gradient MVM's lane-per-row launch, 0 if it did not run one), "last_hess_path" (0 = no Hessian MVM yet or one without rows / columns, 1 = the last covgram_hess_mvm ran its block kernel, csrc/hess_mvm.hpp), "last_block_matrix_path" (0 = no covgram_block_matrix yet or an empty product, otherwise (kind + 1) + 10 VR, VR = scalars per store instruction of the launch that ran: 1, or 2 for fp64 / 4 for fp32 on the 16-byte route), "last_sum_fused" (1: the last covgram_mvm ran a Sum on the one-pass kernels), "last_mfma_instance" (which instance of the matrix-core EQ kernels the last launch was: the template arguments of dense_mfma_eq_kernel as K2 1e5 + RT 1e4 + WPB 1e3 + LDS 100 + STAMP 10 + FMT, -(K2 10 + FMT) for the symmetric kernel, 0 otherwise — bench.py checks its recorded PMC pass against it), "last_dense_bcast" (1: the last fp64 dense MVM ran a register-broadcast kernel), "last_mfma_f16" (1: the last general matrix-core EQ MVM ran the fp16 two-way split), "last_jsplit" (the column split of the last lane-per-row dense launch), "last_kron_path" (which kernels the last covgram_kron_mvm ran, as bits: 1 = the fused last-two-modes pass, 2 = the single-mode kernel, 4 = the last-mode kernel, 8 = a rocBLAS GEMM (a factor side >= 1024, >= 256 with >= 2 GFLOP, or a shape the kernels refuse), 16 = two small trailing factors multiplied out first), "num_cus", "last_clock_khz" (median shader clock over the workgroups of the last
  * launch made with "mfma_stamp" = 1; synchronises the stream; 0 = no stamped launch yet). */
 int covgram_ctx_get_info(covgram_ctx* ctx, const char* key, int64_t* value);
 int covgram_sync(covgram_ctx* ctx);
@@ -321,6 +323,25 @@ int covgram_hess_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram_po
  * Aliasing: a and y may overlap in any way; a is then read from a private copy. */
 int covgram_valgradhess_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, const void* a,
                             int64_t lda, void* y, int64_t ldy, int32_t nrhs, double alpha, double beta, int32_t loc);
+
+/* Dense instantiation of a block Gramian: out[(i B + p) + (j B + q) ldo] = entry (p, q) of block (i, j), the (n B) x (m B) matrix the MVM
+ * of the same kind applies (column c is that MVM applied to the unit vector e_c), column-major, point-major blocks, with the ordering
+ * inside a block that the MVM's comment above fixes: the value first, then the gradient, then Hessian component (a, b) at a + b d.
+ * Any n and m (0: nothing is written); ldo >= n B, else COVGRAM_EINVAL; only the rows < n B of each column are written, with loc == HOST
+ * as with loc == DEVICE.  r = x_i - y_j is a direct difference (no expanded form, no radius gate).  Kernels: those of the MVM of the
+ * same kind with the same refusals — gradient / value-gradient: single profiles of both traits, Power wrappers, MaternP, Matern(nu),
+ * Sum / Product composites, with the rows in registers (d <= 64); Hessian / value-gradient-Hessian: EQ, RQ, Cauchy, IMQ, ExponentialDot
+ * and Dot (under COVGRAM_BLOCK_HESSIAN a matrix of zeros, which IS written), d <= 32, everything else COVGRAM_EUNSUPPORTED with a message
+ * that names the kernel.  A thread writes VR = 4 (fp32) / 2 (fp64) consecutive rows with one 16-byte streaming store per column when
+ * B and ldo are multiples of VR and out is 16-byte aligned (loc == HOST: the staged tile has leading dimension n B), otherwise one row
+ * (VR = 1) with the same arithmetic: the entries do not depend on ldo or on the alignment of out.  Info key "last_block_matrix_path";
+ * option "time_kernels" brackets the kernel. */
+#define COVGRAM_BLOCK_GRADIENT 0               /* B = d            blocks of covgram_grad_mvm        */
+#define COVGRAM_BLOCK_VALUE_GRADIENT 1         /* B = d + 1        blocks of covgram_valgrad_mvm     */
+#define COVGRAM_BLOCK_HESSIAN 2                /* B = d*d          blocks of covgram_hess_mvm        */
+#define COVGRAM_BLOCK_VALUE_GRADIENT_HESSIAN 3 /* B = 1 + d + d*d  blocks of covgram_valgradhess_mvm */
+int covgram_block_matrix(covgram_ctx* ctx, int32_t kind, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, void* out,
+                         int64_t ldo, int32_t loc);
 
 /* Toeplitz T[i,j] = vc[i-j] (i >= j), vr[j-i] (i < j); vr == NULL: symmetric (vr = vc, m = n).
  * circulant != 0: T[i,j] = vc[(i-j) mod n] (vr must be NULL).  The spectrum of the circulant embedding
