@@ -114,6 +114,12 @@ PROTOTYPES = {
     "covgram_comm_all_reduce_sum": (C.c_int, [_P, _P, _I64, _I32]),
     "covgram_mvm_sharded": (C.c_int, [_P, _KP, _P, _P, _P, _P, _D, _D]),
     "covgram_mvm_sym_allreduce": (C.c_int, [_P, _KP, _P, _P, _P, _D, _D]),
+    "covgram_decay_radius": (C.c_int, [_KP, _D, C.POINTER(_D)]),
+    "covgram_sparse_create": (C.c_int, [_P, C.POINTER(_P), _KP, _P, _P, _D]),
+    "covgram_sparse_info": (C.c_int, [_P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I32), C.POINTER(_D)]),
+    "covgram_sparse_export": (C.c_int, [_P, _P, _P, _P, _I32]),
+    "covgram_sparse_mvm": (C.c_int, [_P, _P, _I64, _P, _I64, _I32, _D, _D, _I32]),
+    "covgram_sparse_destroy": (C.c_int, [_P]),
     "covgram_toeplitz_create": (C.c_int, [_P, C.POINTER(_P), _P, _P, _I64, _I64, _I32, _I32, _I32]),
     "covgram_toeplitz_mvm": (C.c_int, [_P, _P, _P, _D, _D, _I32]),
     "covgram_toeplitz_destroy": (C.c_int, [_P]),

@@ -617,6 +617,94 @@ class Circulant(_ToeplitzBase):
         super().__init__(vc, None, True)
 
 
+class SparseGramian(LazyOperator):
+    """sparse(G, δ) (src/sparse.jl:5-22): the entries of gramian(k, x, y) within the kernel's decay radius, as a CSR matrix that lives
+    on the device (covgram_sparse_create); `mul!` is the library's CSR product (covgram_sparse_mvm).  The handle owns its arrays and
+    keeps no reference to the Gramian's points."""
+
+    def __init__(self, G: "Gramian", delta: float = 1e-6):
+        self.delta = float(delta)
+        self.shape, self.dtype, self.device = G.shape, G.dtype, G.device
+        self._ctx = G._px.ctx
+        self.handle = _ffi._P()
+        _ffi.check(_ffi.lib().covgram_sparse_create(self._ctx.bind_stream(), C.byref(self.handle), _ffi.kref(G._spec()), G._px.handle,
+                                                    G._py.handle, self.delta))
+        n, m, nnz, dt, r = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_double(0)
+        _ffi.check(_ffi.lib().covgram_sparse_info(self.handle, C.byref(n), C.byref(m), C.byref(nnz), C.byref(dt), C.byref(r)))
+        self.nnz, self.radius = int(nnz.value), float(r.value)
+
+    def __del__(self):
+        try:
+            if self.handle:
+                _ffi.lib().covgram_sparse_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+    def csr(self):
+        """(rowptr, colind, vals): int64 n + 1, int32 nnz (0-based, ascending within a row), nnz scalars — copies, as device tensors."""
+        rowptr = torch.empty(self.shape[0] + 1, dtype=torch.int64, device=self.device)
+        colind = torch.empty(self.nnz, dtype=torch.int32, device=self.device)
+        vals = torch.empty(self.nnz, dtype=self.dtype, device=self.device)
+        self._ctx.bind_stream()
+        _ffi.check(_ffi.lib().covgram_sparse_export(self.handle, _ffi._P(rowptr.data_ptr()), _ffi._P(colind.data_ptr()),
+                                                    _ffi._P(vals.data_ptr()), _ffi.DEVICE))
+        return rowptr, colind, vals
+
+    def mul_(self, y, a, alpha=1.0, beta=0.0):
+        n, m = self.shape
+        a = _vec_arg(a, m, self.dtype, self.device, "a")
+        if y.shape[0] != n or y.dtype != self.dtype or tuple(y.shape[1:]) != tuple(a.shape[1:]):
+            raise _ffi.DimensionMismatch(_ffi.EINVAL, f"DimensionMismatch: y has shape {tuple(y.shape)}, expected ({n}, ...) of {self.dtype}")
+        self._ctx.bind_stream()
+        lib = _ffi.lib()
+        if a.dim() == 1:
+            a_c = a.contiguous()
+            y_c = y if y.is_contiguous() else y.contiguous()
+            _ffi.check(lib.covgram_sparse_mvm(self.handle, _ffi._P(a_c.data_ptr()), max(m, 1), _ffi._P(y_c.data_ptr()), max(n, 1), 1,
+                                              float(alpha), float(beta), _ffi.DEVICE))
+            if y_c is not y:
+                y.copy_(y_c)
+            return y
+        p = a.shape[1]
+        if p == 0:                                             # no columns: nothing to do (the ABI requires nrhs >= 1)
+            return y
+        a_cm = a.t().contiguous()                              # (p, m) row-major == m×p column-major
+        direct = y.t().is_contiguous()
+        y_cm = y.t() if direct else y.t().contiguous()
+        _ffi.check(lib.covgram_sparse_mvm(self.handle, _ffi._P(a_cm.data_ptr()), max(m, 1), _ffi._P(y_cm.data_ptr()), max(n, 1), p,
+                                          float(alpha), float(beta), _ffi.DEVICE))
+        if not direct:
+            y.copy_(y_cm.t())
+        return y
+
+    def to_dense(self):
+        n, m = self.shape
+        rowptr, colind, vals = self.csr()
+        out = torch.zeros((n, m), dtype=self.dtype, device=self.device)
+        if self.nnz:
+            rows = torch.repeat_interleave(torch.arange(n, device=self.device), rowptr[1:] - rowptr[:-1])
+            out[rows, colind.long()] = vals
+        return out
+
+
+def decay_radius(k, delta: float = 1e-6) -> float:
+    """decay_radius(k, δ) of src/sparse.jl:24-38, with the two corrections described at kernels.decay_radius."""
+    return K.decay_radius(k, delta)
+
+
+def sparse(G, delta: float = 1e-6) -> SparseGramian:
+    """SparseArrays.sparse(G::Gramian, δ = 1e-6): a plain scalar Gramian of a kernel that has a decay radius; block and structured
+    Gramians and every other kernel raise UnsupportedKernel."""
+    if type(G) is not Gramian:
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"sparse: {type(G).__name__} is not a plain scalar Gramian (block and structured "
+                                                        "Gramians have no sparse form)")
+    # refusals name the kernel before anything touches the device; the value is discarded: the radius in use is the library's own
+    # (covgram_sparse_create computes it again, S.radius reports it), and tests/test_sparse_host.py holds the two together to 1e-15
+    K.decay_radius(G.k, delta)
+    return SparseGramian(G, delta)
+
+
 class KroneckerProduct(LazyOperator):
     """kronecker(F_1, ..., F_q) (KroneckerProducts 1.1.1): standard order, F_1 = slowest index.  Factors are
     lazy Gramians or dense matrices; lazy factors are instantiated once on the device (they are the small

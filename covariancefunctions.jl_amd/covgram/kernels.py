@@ -780,3 +780,60 @@ def require_vgh_spec(k, d: Optional[int] = None):
     if d is not None and d > HESSIAN_MAX_D:
         raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"ValueGradientHessianKernel({name}): d = {d} exceeds the compiled maximum {HESSIAN_MAX_D}")
     return spec
+
+
+# ----------------------------------------------------------------------------------------------
+# decay radius of exponentially decaying isotropic kernels (src/sparse.jl:24-38)
+# ----------------------------------------------------------------------------------------------
+def decay_radius(k, delta: float = 1e-6) -> float:
+    """The distance beyond which |k| < delta, for ONE isotropic profile under Lengthscale and Constant factors (src/sparse.jl:25-38):
+    EQ sqrt(-2 ln de), Exponential -ln de, GammaExponential(g) (-2 ln de)^(1/g), MaternP and Matern(nu >= 1/2) -ln de (conservative).
+
+    Two deliberate corrections of the reference (the same as covgram_decay_radius, include/covgram.h): Lengthscale(k, l) evaluates
+    k(r / l), so the radius is l r0 (src/sparse.jl:38 drops its delta argument and divides by l); a Constant factor c uses
+    de = delta / |c| in place of delta.  0 < delta / |c| < 1 is required (ValueError).  Matern(nu < 1/2) raises DomainError as in the
+    reference; kernels without exponential decay (RQ, Cauchy, IMQ, dot-product kernels), Power wrappers, composites and GenericInput
+    kernels raise UnsupportedKernel naming the kernel (the reference's TypeError branch)."""
+    top = k
+    scale, ls = 1.0, 1.0
+
+    def refuse(what):
+        return _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"decay_radius: {what} (defined for EQ, Exponential, GammaExponential, MaternP and "
+                                                         f"Matern under Lengthscale and Constant factors); kernel: {type(top).__name__}")
+
+    while True:
+        if isinstance(k, Product):
+            rest = [a for a in k.args if not isinstance(a, Constant)]
+            if len(rest) != 1:
+                raise refuse(f"a Product of {len(rest)} profiles has no single decay radius")
+            for c in k.args:
+                if isinstance(c, Constant):
+                    scale *= c.c
+            k = rest[0]
+        elif isinstance(k, Lengthscale):
+            ls *= k.l
+            k = k.k
+        elif isinstance(k, (Sum, Power)):
+            raise refuse(f"{type(k).__name__} has no single decay radius")
+        else:
+            break
+    if isinstance(k, (RationalQuadratic, Cauchy, InverseMultiQuadratic, DotProductKernel, Constant)):
+        raise refuse(f"{type(k).__name__} does not decay exponentially")
+    if not isinstance(k, (ExponentiatedQuadratic, Exponential, GammaExponential, MaternP, Matern)):
+        raise refuse(f"{type(k).__name__} is not an isotropic profile with a known decay radius")
+    if isinstance(k, Matern) and k.nu < 0.5:
+        raise DomainError(f"decay_radius not defined for Matern kernel with ν = {k.nu} < 1/2")
+    delta = float(delta)
+    c = abs(scale)
+    if not (c > 0 and 0 < delta / c < 1):
+        raise ValueError(f"decay_radius: need 0 < delta / |c| < 1 (delta = {delta}, Constant factor c = {scale})")
+    de = delta / c
+    if isinstance(k, ExponentiatedQuadratic):
+        r0 = math.sqrt(-2.0 * math.log(de))
+    elif isinstance(k, GammaExponential):
+        if not k.gamma > 0:
+            raise DomainError(f"decay_radius: gamma = {k.gamma} not in (0, 2]")
+        r0 = math.pow(-2.0 * math.log(de), 1.0 / k.gamma)
+    else:
+        r0 = -math.log(de)
+    return ls * r0

@@ -20,6 +20,7 @@
 module CovGram
 
 using LinearAlgebra
+using SparseArrays
 using CovarianceFunctions
 using CovarianceFunctions: Gramian, GradientKernel, ValueGradientKernel, HessianKernel, ValueGradientHessianKernel, IsotropicInput, DotProductInput, StationaryInput,
                            GenericInput, input_trait, EQ, RQ, Exp, γExp, Cauchy, InverseMultiQuadratic, MaternP, Dot,
@@ -565,6 +566,66 @@ function gramian(k::FiniteBasis{T}, x::AbstractVector, y::AbstractVector) where 
     U = CovarianceFunctions.basis(k, x)
     V = x === y ? U : CovarianceFunctions.basis(k, y)
     DeviceLowRank{T}(U, V)
+end
+
+# --- src/sparse.jl:5-38: sparse(G, δ) -> covgram_sparse_* (count / scan / fill on the device instead of the ball-tree range search) ------
+# decay_radius as the LIBRARY defines it (include/covgram.h): l r0(δ / |c|) — src/sparse.jl:38 divides by l and drops δ, and ignores
+# Constant factors; both are put right there.
+function device_decay_radius(spec, δ::Real)
+    r = Ref{Float64}(0.0)
+    check(ccall((:covgram_decay_radius, libcovgram), Cint, (Ptr{Cvoid}, Float64, Ref{Float64}), kref(spec), Float64(δ), r))
+    r[]
+end
+# the device-resident CSR matrix itself, for callers that keep multiplying on the GPU (host vectors are staged per call)
+mutable struct DeviceSparse{T} <: AbstractMatrix{T}
+    handle::Ptr{Cvoid}
+    n::Int; m::Int; nnz::Int; radius::Float64
+    function DeviceSparse(k, x, y, ::Type{T}, δ::Real, spec) where {T <: DevFloat}
+        X = points(x, T); Y = x === y ? X : points(y, T)
+        h = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ccall((:covgram_sparse_create, libcovgram), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64),
+                    ctx(), h, kref(spec), X.handle, Y.handle, Float64(δ)))
+        n = Ref{Int64}(0); m = Ref{Int64}(0); nnz = Ref{Int64}(0); dt = Ref{Int32}(0); r = Ref{Float64}(0.0)
+        check(ccall((:covgram_sparse_info, libcovgram), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int32}, Ref{Float64}),
+                    h[], n, m, nnz, dt, r))
+        S = new{T}(h[], n[], m[], nnz[], r[])
+        finalizer(q -> ccall((:covgram_sparse_destroy, libcovgram), Cint, (Ptr{Cvoid},), q.handle), S)
+        S
+    end
+end
+Base.size(S::DeviceSparse) = (S.n, S.m)
+# (rowptr, colind, vals) of the CSR arrays, 0-based as the library stores them
+function csr(S::DeviceSparse{T}) where {T}
+    rowptr = Vector{Int64}(undef, S.n + 1); colind = Vector{Int32}(undef, S.nnz); vals = Vector{T}(undef, S.nnz)
+    check(ccall((:covgram_sparse_export, libcovgram), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int32}, Ptr{Cvoid}, Int32),
+                S.handle, rowptr, colind, vals, HOST))
+    rowptr, colind, vals
+end
+function LinearAlgebra.mul!(y::StridedVecOrMat{T}, S::DeviceSparse{T}, a::StridedVecOrMat{T}, α::Real = 1, β::Real = 0) where {T <: DevFloat}
+    size(a, 1) == S.m && size(y, 1) == S.n && size(y, 2) == size(a, 2) || throw(DimensionMismatch("mul!: size mismatch"))
+    size(a, 2) == 0 && return y                        # no columns: nothing to do (the ABI requires nrhs >= 1)
+    check(ccall((:covgram_sparse_mvm, libcovgram), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int32, Float64, Float64, Int32),
+                S.handle, a, max(stride(a, 2), S.m), y, max(stride(y, 2), S.n), size(a, 2), Float64(α), Float64(β), HOST))
+    return y
+end
+function Base.getindex(S::DeviceSparse{T}, i::Integer, j::Integer) where {T}   # (for show and tests; not a hot path)
+    rowptr, colind, vals = csr(S)
+    for p in rowptr[i] + 1:rowptr[i + 1]
+        colind[p] == j - 1 && return vals[p]
+    end
+    zero(T)
+end
+# sparse(G, δ): the reference's SparseMatrixCSC.  An isotropic kernel is symmetric in its arguments, so the handle is built with X and Y
+# EXCHANGED: the CSR arrays of the m × n matrix sparse(gramian(k, y, x)) are, plus 1, the colptr / rowval / nzval of the n × m CSC matrix.
+# Only a kernel without a device spec goes to the reference's method (its signature as of src/sparse.jl:5); a kernel that has a spec but
+# no decay radius (RQ, a Sum, a Power, ...) is refused by the library, by name, through check(...): INTEGRATION.md.
+function SparseArrays.sparse(G::Gramian{T}, δ::Real = 1e-6; leafsize::Int = 16) where {T <: DevFloat}
+    spec = device_kernel_for(G.k)
+    spec === nothing && return invoke(SparseArrays.sparse, Tuple{Gramian, Real}, G, δ; leafsize = leafsize)
+    n, m = size(G)
+    St = DeviceSparse(G.k, G.y, G.x, T, δ, spec)
+    rowptr, colind, vals = csr(St)
+    SparseArrays.SparseMatrixCSC{T, Int64}(n, m, rowptr .+ 1, Int64.(colind) .+ 1, vals)
 end
 
 end # module

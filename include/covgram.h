@@ -17,6 +17,8 @@
  *   covgram_hess_mvm       the same  blockmul! with the HessianKernel elements' O(d^2) mul!             src/hessian.jl:125-190, 227-275
  *   covgram_valgradhess_mvm the same blockmul! with the ValueGradientHessianKernel elements, in O(d^2)           src/hessian.jl:279-325, 392-479
  *   covgram_block_matrix   replaces  Base.Matrix(G) of those four block Gramians (gramian(k, x, y, Val(false)))   src/gramian.jl:125-130, 192-199
+ *   covgram_sparse_create  replaces  SparseArrays.sparse(G::Gramian, delta) and decay_radius(k, delta)         src/sparse.jl:5-38
+ *   covgram_sparse_mvm     replaces  mul!(y, ::SparseMatrixCSC, a, alpha, beta) on its result
  *   covgram_toeplitz_*     replaces  mul!(y, ::SymmetricToeplitz/Toeplitz/Circulant, a, α, β) of ToeplitzMatrices 0.7.1 as
  *                          constructed by gramian(k, x::StepRangeLen, y::StepRangeLen)            src/gramian.jl:167-189
  *   covgram_toeplitz_durbin / _levinson / _trench  replace durbin! / levinson! / trench!             src/toeplitz.jl:12-111
@@ -55,7 +57,8 @@ extern "C" {
                                compatibly (no version step): covgram_hess_mvm and the info key "last_hess_path";
                                covgram_valgradhess_mvm and the info key "last_vgh_path";
                                the info key "last_matrix_path";
-                               covgram_block_matrix, the COVGRAM_BLOCK_* kinds and the info key "last_block_matrix_path".
+                               covgram_block_matrix, the COVGRAM_BLOCK_* kinds and the info key "last_block_matrix_path";
+                               covgram_decay_radius and the covgram_sparse_* handle (sparse(G, delta)).
                                A binding checks covgram_version() against the header it mirrors at load time */
 
 typedef enum covgram_status {
@@ -126,6 +129,7 @@ typedef struct covgram_kernel_composite {
 typedef struct covgram_ctx covgram_ctx;           /* one device + one stream + workspace + rocFFT plans */
 typedef struct covgram_points covgram_points;     /* device-resident point set (stays resident across MVMs) */
 typedef struct covgram_toeplitz covgram_toeplitz; /* cached circulant spectrum + plans */
+typedef struct covgram_sparse covgram_sparse;     /* radius-thresholded CSR Gramian: owns its three arrays */
 
 int covgram_version(void);
 /* sizeof() of the two structs that cross the ABI by pointer, as THIS build of the library sees them: a binding asserts its
@@ -342,6 +346,47 @@ int covgram_valgradhess_mvm(covgram_ctx* ctx, const covgram_kernel* k, const cov
 #define COVGRAM_BLOCK_VALUE_GRADIENT_HESSIAN 3 /* B = 1 + d + d*d  blocks of covgram_valgradhess_mvm */
 int covgram_block_matrix(covgram_ctx* ctx, int32_t kind, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, void* out,
                          int64_t ldo, int32_t loc);
+
+/* ---- sparse(G, delta): the Gramian of an exponentially decaying isotropic kernel thresholded at its decay radius (src/sparse.jl:5-38) ----
+ * covgram_decay_radius: the distance R beyond which |k| < delta, for ONE isotropic profile (needs no device), src/sparse.jl:25-38:
+ *     EQ  sqrt(-2 ln de)    Exponential  -ln de    GammaExponential(g)  (-2 ln de)^(1/g)    MaternP(p), Matern(nu >= 1/2)  -ln de (conservative)
+ * times the lengthscale, with de = delta / |scale|.  Two deliberate corrections of the reference: (1) src/sparse.jl:38 drops its delta
+ * argument and DIVIDES by l, but Lengthscale(k, l) evaluates k(r / l), so R = l r0; (2) a Constant factor c (the spec's `scale`) is
+ * honoured: c k(r) < delta exactly when k(r) < delta / |c|.  0 < delta / |scale| < 1 is required (COVGRAM_EINVAL), Matern(nu < 1/2) is the
+ * reference's DomainError (COVGRAM_EINVAL, "DomainError: ..."); RQ, Cauchy, IMQ, the dot-product families, a Power wrapper and composites
+ * have no decay radius: COVGRAM_EUNSUPPORTED with a message that names the kernel (the reference's TypeError branch).
+ *
+ * covgram_sparse_create builds S = sparse(gramian(k, X, Y), delta) on the device:
+ *   - pattern: entry (i, j) is kept exactly when s_ij <= R^2, R = the decay radius above (R^2 rounded to the points' precision),
+ *     s_ij = sum_l (x_il - y_jl)^2 formed from the STORED coordinates by direct differences (src/util.jl:40-47), one explicit fused
+ *     multiply-add per dimension in ascending l, in the points' own precision; the comparison is inclusive, as the ball tree's inrange is;
+ *     no centring, no expanded form and no radius gate on this path;
+ *   - value: k(x_i, y_j) of that s_ij, with the library's usual profile evaluation (that of covgram_matrix: scale phi(s / l^2));
+ *   - layout: CSR, 0-based: rowptr n + 1 int64, colind nnz int32 ascending within every row, vals nnz scalars of the points' dtype;
+ *     m >= 2^31 is COVGRAM_EINVAL;
+ *   - n = 0 or m = 0: a valid handle with nnz = 0;
+ *   - deterministic: count, scan, fill — integer counts scanned in a fixed order, every lane walks its row's columns in ascending order — the
+ *     three arrays are bit-identical from run to run;
+ *   - memory: the stream is synchronised once to learn nnz before colind and vals are allocated; if they do not fit: COVGRAM_ENOMEM with a
+ *     message that states nnz.  It is synchronised again before returning: the handle keeps no reference to X or Y, which may be
+ *     destroyed (or, if borrowed, changed) at once;
+ *   - any d >= 1 (rows in registers up to d = 64), fp32 and fp64; X and Y follow the rules of covgram_mvm: one ctx, one dtype, one d;
+ *   - a row's fill count that differs from its count is COVGRAM_EHIP "internal: count/fill mismatch" (both passes run ONE predicate, and
+ *     the fill never writes at or beyond the next row's offset).
+ * covgram_sparse_info: any output pointer may be NULL.  covgram_sparse_export copies the three arrays to caller memory (loc: host or
+ * device; a NULL pointer skips that array).
+ * covgram_sparse_mvm: y <- alpha S a + beta y for nrhs columns, column-major (lda >= m, ldy >= n), loc applies to a and y; beta == 0 never
+ * reads y; 1, 4, 16 or 64 lanes per row (from nnz / n), partial sums folded in a fixed order, no atomics: bit-identical from run to run.
+ * Aliasing: a and y may overlap in any way; a is then read from a private copy.
+ * Option "time_kernels" brackets the fill kernel of covgram_sparse_create and the product kernel. */
+int covgram_decay_radius(const covgram_kernel* k, double delta, double* radius);
+int covgram_sparse_create(covgram_ctx* ctx, covgram_sparse** out, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y,
+                          double delta);
+int covgram_sparse_info(const covgram_sparse* S, int64_t* n, int64_t* m, int64_t* nnz, int32_t* dtype, double* radius);
+int covgram_sparse_export(const covgram_sparse* S, int64_t* rowptr, int32_t* colind, void* vals, int32_t loc);
+int covgram_sparse_mvm(covgram_sparse* S, const void* a, int64_t lda, void* y, int64_t ldy, int32_t nrhs, double alpha, double beta,
+                       int32_t loc);
+int covgram_sparse_destroy(covgram_sparse* S);
 
 /* Toeplitz T[i,j] = vc[i-j] (i >= j), vr[j-i] (i < j); vr == NULL: symmetric (vr = vc, m = n).
  * circulant != 0: T[i,j] = vc[(i-j) mod n] (vr must be NULL).  The spectrum of the circulant embedding
