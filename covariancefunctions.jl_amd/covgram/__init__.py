@@ -21,7 +21,8 @@ from .kernels import (AbstractKernel, MercerKernel, StationaryKernel, IsotropicK
                       device_spec, require_hessian_spec, require_vgh_spec, DomainError)
 from .gramian import (Gramian, BlockGramian, HessianGramian, ValueGradientHessianGramian, SymmetricToeplitz, Toeplitz, Circulant, KroneckerProduct, kronecker,
                       SeparableGramian, LazyMatrixProduct, LazyMatrixSum, ScaledOperator, LinearMapBlockGramian, CosineBlockGramian, PointJacobianBlockGramian, Fill, LazyOperator, LazyGrid, StepRangeLen,
-                      srange, gramian, mul_, get_ctx, set_option, get_info, kernel_time, SparseGramian, sparse, decay_radius)
+                      srange, gramian, mul_, get_ctx, set_option, get_info, kernel_time, SparseGramian, sparse, decay_radius,
+                      BarnesHutFactorization, require_barneshut_spec)
 from .dist import ShardedGramian, shard_bounds
 from .solve import cg, solve, toeplitz_solve, durbin, levinson, trench
 from .factorize import cholesky, factorize, diagonal, CholeskyFactor, PivotedCholesky

@@ -120,6 +120,13 @@ PROTOTYPES = {
     "covgram_sparse_export": (C.c_int, [_P, _P, _P, _P, _I32]),
     "covgram_sparse_mvm": (C.c_int, [_P, _P, _I64, _P, _I64, _I32, _D, _D, _I32]),
     "covgram_sparse_destroy": (C.c_int, [_P]),
+    "covgram_bh_create": (C.c_int, [_P, C.POINTER(_P), _KP, _P, _P, _D, _I32]),
+    "covgram_bh_info": (C.c_int, [_P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I64), C.POINTER(_I32),
+                                  C.POINTER(_D)]),
+    "covgram_bh_export": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I32]),
+    "covgram_bh_moments": (C.c_int, [_P, _P, _P, _P, _I32]),
+    "covgram_bh_mvm": (C.c_int, [_P, _P, _P, _D, _D, _D, _I32, _P, _I64, _I32]),
+    "covgram_bh_destroy": (C.c_int, [_P]),
     "covgram_toeplitz_create": (C.c_int, [_P, C.POINTER(_P), _P, _P, _I64, _I64, _I32, _I32, _I32]),
     "covgram_toeplitz_mvm": (C.c_int, [_P, _P, _P, _D, _D, _I32]),
     "covgram_toeplitz_destroy": (C.c_int, [_P]),

@@ -705,6 +705,152 @@ def sparse(G, delta: float = 1e-6) -> SparseGramian:
     return SparseGramian(G, delta)
 
 
+BARNES_HUT_THETA = 0.25       # src/barneshut.jl:3-4
+BARNES_HUT_LEAFSIZE = 16
+BARNES_HUT_MAX_D = 8          # covgram_bh_create: points in registers (include/covgram.h)
+
+
+def _point_dim(x) -> int:
+    """d of a point set as given by the caller, read without moving anything to a device."""
+    if isinstance(x, StepRangeLen):
+        return 1
+    if isinstance(x, LazyGrid):
+        return x.ndims()
+    shape = tuple(x.shape) if isinstance(x, torch.Tensor) else np.shape(x)
+    return int(shape[1]) if len(shape) >= 2 else 1
+
+
+def require_barneshut_spec(k, d: Optional[int] = None, theta: float = BARNES_HUT_THETA, leafsize: int = BARNES_HUT_LEAFSIZE):
+    """The covgram_kernel that covgram_bh_create runs for k, checked on the host before any device call: ONE isotropic profile under
+    Lengthscale, Constant factors and Power.  Block (derivative) kernels, composites, dot-product kernels and d > 8 raise
+    UnsupportedKernel naming what was refused; theta < 0 or leafsize < 1 raise DimensionMismatch (COVGRAM_EINVAL, a ValueError)."""
+    name = type(k).__name__
+    if isinstance(k, K.MultiKernel):
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"BarnesHutFactorization: {name} is a block (derivative) kernel; only scalar "
+                                                        "isotropic kernels have a Barnes-Hut product")
+    spec = K.require_device_spec(k)
+    if not isinstance(spec, _ffi.covgram_kernel):
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"BarnesHutFactorization: {name} lowers to a composite of profiles; only single "
+                                                        "isotropic profiles under Lengthscale, Constant and Power are supported")
+    if spec.trait != _ffi.ISOTROPIC:
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"BarnesHutFactorization: {name} is a dot-product kernel; the far field of a ball "
+                                                        "tree needs an isotropic profile")
+    if d is not None and d > BARNES_HUT_MAX_D:
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"BarnesHutFactorization: d = {d} exceeds the limit of {BARNES_HUT_MAX_D} dimensions "
+                                                        "(a ball tree compresses nothing beyond)")
+    if not float(theta) >= 0:
+        raise _ffi.DimensionMismatch(_ffi.EINVAL, f"BarnesHutFactorization: theta = {theta} is negative (0 = the exact product)")
+    if int(leafsize) < 1:
+        raise _ffi.DimensionMismatch(_ffi.EINVAL, f"BarnesHutFactorization: leafsize = {leafsize} is smaller than 1")
+    return spec
+
+
+class BarnesHutFactorization(LazyOperator):
+    """BarnesHutFactorization(k, x, y = x, D = nothing; θ = 1/4, leafsize = 16) (src/barneshut.jl:8-39): a ball tree over y, built once on
+    the device (covgram_bh_create), and the tree-based approximate product F w + D w (covgram_bh_mvm).  `BarnesHutFactorization(G)` takes
+    k, x, y from a Gramian.  D is None, a number, or n values (n == m).
+
+    mul_ / @ is the SPLIT product BH(w⁺) − BH(w⁻), the default of the reference's barneshut!; the reference's mul! sends signed weights
+    to taylor!, which is out of scope here.  `solve.cg(F, b)` works on it (the product is not exactly linear in w — the
+    far-field points depend on the weights — so the attainable residual is bounded below by the approximation error: lower θ for more); the reference's `\\` uses minres!, which is not
+    built."""
+
+    def __init__(self, k, x=None, y=None, D=None, theta: float = BARNES_HUT_THETA, leafsize: int = BARNES_HUT_LEAFSIZE):
+        if isinstance(k, Gramian):
+            if type(k) is not Gramian:
+                raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"BarnesHutFactorization: {type(k).__name__} is not a plain scalar Gramian")
+            G = k
+            k, x, y = G.k, G.x, G.y
+        else:
+            G = None
+            if isinstance(k, LazyOperator):
+                raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"BarnesHutFactorization: {type(k).__name__} is not a plain scalar Gramian")
+        spec = require_barneshut_spec(k, _point_dim(x), theta, leafsize)      # every refusal comes before the first device call
+        self._G = G if G is not None else Gramian(k, x, y)
+        G = self._G
+        self.k, self.x, self.y = G.k, G.x, G.y
+        self.shape, self.dtype, self.device = G.shape, G.dtype, G.device
+        self.theta, self.leafsize = float(theta), int(leafsize)
+        n, m = self.shape
+        if D is None:
+            self.D = None
+        else:
+            if n != m:
+                raise _ffi.DimensionMismatch(_ffi.EINVAL, f"DimensionMismatch: a diagonal on a {n} x {m} factorization")
+            Dt = torch.as_tensor(D, dtype=self.dtype).reshape(-1).to(self.device).contiguous()
+            if Dt.shape[0] not in (1, n):
+                raise _ffi.DimensionMismatch(_ffi.EINVAL, f"DimensionMismatch: D has length {Dt.shape[0]}, expected 1 or {n}")
+            self.D = Dt
+        self._ctx = G._px.ctx
+        self.handle = _ffi._P()
+        _ffi.check(_ffi.lib().covgram_bh_create(self._ctx.bind_stream(), C.byref(self.handle), _ffi.kref(spec), G._px.handle, G._py.handle,
+                                                self.theta, self.leafsize))
+        nn = C.c_int64(0)
+        _ffi.check(_ffi.lib().covgram_bh_info(self.handle, None, None, None, None, C.byref(nn), None, None))
+        self.nnodes = int(nn.value)
+
+    def __del__(self):
+        try:
+            if self.handle:
+                _ffi.lib().covgram_bh_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+    def __getitem__(self, ij):
+        return self._G[ij]                                     # src/barneshut.jl:42: F[i, j] = k(x[i], y[j])
+
+    def tree(self):
+        """The export: {"indices": int32 m, "lo" / "hi" / "left" / "right": int32 per node (root = node 0, −1 at a leaf),
+        "centers": nnodes × d, "radii": nnodes} — copies, as device tensors."""
+        m, nn, d = self.shape[1], self.nnodes, self.x.shape[1]
+        i32 = lambda count: torch.empty(count, dtype=torch.int32, device=self.device)
+        out = {"indices": i32(m if nn else 0), "lo": i32(nn), "hi": i32(nn), "left": i32(nn), "right": i32(nn),
+               "centers": torch.empty((nn, d), dtype=self.dtype, device=self.device), "radii": torch.empty(nn, dtype=self.dtype, device=self.device)}
+        self._ctx.bind_stream()
+        _ffi.check(_ffi.lib().covgram_bh_export(self.handle, *[_ffi._P(out[key].data_ptr()) for key in
+                                                               ("indices", "lo", "hi", "left", "right", "centers", "radii")], _ffi.DEVICE))
+        return out
+
+    def moments(self, w):
+        """(sums, com) of the weights w: per node Σ w_j and Σ|w_j| y_j / (Σ|w_j| + eps(T)) (src/barneshut.jl:157-163), as device tensors."""
+        m, nn, d = self.shape[1], self.nnodes, self.x.shape[1]
+        w = _vec_arg(w, m, self.dtype, self.device, "w").contiguous()
+        sums = torch.empty(nn, dtype=self.dtype, device=self.device)
+        com = torch.empty((nn, d), dtype=self.dtype, device=self.device)
+        self._ctx.bind_stream()
+        _ffi.check(_ffi.lib().covgram_bh_moments(self.handle, _ffi._P(w.data_ptr()), _ffi._P(sums.data_ptr()), _ffi._P(com.data_ptr()), _ffi.DEVICE))
+        return sums, com
+
+    def mul_(self, y, a, alpha=1.0, beta=0.0, theta: Optional[float] = None, split: bool = True):
+        """b ← α (F w) + β b + α D w.  theta=None: the handle's θ; θ = 0 is the exact product.  split=False: the single pass of
+        barneshut!(…; split = false)."""
+        n, m = self.shape
+        a = _vec_arg(a, m, self.dtype, self.device, "a")
+        if y.shape[0] != n or y.dtype != self.dtype or tuple(y.shape[1:]) != tuple(a.shape[1:]):
+            raise _ffi.DimensionMismatch(_ffi.EINVAL, f"DimensionMismatch: y has shape {tuple(y.shape)}, expected ({n}, ...) of {self.dtype}")
+        if theta is not None and not float(theta) >= 0:
+            raise _ffi.DimensionMismatch(_ffi.EINVAL, f"BarnesHutFactorization: theta = {theta} is negative (0 = the exact product)")
+        if a.dim() == 2:
+            return _by_columns(self, y, a, alpha, beta, theta=theta, split=split)
+        a_c = a.contiguous()
+        y_c = y if y.is_contiguous() else y.contiguous()
+        self._ctx.bind_stream()
+        dptr, dlen = (None, 0) if self.D is None else (_ffi._P(self.D.data_ptr()), self.D.shape[0])
+        _ffi.check(_ffi.lib().covgram_bh_mvm(self.handle, _ffi._P(a_c.data_ptr()), _ffi._P(y_c.data_ptr()), float(alpha), float(beta),
+                                             -1.0 if theta is None else float(theta), 1 if split else 0, dptr, dlen, _ffi.DEVICE))
+        if y_c is not y:
+            y.copy_(y_c)
+        return y
+
+    def to_dense(self):
+        """The matrix the factorization approximates, Matrix(G) + D."""
+        out = self._G.to_dense().clone()
+        if self.D is not None:
+            out.diagonal().add_(self.D if self.D.shape[0] > 1 else self.D[0])
+        return out
+
+
 class KroneckerProduct(LazyOperator):
     """kronecker(F_1, ..., F_q) (KroneckerProducts 1.1.1): standard order, F_1 = slowest index.  Factors are
     lazy Gramians or dense matrices; lazy factors are instantiated once on the device (they are the small
@@ -834,11 +980,11 @@ class LazyMatrixProduct(LazyOperator):
         return self.U @ self.V.t()
 
 
-def _by_columns(op, y, a, alpha, beta):
-    """Matrix right-hand side for operators whose mul_ is written for vectors: one column at a time."""
+def _by_columns(op, y, a, alpha, beta, **kw):
+    """Matrix right-hand side for operators whose mul_ is written for vectors: one column at a time (kw: further keywords of op.mul_)."""
     for c in range(a.shape[1]):
         yc = y[:, c].contiguous()
-        op.mul_(yc, a[:, c].contiguous(), alpha, beta)
+        op.mul_(yc, a[:, c].contiguous(), alpha, beta, **kw)
         y[:, c] = yc
     return y
 

@@ -240,7 +240,7 @@ struct covgram_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
-    covgram::Workspace ws[6];  // 0: packed tile stream, 1: split-J partials, 2/3: host staging (device copies of a / y), 4: wide-gradient slices, 5: private copy of an a that overlaps y
+    covgram::Workspace ws[6];  // 0: packed tile stream, 1: split-J partials, 2/3: host staging (device copies of a / y), 4: wide-gradient slices; host staging of a Barnes-Hut diagonal, 5: private copy of an a that overlaps y
     // options
     int64_t dense_variant = 0;   // 0 auto (fp32 EQ on the matrix cores when the norm bound allows; Dot() as X (Y' a)), 1 direct differences / entry by entry, 2 MFMA whenever the shape allows
     int64_t rows_per_lane = 0;   // 0 = auto

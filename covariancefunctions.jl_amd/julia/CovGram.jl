@@ -628,4 +628,78 @@ function SparseArrays.sparse(G::Gramian{T}, δ::Real = 1e-6; leafsize::Int = 16)
     SparseArrays.SparseMatrixCSC{T, Int64}(n, m, rowptr .+ 1, Int64.(colind) .+ 1, vals)
 end
 
+# --- src/barneshut.jl:8-143: BarnesHutFactorization -> covgram_bh_* (ball tree over y built on the device, tree-based approximate product) ---
+# Deviation from the reference (DESIGN.md, "Barnes-Hut"): its mul! sends signed weights to taylor!, which the library does not have; here
+# mul! and * are the SPLIT Barnes-Hut product BH(w+) - BH(w-), the default of the reference's own barneshut!.  ldiv! / `\` (minres!) is not
+# provided: IterativeSolvers.cg!(x, F, b) runs on mul!.
+mutable struct DeviceBarnesHut{T} <: AbstractMatrix{T}
+    handle::Ptr{Cvoid}
+    k::Any; x::Any; y::Any
+    D::Union{Nothing, Vector{T}}
+    n::Int; m::Int; d::Int; nnodes::Int; leafsize::Int; θ::Float64
+    function DeviceBarnesHut(k, x, y, D, ::Type{T}, θ::Real, leafsize::Integer, spec) where {T <: DevFloat}
+        X = points(x, T); Y = x === y ? X : points(y, T)
+        h = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ccall((:covgram_bh_create, libcovgram), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Int32),
+                    ctx(), h, kref(spec), X.handle, Y.handle, Float64(θ), Int32(leafsize)))
+        n = Ref{Int64}(0); m = Ref{Int64}(0); d = Ref{Int32}(0); dt = Ref{Int32}(0); nn = Ref{Int64}(0); ls = Ref{Int32}(0); th = Ref{Float64}(0.0)
+        check(ccall((:covgram_bh_info, libcovgram), Cint,
+                    (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int32}, Ref{Int32}, Ref{Int64}, Ref{Int32}, Ref{Float64}), h[], n, m, d, dt, nn, ls, th))
+        Dv = D === nothing ? nothing : (D isa Number ? T[D] : Vector{T}(diag(D)))
+        F = new{T}(h[], k, x, y, Dv, n[], m[], d[], nn[], ls[], th[])
+        finalizer(q -> ccall((:covgram_bh_destroy, libcovgram), Cint, (Ptr{Cvoid},), q.handle), F)
+        F
+    end
+end
+Base.size(F::DeviceBarnesHut) = (F.n, F.m)
+Base.getindex(F::DeviceBarnesHut, i::Integer, j::Integer) = F.k(F.x[i], F.y[j])                 # src/barneshut.jl:42
+# the export: indices (0-based permutation of the columns), per node lo, hi, left, right (-1 at a leaf, root = node 0), centres d × nnodes, radii
+function tree(F::DeviceBarnesHut{T}) where {T}
+    indices = Vector{Int32}(undef, F.nnodes > 0 ? F.m : 0)
+    lo = Vector{Int32}(undef, F.nnodes); hi = similar(lo); left = similar(lo); right = similar(lo)
+    centers = Matrix{T}(undef, F.d, F.nnodes); radii = Vector{T}(undef, F.nnodes)
+    check(ccall((:covgram_bh_export, libcovgram), Cint,
+                (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Cvoid}, Ptr{Cvoid}, Int32),
+                F.handle, indices, lo, hi, left, right, centers, radii, HOST))
+    (; indices, lo, hi, left, right, centers, radii)
+end
+# node_sums / compute_centers_of_mass of src/barneshut.jl:145-190 in one call: (sums, centers_of_mass d × nnodes)
+function moments(F::DeviceBarnesHut{T}, w::StridedVector{T}) where {T}
+    length(w) == F.m || throw(DimensionMismatch("length of w does not match second dimension of F: $(length(w)) ≠ $(F.m)"))
+    sums = Vector{T}(undef, F.nnodes); com = Matrix{T}(undef, F.d, F.nnodes)
+    check(ccall((:covgram_bh_moments, libcovgram), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32), F.handle, w, sums, com, HOST))
+    sums, com
+end
+function barneshut!(b::StridedVector{T}, F::DeviceBarnesHut{T}, w::StridedVector{T}, α::Real = 1, β::Real = 0, θ::Real = F.θ;
+                    split::Bool = true) where {T <: DevFloat}
+    length(w) == F.m || throw(DimensionMismatch("length of w does not match second dimension of F: $(length(w)) ≠ $(F.m)"))
+    length(b) == F.n || throw(DimensionMismatch("length of b does not match first dimension of F: $(length(b)) ≠ $(F.n)"))
+    stride(b, 1) == 1 && stride(w, 1) == 1 || throw(ArgumentError("barneshut!: contiguous vectors expected"))
+    Dp = F.D === nothing ? Ptr{Cvoid}(C_NULL) : Ptr{Cvoid}(pointer(F.D))
+    GC.@preserve F check(ccall((:covgram_bh_mvm, libcovgram), Cint,
+                               (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Int32, Ptr{Cvoid}, Int64, Int32),
+                               F.handle, w, b, Float64(α), Float64(β), Float64(θ), Int32(split), Dp, Int64(F.D === nothing ? 0 : length(F.D)), HOST))
+    b
+end
+LinearAlgebra.mul!(b::StridedVector{T}, F::DeviceBarnesHut{T}, w::StridedVector{T}, α::Real = 1, β::Real = 0) where {T <: DevFloat} =
+    barneshut!(b, F, w, α, β)
+function LinearAlgebra.mul!(B::StridedMatrix{T}, F::DeviceBarnesHut{T}, W::StridedMatrix{T}, α::Real = 1, β::Real = 0) where {T <: DevFloat}
+    size(B, 2) == size(W, 2) || throw(DimensionMismatch("mul!: size mismatch"))
+    for c in 1:size(W, 2)
+        barneshut!(view(B, :, c), F, view(W, :, c), α, β)
+    end
+    B
+end
+Base.:*(F::DeviceBarnesHut{T}, w::StridedVector{T}) where {T <: DevFloat} = mul!(zeros(T, F.n), F, w)
+# CovGram.BarnesHutFactorization: the signatures of the reference's constructors (src/barneshut.jl:25-39) as a function of THIS module (the
+# reference's own type and constructors stay as they are).  A kernel without a device spec gets the reference's factorization; a kernel
+# that has one but is refused (composites, dot-product kernels, d > 8) is refused by the library, by name, through check(...)
+function BarnesHutFactorization(k, x, y = x, D = nothing; θ::Real = 1 / 4, leafsize::Int = 16)
+    spec = ENABLED[] ? device_kernel_for(k) : nothing
+    T = CovarianceFunctions.gramian_eltype(k, x[1], y[1])
+    (spec === nothing || !(T <: DevFloat)) && return CovarianceFunctions.BarnesHutFactorization(k, x, y, D; θ = θ, leafsize = leafsize)
+    DeviceBarnesHut(k, x, y, D, T, θ, leafsize, spec)
+end
+BarnesHutFactorization(G::Gramian; θ::Real = 1 / 4, leafsize::Int = 16) = BarnesHutFactorization(G.k, G.x, G.y; θ = θ, leafsize = leafsize)
+
 end # module

@@ -19,6 +19,9 @@
  *   covgram_block_matrix   replaces  Base.Matrix(G) of those four block Gramians (gramian(k, x, y, Val(false)))   src/gramian.jl:125-130, 192-199
  *   covgram_sparse_create  replaces  SparseArrays.sparse(G::Gramian, delta) and decay_radius(k, delta)         src/sparse.jl:5-38
  *   covgram_sparse_mvm     replaces  mul!(y, ::SparseMatrixCSC, a, alpha, beta) on its result
+ *   covgram_bh_create      replaces  BarnesHutFactorization(k, x, y, D; theta, leafsize)                 src/barneshut.jl:25-39
+ *   covgram_bh_mvm         replaces  barneshut!(b, F, w, alpha, beta, theta; split) and mul!(b, F, w, alpha, beta)   src/barneshut.jl:45-143
+ *   covgram_bh_moments     replaces  node_sums / compute_centers_of_mass                                 src/barneshut.jl:145-190
  *   covgram_toeplitz_*     replaces  mul!(y, ::SymmetricToeplitz/Toeplitz/Circulant, a, α, β) of ToeplitzMatrices 0.7.1 as
  *                          constructed by gramian(k, x::StepRangeLen, y::StepRangeLen)            src/gramian.jl:167-189
  *   covgram_toeplitz_durbin / _levinson / _trench  replace durbin! / levinson! / trench!             src/toeplitz.jl:12-111
@@ -58,7 +61,8 @@ extern "C" {
                                covgram_valgradhess_mvm and the info key "last_vgh_path";
                                the info key "last_matrix_path";
                                covgram_block_matrix, the COVGRAM_BLOCK_* kinds and the info key "last_block_matrix_path";
-                               covgram_decay_radius and the covgram_sparse_* handle (sparse(G, delta)).
+                               covgram_decay_radius and the covgram_sparse_* handle (sparse(G, delta));
+                               the covgram_bh_* handle (BarnesHutFactorization).
                                A binding checks covgram_version() against the header it mirrors at load time */
 
 typedef enum covgram_status {
@@ -130,6 +134,7 @@ typedef struct covgram_ctx covgram_ctx;           /* one device + one stream + w
 typedef struct covgram_points covgram_points;     /* device-resident point set (stays resident across MVMs) */
 typedef struct covgram_toeplitz covgram_toeplitz; /* cached circulant spectrum + plans */
 typedef struct covgram_sparse covgram_sparse;     /* radius-thresholded CSR Gramian: owns its three arrays */
+typedef struct covgram_bh covgram_bh;             /* Barnes-Hut factorization: ball tree over the columns, tree-ordered copies of both point sets */
 
 int covgram_version(void);
 /* sizeof() of the two structs that cross the ABI by pointer, as THIS build of the library sees them: a binding asserts its
@@ -387,6 +392,48 @@ int covgram_sparse_export(const covgram_sparse* S, int64_t* rowptr, int32_t* col
 int covgram_sparse_mvm(covgram_sparse* S, const void* a, int64_t lda, void* y, int64_t ldy, int32_t nrhs, double alpha, double beta,
                        int32_t loc);
 int covgram_sparse_destroy(covgram_sparse* S);
+
+/* ---- BarnesHutFactorization: the tree-based approximate product of a scalar isotropic Gramian (src/barneshut.jl:25-190) ----
+ * covgram_bh_create builds, once per (k, X, Y), a binary ball tree over the COLUMN points Y on the device:
+ *   - a node owns the range [lo, hi) of a permutation `indices` of 0 .. m-1; a range of more than `leafsize` points (reference default 16)
+ *     is sorted along its dimension of widest extent and split BY POSITION at lo + ceil((hi - lo) / 2), so duplicated points split like
+ *     any others and the depth is at most ceil(log2(m / leafsize)) + 1; the shape of the tree therefore depends on (m, leafsize) only;
+ *   - nodes are numbered in pre-order: the root is node 0 and the left child of v is v + 1; a leaf has left = right = -1;
+ *   - every node has a centre (the midpoint of its bounding box) and a radius such that each of its points lies within the radius of
+ *     the centre (distances in fp64, rounded up to the points' precision);
+ *   - deterministic: exact minima / maxima and a radix sort whose result depends on its input alone — bit-identical from run to run;
+ *   - the handle keeps tree-ordered COPIES of both point sets (the targets X are ordered along the tree when X and Y are the same
+ *     device points, otherwise along a tree of their own): X and Y may be destroyed, or changed, when create returns;
+ *   - kernels: ONE isotropic profile (EQ, Exponential, RQ, GammaExponential, Cauchy, IMQ, MaternP, Matern) under lengthscale, scale and
+ *     power.  Dot-product families and composites are COVGRAM_EUNSUPPORTED by name, before any launch; 1 <= d <= 8 (points in registers),
+ *     larger d is COVGRAM_EUNSUPPORTED naming the limit; theta < 0 or leafsize < 1 is COVGRAM_EINVAL; fp32 and fp64;
+ *   - n = 0 or m = 0 give a valid handle (m = 0: no nodes).
+ * covgram_bh_info: any output pointer may be NULL.  covgram_bh_export copies indices[m], per node lo, hi, left, right (int32), the
+ * centres (nnodes x d, node-major) and the radii (nnodes) in the points' dtype to caller memory (host or device; NULL skips an array).
+ * covgram_bh_moments: the first stage of a product for the weights w (m scalars): sums[v] = sum of w_j over node v and
+ * com[v] = sum |w_j| y_j / (sum |w_j| + eps(T)) (nnodes x d), src/barneshut.jl:157-163 — accumulated in fp64 for both dtypes, leaves
+ * first, then every parent from its two children (no floating-point atomics), rounded to T once.  A node whose weights are all zero
+ * has com = 0 and sums = 0.
+ * covgram_bh_mvm: y <- alpha (F a) + beta y [+ alpha D a], one right-hand side; beta == 0 never reads y; a and y may be the same memory.
+ *   For every target x_i the tree is walked from the root: a leaf adds sum_j k(x_i, y_j) a_j by direct differences; an internal node
+ *   with radius < theta |x_i - com[v]| adds k(x_i, com[v]) sums[v]; otherwise both children are visited (src/barneshut.jl:123-143).  The
+ *   criterion is evaluated per target; the terms a target receives are exactly the recursion's, added in pre-order.
+ *   theta < 0: the handle's; theta = 0: the exact product.  split != 0: BH(a+) - BH(a-) with a+ = max(a, 0), a- = max(-a, 0)
+ *   (src/barneshut.jl:101-112): both signs carry their own moments and share one walk; an empty sign adds exact zeros, so the weights are
+ *   never inspected on the host.  split == 0: the single pass on a as it is.  (The reference's mul! sends signed weights to taylor!,
+ *   which this library does not have: bindings map mul! to split = 1, the default of the reference's own barneshut!.)
+ *   diag: NULL, or diag_len = 1 or n scalars of the points' dtype (n == m): the diagonal D of src/barneshut.jl:92-94.
+ *   With loc == DEVICE the product is stream-ordered, allocates nothing and never synchronises: a captured graph may contain it.
+ *   m = 0: y <- beta y.  n = 0: returns at once.  Option "time_kernels" brackets the walk kernel. */
+int covgram_bh_create(covgram_ctx* ctx, covgram_bh** out, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, double theta,
+                      int32_t leafsize);
+int covgram_bh_info(const covgram_bh* F, int64_t* n, int64_t* m, int32_t* d, int32_t* dtype, int64_t* nnodes, int32_t* leafsize, double* theta);
+int covgram_bh_export(const covgram_bh* F, int32_t* indices, int32_t* lo, int32_t* hi, int32_t* left, int32_t* right, void* centers, void* radii,
+                      int32_t loc);
+int covgram_bh_moments(covgram_bh* F, const void* w, void* sums, void* com, int32_t loc);
+int covgram_bh_mvm(covgram_bh* F, const void* a, void* y, double alpha, double beta, double theta, int32_t split, const void* diag, int64_t diag_len,
+                   int32_t loc);
+int covgram_bh_destroy(covgram_bh* F);
 
 /* Toeplitz T[i,j] = vc[i-j] (i >= j), vr[j-i] (i < j); vr == NULL: symmetric (vr = vc, m = n).
  * circulant != 0: T[i,j] = vc[(i-j) mod n] (vr must be NULL).  The spectrum of the circulant embedding
