@@ -126,6 +126,8 @@ PROTOTYPES = {
     "covgram_bh_export": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I32]),
     "covgram_bh_moments": (C.c_int, [_P, _P, _P, _P, _I32]),
     "covgram_bh_mvm": (C.c_int, [_P, _P, _P, _D, _D, _D, _I32, _P, _I64, _I32]),
+    "covgram_bh_taylor_moments": (C.c_int, [_P, _P, _I32, _P, _P, _P, _I32]),
+    "covgram_bh_taylor_mvm": (C.c_int, [_P, _P, _P, _D, _D, _D, _I32, _P, _I64, _I32]),
     "covgram_bh_destroy": (C.c_int, [_P]),
     "covgram_toeplitz_create": (C.c_int, [_P, C.POINTER(_P), _P, _P, _I64, _I64, _I32, _I32, _I32]),
     "covgram_toeplitz_mvm": (C.c_int, [_P, _P, _P, _D, _D, _I32]),

@@ -750,12 +750,23 @@ class BarnesHutFactorization(LazyOperator):
     the device (covgram_bh_create), and the tree-based approximate product F w + D w (covgram_bh_mvm).  `BarnesHutFactorization(G)` takes
     k, x, y from a Gramian.  D is None, a number, or n values (n == m).
 
-    mul_ / @ is the SPLIT product BH(w⁺) − BH(w⁻), the default of the reference's barneshut!; the reference's mul! sends signed weights
-    to taylor!, which is out of scope here.  `solve.cg(F, b)` works on it (the product is not exactly linear in w — the
-    far-field points depend on the weights — so the attainable residual is bounded below by the approximation error: lower θ for more); the reference's `\\` uses minres!, which is not
-    built."""
+    Two products:
+      - product="split" (the default): mul_ / @ is the SPLIT product BH(w⁺) − BH(w⁻), the default of the reference's barneshut!.  It is not
+        exactly linear in w (the far-field points depend on the weights), which costs a Krylov recurrence iterations;
+      - product="taylor": mul_ / @ is taylor_ (src/taylor.jl:7-57, covgram_bh_taylor_mvm), the first-order expansion of the far field in
+        ONE pass for weights of any sign — the product the reference's mul! runs for signed weights.  mul_'s `split` is then not
+        consulted.  use_com=True expands about the |w|-weighted centres of mass; for w ≥ 0 the first moment is then rounding-level and
+        the product is the reference's unsplit single pass, so the reference's mul! is reproduced without inspecting the weights on the
+        host.  use_com=False expands about the ball centres, which do not depend on w: the product is an exactly linear map, the
+        variant a Krylov solver wants.  The operator is not exactly symmetric either way (targets and sources are treated differently).
+    taylor_ / taylor / taylor_moments are available whatever `product` is.  `solve.cg(F, b)` and `solve.minres(F, b)` run on mul_;
+    `F.solve(b)` is the reference's `\\` (minres!, src/barneshut.jl:64-72).  The expansion stops at first order, like the reference's."""
 
-    def __init__(self, k, x=None, y=None, D=None, theta: float = BARNES_HUT_THETA, leafsize: int = BARNES_HUT_LEAFSIZE):
+    def __init__(self, k, x=None, y=None, D=None, theta: float = BARNES_HUT_THETA, leafsize: int = BARNES_HUT_LEAFSIZE,
+                 product: str = "split", use_com: bool = True):
+        if product not in ("split", "taylor"):
+            raise ValueError(f"BarnesHutFactorization: product = {product!r} (\"split\" or \"taylor\")")
+        self.product, self.use_com = product, bool(use_com)
         if isinstance(k, Gramian):
             if type(k) is not Gramian:
                 raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"BarnesHutFactorization: {type(k).__name__} is not a plain scalar Gramian")
@@ -822,9 +833,20 @@ class BarnesHutFactorization(LazyOperator):
         _ffi.check(_ffi.lib().covgram_bh_moments(self.handle, _ffi._P(w.data_ptr()), _ffi._P(sums.data_ptr()), _ffi._P(com.data_ptr()), _ffi.DEVICE))
         return sums, com
 
-    def mul_(self, y, a, alpha=1.0, beta=0.0, theta: Optional[float] = None, split: bool = True):
-        """b ← α (F w) + β b + α D w.  theta=None: the handle's θ; θ = 0 is the exact product.  split=False: the single pass of
-        barneshut!(…; split = false)."""
+    def taylor_moments(self, w, use_com: bool = True):
+        """(sums, centers, m1) of taylor! for the weights w, as device tensors: per node Σ w_j, the expansion centre (use_com: the
+        |w|-weighted centre of mass; otherwise the ball centre) and the centred signed first moment Σ w_j y_j − sums · centre."""
+        m, nn, d = self.shape[1], self.nnodes, self.x.shape[1]
+        w = _vec_arg(w, m, self.dtype, self.device, "w").contiguous()
+        sums = torch.empty(nn, dtype=self.dtype, device=self.device)
+        cen = torch.empty((nn, d), dtype=self.dtype, device=self.device)
+        m1 = torch.empty((nn, d), dtype=self.dtype, device=self.device)
+        self._ctx.bind_stream()
+        _ffi.check(_ffi.lib().covgram_bh_taylor_moments(self.handle, _ffi._P(w.data_ptr()), 1 if use_com else 0, _ffi._P(sums.data_ptr()),
+                                                        _ffi._P(cen.data_ptr()), _ffi._P(m1.data_ptr()), _ffi.DEVICE))
+        return sums, cen, m1
+
+    def _mvm(self, taylor, y, a, alpha, beta, theta, flag):
         n, m = self.shape
         a = _vec_arg(a, m, self.dtype, self.device, "a")
         if y.shape[0] != n or y.dtype != self.dtype or tuple(y.shape[1:]) != tuple(a.shape[1:]):
@@ -832,16 +854,43 @@ class BarnesHutFactorization(LazyOperator):
         if theta is not None and not float(theta) >= 0:
             raise _ffi.DimensionMismatch(_ffi.EINVAL, f"BarnesHutFactorization: theta = {theta} is negative (0 = the exact product)")
         if a.dim() == 2:
-            return _by_columns(self, y, a, alpha, beta, theta=theta, split=split)
+            return _by_columns(self, y, a, alpha, beta, method="_mvm_column", taylor=taylor, theta=theta, flag=flag)
         a_c = a.contiguous()
         y_c = y if y.is_contiguous() else y.contiguous()
         self._ctx.bind_stream()
         dptr, dlen = (None, 0) if self.D is None else (_ffi._P(self.D.data_ptr()), self.D.shape[0])
-        _ffi.check(_ffi.lib().covgram_bh_mvm(self.handle, _ffi._P(a_c.data_ptr()), _ffi._P(y_c.data_ptr()), float(alpha), float(beta),
-                                             -1.0 if theta is None else float(theta), 1 if split else 0, dptr, dlen, _ffi.DEVICE))
+        fn = _ffi.lib().covgram_bh_taylor_mvm if taylor else _ffi.lib().covgram_bh_mvm
+        _ffi.check(fn(self.handle, _ffi._P(a_c.data_ptr()), _ffi._P(y_c.data_ptr()), float(alpha), float(beta),
+                      -1.0 if theta is None else float(theta), 1 if flag else 0, dptr, dlen, _ffi.DEVICE))
         if y_c is not y:
             y.copy_(y_c)
         return y
+
+    def _mvm_column(self, y, a, alpha, beta, taylor, theta, flag):
+        return self._mvm(taylor, y, a, alpha, beta, theta, flag)
+
+    def taylor_(self, y, w, alpha=1.0, beta=0.0, theta: Optional[float] = None, use_com: bool = True):
+        """b ← α (T w) + β b + α D w with T the first-order Taylor product taylor!(b, F, w, α, β, θ; use_com) (src/taylor.jl:7-57).
+        theta=None: the handle's θ; θ = 0 is the exact product.  A matrix right-hand side goes column by column."""
+        return self._mvm(True, y, w, alpha, beta, theta, use_com)
+
+    def taylor(self, w, **kw):
+        """T w + D w as a new tensor (kw: theta, use_com)."""
+        w = _vec_arg(w, self.shape[1], self.dtype, self.device, "w")
+        y = torch.empty((self.shape[0],) + tuple(w.shape[1:]), dtype=self.dtype, device=self.device)
+        return self.taylor_(y, w, 1.0, 0.0, **kw)
+
+    def solve(self, b, **kw):
+        """F \\ b (src/barneshut.jl:64-72): MINRES on mul_ (kw: the keywords of solve.minres)."""
+        from .solve import minres
+        return minres(self, b, **kw)[0]
+
+    def mul_(self, y, a, alpha=1.0, beta=0.0, theta: Optional[float] = None, split: bool = True):
+        """b ← α (F w) + β b + α D w.  theta=None: the handle's θ; θ = 0 is the exact product.  split=False: the single pass of
+        barneshut!(…; split = false).  With product="taylor" this is taylor_ with the constructor's use_com, and `split` is not consulted."""
+        if self.product == "taylor":
+            return self._mvm(True, y, a, alpha, beta, theta, self.use_com)
+        return self._mvm(False, y, a, alpha, beta, theta, split)
 
     def to_dense(self):
         """The matrix the factorization approximates, Matrix(G) + D."""
@@ -980,11 +1029,13 @@ class LazyMatrixProduct(LazyOperator):
         return self.U @ self.V.t()
 
 
-def _by_columns(op, y, a, alpha, beta, **kw):
-    """Matrix right-hand side for operators whose mul_ is written for vectors: one column at a time (kw: further keywords of op.mul_)."""
+def _by_columns(op, y, a, alpha, beta, method="mul_", **kw):
+    """Matrix right-hand side for operators whose mul_ is written for vectors: one column at a time (kw: further keywords of op.mul_;
+    method: another product of op with mul_'s leading arguments)."""
+    product = getattr(op, method)
     for c in range(a.shape[1]):
         yc = y[:, c].contiguous()
-        op.mul_(yc, a[:, c].contiguous(), alpha, beta, **kw)
+        product(yc, a[:, c].contiguous(), alpha, beta, **kw)
         y[:, c] = yc
     return y
 

@@ -179,6 +179,66 @@ def _cg_graph(A, b, x0, reltol, abstol, maxiter, precond, check_every):
     return x, {"iterations": it, "residual_norm": resf, "converged": resf <= tol, "graph": True}
 
 
+def minres(A: LazyOperator, b: torch.Tensor, x0: Optional[torch.Tensor] = None, reltol: Optional[float] = None, abstol: float = 0.0,
+           maxiter: Optional[int] = None, check_every: int = 1) -> Tuple[torch.Tensor, dict]:
+    """Solve A x = b for a square SYMMETRIC lazy operator A, definite or not (minres!, IterativeSolvers 0.9.2; the reference's
+    `F \\ b` for a BarnesHutFactorization, src/barneshut.jl:64-72): the Paige-Saunders recurrence — Lanczos vectors, one Givens
+    rotation per iteration, the iterate updated from three direction vectors.  Stops when the recurrence's residual norm is
+    ≤ max(reltol·‖r₀‖, abstol); reltol defaults to sqrt(eps(dtype)).  Returns (x, {"iterations", "residual_norm", "converged"}).
+    Every scalar of the recurrence is a 0-dim device tensor; the only host synchronisation is the convergence read every
+    `check_every` iterations (the solve may then run up to check_every − 1 iterations past the tolerance)."""
+    n = A.shape[0]
+    if A.shape[0] != A.shape[1] or b.shape[0] != n:
+        raise ValueError("minres: A must be square and match b")
+    if b.dim() != 1:
+        raise ValueError(f"minres: b must be a vector, got shape {tuple(b.shape)} (solve a matrix right-hand side column by column)")
+    b = b.to(device=A.device, dtype=A.dtype)
+    if reltol is None:
+        reltol = float(torch.finfo(A.dtype).eps) ** 0.5
+    x = torch.zeros_like(b) if x0 is None else x0.to(device=A.device, dtype=A.dtype).clone()
+    r2 = b.clone()
+    y = torch.empty_like(b)
+    if x0 is not None:
+        A.mul_(y, x)
+        r2 -= y
+    beta = torch.linalg.vector_norm(r2)
+    r0 = float(beta)
+    tol = max(reltol * r0, abstol)
+    maxiter = n if maxiter is None else maxiter
+    check_every = max(1, int(check_every))
+    it, res = 0, r0
+    if not (r0 > tol):
+        return x, {"iterations": 0, "residual_norm": r0, "converged": r0 <= tol}
+    zero, one = torch.zeros_like(beta), torch.ones_like(beta)
+    tiny = torch.full_like(beta, float(torch.finfo(A.dtype).tiny))
+    r1 = torch.zeros_like(b)                # (the first iteration subtracts (beta / oldb) r1 = 0)
+    v = torch.empty_like(b)
+    w, w1, w2 = torch.zeros_like(b), torch.zeros_like(b), torch.zeros_like(b)
+    oldb, dbar, epsln, phibar, cs, sn = one, zero, zero, beta, -one, zero
+    while it < maxiter and res > tol:
+        torch.mul(r2, torch.where(beta > 0, 1 / beta, zero), out=v)      # the Lanczos vector (beta = 0: the Krylov space is exhausted)
+        A.mul_(y, v)                        # the hot path
+        y.addcmul_(r1, -(beta / oldb))
+        alfa = torch.dot(v, y)
+        y.addcmul_(r2, -(alfa / torch.maximum(beta, tiny)))
+        r1, r2, y = r2, y, r1               # (y is overwritten by the next product)
+        oldb, beta = beta, torch.linalg.vector_norm(r2)
+        oldeps = epsln                      # the previous rotation on the new column of the tridiagonal matrix
+        delta = cs * dbar + sn * alfa
+        gbar = sn * dbar - cs * alfa
+        epsln, dbar = sn * beta, -cs * beta
+        gamma = torch.maximum(torch.hypot(gbar, beta), tiny)             # the new rotation
+        cs, sn = gbar / gamma, beta / gamma
+        phi, phibar = cs * phibar, sn * phibar
+        w1, w2, w = w2, w, w1               # w <- (v - oldeps w1 - delta w2) / gamma
+        w.copy_(v).addcmul_(w1, -oldeps).addcmul_(w2, -delta).div_(gamma)
+        x.addcmul_(w, phi)
+        it += 1
+        if it % check_every == 0 or it == maxiter:
+            res = float(phibar)             # |r| of the recurrence: the convergence test's synchronisation
+    return x, {"iterations": it, "residual_norm": res, "converged": res <= tol}
+
+
 def solve(A: LazyOperator, b: torch.Tensor, **kw) -> torch.Tensor:
     """`A \\ b` for lazy Gramians (src/gramian.jl:229-238)."""
     return cg(A, b, **kw)[0]

@@ -18,6 +18,12 @@
 // the same addresses in all 64 lanes.  The criterion h.r < theta |x_i - com[v]| is per lane: the terms a
 // target receives are exactly those of the reference's recursion, in pre-order.  With split on, the positive and the negative part of
 // w carry their own moments and their own masks and share one walk (a leaf's pair is evaluated once for both).
+//
+// TAYLOR PRODUCT (src/taylor.jl:7-57; covgram_bh_taylor_*).  One pass for weights of any sign: a compressed node adds the first-order
+// expansion f0(s) sum w_j - 2 f1(s) (x_i - c) . m1 about a centre c, s = |x_i - c|^2, with m1 = sum w_j (y_j - c) the centred signed first
+// moment.  c is the |w|-weighted centre of mass (use_com) or the ball centre, which does not depend on w: the product is then an exactly
+// linear map of w.  The moments ride in ONE channel of 2 + 2 DM doubles per node, { sum w, sum |w|, sum |w| y, sum w y }, through the same
+// leaf-then-parents schedule; the walk is the single-channel walk with the jet (f0, f1) in place of the value at internal nodes.
 #include <math.h>
 #include <string.h>
 
@@ -369,6 +375,122 @@ __global__ __launch_bounds__(64) void bh_walk_kernel(const BhWalk<T> g, const KP
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// taylor! (src/taylor.jl:7-57): moments and walk
+// ------------------------------------------------------------------------------------------------
+// one thread per leaf: mom[v (2 + 2 DM)] = { sum w, sum |w|, sum |w| y_0 .., sum w y_0 .. }, fp64, and ws[j] = w[indices[j]].  The record
+// is 2 + DM' doubles wide with DM' = 2 DM, so the parents are summed by bh_up_level_kernel<2 DM, 1> / bh_up_top_kernel<2 DM, 1> as they are.
+template <typename T, int DM>
+__global__ __launch_bounds__(256) void bh_taylor_leaf_moments_kernel(const int32_t* __restrict__ leaves, int64_t nleaves, const int32_t* __restrict__ nlo,
+                                                                     const int32_t* __restrict__ nhi, const int32_t* __restrict__ idx,
+                                                                     const T* __restrict__ Ys, const T* __restrict__ w, T* __restrict__ ws,
+                                                                     double* __restrict__ mom) {
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= nleaves) return;
+    const int v = leaves[q];
+    const int lo = nlo[v], hi = nhi[v];
+    double S = 0, A = 0, M[DM], R[DM];
+#pragma unroll
+    for (int l = 0; l < DM; ++l) { M[l] = 0; R[l] = 0; }
+    for (int j = lo; j < hi; ++j) {
+        const T wj = w[idx[j]];
+        ws[j] = wj;
+        const double wc = (double)wj, aw = fabs(wc);
+        S += wc; A += aw;
+#pragma unroll
+        for (int l = 0; l < DM; ++l) {
+            const double y = (double)Ys[(int64_t)j * DM + l];
+            M[l] = fma(aw, y, M[l]);
+            R[l] = fma(wc, y, R[l]);
+        }
+    }
+    double* o = mom + (int64_t)v * (2 + 2 * DM);
+    o[0] = S; o[1] = A;
+#pragma unroll
+    for (int l = 0; l < DM; ++l) { o[2 + l] = M[l]; o[2 + DM + l] = R[l]; }
+}
+
+// rounded to T once: sums[v], cm[(2 v) DM + l] = the centre c (use_com: M_l / (A + eps(T)), src/barneshut.jl:157-163; otherwise the ball
+// centre, padded with zeros) and cm[(2 v + 1) DM + l] = m1 = R_l - S c_l (src/taylor.jl:15-18), centred in fp64 about c AS ROUNDED TO T
+template <typename T, int DM>
+__global__ __launch_bounds__(256) void bh_taylor_finalize_kernel(const double* __restrict__ mom, int64_t nnodes, int use_com, const T* __restrict__ centers,
+                                                                 int d, T* __restrict__ sums, T* __restrict__ cm) {
+    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (v >= nnodes) return;
+    const double eps = sizeof(T) == 4 ? 1.1920928955078125e-07 : 2.220446049250313e-16;
+    const double* o = mom + v * (2 + 2 * DM);
+    sums[v] = (T)o[0];
+    const double den = o[1] + eps;
+#pragma unroll
+    for (int l = 0; l < DM; ++l) {
+        const T c = use_com ? (T)(o[2 + l] / den) : (l < d ? centers[v * d + l] : (T)0);
+        cm[(2 * v) * DM + l] = c;
+        cm[(2 * v + 1) * DM + l] = (T)fma(-o[0], (double)c, o[2 + DM + l]);
+    }
+}
+
+// The walk of bh_walk_kernel<T, DM, 1> with g.com = cm above.  Leaves: the direct sums, through the same evaluation site.  An internal
+// node that a lane compresses adds f0(s) sums[v] - 2 f1(s) (x - c) . m1 (src/taylor.jl:43-50), f0 = phi(s / l^2)^p and f1 = d f0 / d s
+// (jet_any carries the Power chain rule; the Lengthscale's is the factor gamma2; the Constant is in alpha_k).  The criterion is strict
+// and h.r >= 0, so a lane that takes the term has s > 0: the derivative of Exponential, GammaExponential and Matern(nu < 1), singular
+// at s = 0, is never USED there (a lane that does not take the term may evaluate it at 0 and discards the result).
+template <typename T, int DM>
+__global__ __launch_bounds__(64) void bh_taylor_walk_kernel(const BhWalk<T> g, const KParams<T> kp) {
+    const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    const bool live = t < g.n;
+    T x[DM];
+    {
+        const T* xp = g.Xs + (live ? t : 0) * DM;
+#pragma unroll
+        for (int l = 0; l < DM; ++l) x[l] = xp[l];
+    }
+    int resume = live ? 0 : 0x7fffffff;      // a lane takes part at node v when v >= resume; lanes beyond n never do
+    T acc = (T)0;
+    int v = 0;
+    while (v < g.nnodes) {
+        v = __builtin_amdgcn_readfirstlane(v);
+        const int lo = g.lo[v], hi = g.hi[v], skip = g.skip[v];
+        const bool act = v >= resume;
+        if (skip == v + 1) {                 // a leaf
+            if (__any(act)) {
+                for (int j = lo; j < hi; ++j) {
+                    const T* y = g.Ys + (int64_t)j * DM;
+                    T s = (T)0;
+#pragma unroll
+                    for (int l = 0; l < DM; ++l) { const T q = x[l] - y[l]; s = fma_t(q, q, s); }
+                    const T kv = phi_any<T>(g.family, s * kp.gamma2, kp);
+                    if (act) acc = fma_t(kv, g.ws[j], acc);
+                }
+            }
+            v = v + 1;
+            continue;
+        }
+        const T* c = g.com + (int64_t)v * 2 * DM;
+        const T* m1 = c + DM;
+        T s = (T)0, dot = (T)0;
+#pragma unroll
+        for (int l = 0; l < DM; ++l) { const T q = x[l] - c[l]; s = fma_t(q, q, s); dot = fma_t(q, m1[l], dot); }
+        const bool far = g.rad[v] < g.theta * cg_sqrt(s);                   // src/taylor.jl:43, per target
+        const bool take = act && far;
+        if (take) resume = skip;
+        if (__any(take)) {                                                  // value and derivative once; skipped wave-wide otherwise
+            T f0, f1, f2;
+            jet_any<T>(g.family, s * kp.gamma2, kp, f0, f1, f2);
+            if (take) {
+                acc = fma_t(f0, g.sums[v], acc);
+                acc = fma_t((T)-2 * (f1 * kp.gamma2), dot, acc);
+            }
+        }
+        v = __any(act && !far) ? v + 1 : skip;
+    }
+    if (live) {
+        const int64_t i = g.xperm[t];
+        T res = g.alpha_k * acc;
+        if (g.diag_len > 0) res = fma_t(g.alpha * g.diag[g.diag_len == 1 ? 0 : i], g.w[i], res);
+        g.b[i] = (g.beta == (T)0) ? res : fma_t(g.beta, g.b[i], res);       // beta == 0: b is never read
+    }
+}
+
 }  // namespace covgram
 
 struct covgram_bh {
@@ -392,9 +514,9 @@ struct covgram_bh {
     std::vector<int64_t> off;
     // per-product storage (allocated once: a product allocates nothing)
     void* ws = nullptr;              // m
-    double* mom = nullptr;           // 2 nnodes (2 + DM)
-    void* sums = nullptr;            // nnodes 2
-    void* com = nullptr;             // nnodes 2 DM
+    double* mom = nullptr;           // 2 nnodes (2 + DM); taylor: nnodes (2 + 2 DM)
+    void* sums = nullptr;            // nnodes 2;          taylor: nnodes
+    void* com = nullptr;             // nnodes 2 DM;       taylor: per node the centre and m1
     const int32_t* lo() const { return nodes; }
     const int32_t* hi() const { return nodes + nnodes; }
     const int32_t* left() const { return nodes + 2 * nnodes; }
@@ -628,9 +750,109 @@ static void bh_moments_dm(covgram_bh* F, const void* w, hipStream_t st) {
     }
 }
 
+// taylor!: ws, then sums, centres and centred first moments (one channel; the storage of the split product holds it: nnodes (2 + 2 DM)
+// doubles <= 2 nnodes (2 + DM), and centre + m1 are the 2 DM values per node of com)
+template <typename T, int DM>
+static void bh_launch_taylor_moments(covgram_bh* F, const T* w, int use_com, hipStream_t st) {
+    const int64_t nn = F->nnodes;
+    hipLaunchKernelGGL((bh_taylor_leaf_moments_kernel<T, DM>), dim3((unsigned)((F->nleaves + 255) / 256)), dim3(256), 0, st, F->leaves, F->nleaves,
+                       F->lo(), F->hi(), F->indices, (const T*)F->Ys, w, (T*)F->ws, F->mom);
+    for (int L = F->maxdepth; L > BH_TOP_DEPTH; --L) {
+        const int64_t cnt = F->off[L + 1] - F->off[L];
+        if (cnt > 0)
+            hipLaunchKernelGGL((bh_up_level_kernel<2 * DM, 1>), dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, F->order, F->off[L], cnt,
+                               F->right(), F->mom, nn);
+    }
+    const int top = std::min<int>(F->maxdepth, BH_TOP_DEPTH);
+    if (F->off[top + 1] > 0)
+        hipLaunchKernelGGL((bh_up_top_kernel<2 * DM, 1>), dim3(1), dim3(256), 0, st, F->order, F->off_dev, top, F->right(), F->mom, nn);
+    hipLaunchKernelGGL((bh_taylor_finalize_kernel<T, DM>), dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, F->mom, nn, use_com,
+                       (const T*)F->centers, (int)F->d, (T*)F->sums, (T*)F->com);
+}
+
+template <typename T, int DM>
+static void bh_launch_taylor(covgram_bh* F, const T* w, T* b, double alpha, double beta, double theta, int use_com, const T* diag, int64_t diag_len,
+                             hipStream_t st) {
+    if (F->nnodes > 0) bh_launch_taylor_moments<T, DM>(F, w, use_com, st);
+    BhWalk<T> g;
+    g.Xs = (const T*)F->Xs; g.xperm = F->xperm; g.n = F->n; g.Ys = (const T*)F->Ys; g.ws = (const T*)F->ws;
+    g.lo = F->lo(); g.hi = F->hi(); g.skip = F->skip(); g.rad = (const T*)F->rad; g.sums = (const T*)F->sums; g.com = (const T*)F->com;
+    g.nnodes = (int32_t)F->nnodes; g.family = F->hk.k.family; g.theta = (T)theta;
+    g.alpha_k = (T)(alpha * F->hk.kp.scale); g.alpha = (T)alpha; g.beta = (T)beta;
+    g.w = w; g.diag = diag; g.diag_len = diag_len; g.b = b;
+    auto* tm = timer_next(F->ctx);
+    if (tm) (void)hipEventRecord(tm->first, st);
+    hipLaunchKernelGGL((bh_taylor_walk_kernel<T, DM>), dim3((unsigned)((F->n + 63) / 64)), dim3(64), 0, st, g, cast_params<T>(F->hk.kp));
+    if (tm) (void)hipEventRecord(tm->second, st);
+}
+
+template <typename T>
+static void bh_taylor_dm(covgram_bh* F, const void* w, void* b, double alpha, double beta, double theta, int use_com, const void* diag, int64_t diag_len,
+                         hipStream_t st) {
+    switch (F->DM) {
+        case 2: bh_launch_taylor<T, 2>(F, (const T*)w, (T*)b, alpha, beta, theta, use_com, (const T*)diag, diag_len, st); break;
+        case 4: bh_launch_taylor<T, 4>(F, (const T*)w, (T*)b, alpha, beta, theta, use_com, (const T*)diag, diag_len, st); break;
+        default: bh_launch_taylor<T, 8>(F, (const T*)w, (T*)b, alpha, beta, theta, use_com, (const T*)diag, diag_len, st); break;
+    }
+}
+
+template <typename T>
+static void bh_taylor_moments_dm(covgram_bh* F, const void* w, int use_com, hipStream_t st) {
+    switch (F->DM) {
+        case 2: bh_launch_taylor_moments<T, 2>(F, (const T*)w, use_com, st); break;
+        case 4: bh_launch_taylor_moments<T, 4>(F, (const T*)w, use_com, st); break;
+        default: bh_launch_taylor_moments<T, 8>(F, (const T*)w, use_com, st); break;
+    }
+}
+
 }  // namespace covgram
 
 using namespace covgram;
+
+// What covgram_bh_mvm and covgram_bh_taylor_mvm share: the argument checks, theta < 0 = the handle's, the staging of host buffers and
+// the copy back.  launch(a_dev, y_dev, theta, diag_dev, diag_len, stream) enqueues the product itself.
+template <typename Launch>
+static int bh_product_call(covgram_bh* F, const void* a, void* y, double beta, double theta, const void* diag, int64_t diag_len, int32_t loc,
+                           Launch launch) {
+    CG_REQUIRE(F != nullptr, COVGRAM_EINVAL, "Barnes-Hut handle is NULL");
+    CG_REQUIRE(loc == COVGRAM_HOST || loc == COVGRAM_DEVICE, COVGRAM_EINVAL, "unknown loc %d", loc);
+    const int64_t n = F->n, m = F->m;
+    CG_REQUIRE((a != nullptr || m == 0) && (y != nullptr || n == 0), COVGRAM_EINVAL, "a or y is NULL");
+    CG_REQUIRE(!(theta != theta), COVGRAM_EINVAL, "BarnesHutFactorization: theta is NaN");
+    if (theta < 0) theta = F->theta;
+    if (diag == nullptr) diag_len = 0;
+    CG_REQUIRE(diag_len == 0 || (n == m && (diag_len == 1 || diag_len == n)), COVGRAM_EINVAL,
+               "DimensionMismatch: a diagonal of length %lld on a %lld x %lld factorization (square, one value or n values)", (long long)diag_len,
+               (long long)n, (long long)m);
+    if (n == 0) return COVGRAM_OK;
+    covgram_ctx* ctx = F->ctx;
+    const size_t ts = dtype_size(F->dtype);
+    CG_DEVICE(ctx);
+    const void *a_dev = a, *d_dev = diag;
+    void* y_dev = y;
+    if (loc == COVGRAM_HOST) {                   // a is staged before anything is written back: any overlap of a and y is harmless
+        void *sa, *sy, *sd;
+        int rc = ws_reserve(ctx, 2, (size_t)std::max<int64_t>(m, 1) * ts, &sa); if (rc) return rc;
+        rc = ws_reserve(ctx, 3, (size_t)n * ts, &sy); if (rc) return rc;
+        if (m > 0) CG_CHECK_HIP(hipMemcpyAsync(sa, a, (size_t)m * ts, hipMemcpyHostToDevice, ctx->stream));
+        if (beta != 0.0) CG_CHECK_HIP(hipMemcpyAsync(sy, y, (size_t)n * ts, hipMemcpyHostToDevice, ctx->stream));
+        if (diag_len > 0) {
+            rc = ws_reserve(ctx, 4, (size_t)diag_len * ts, &sd); if (rc) return rc;
+            CG_CHECK_HIP(hipMemcpyAsync(sd, diag, (size_t)diag_len * ts, hipMemcpyHostToDevice, ctx->stream));
+            d_dev = sd;
+        }
+        a_dev = sa; y_dev = sy;
+    }
+    // (device pointers: y may be a itself — the walk reads the weights from the handle's tree-ordered copy, which the moments stage
+    //  has completed before the walk starts, and a lane reads a[i] for the diagonal term before it writes y[i])
+    launch(a_dev, y_dev, theta, d_dev, diag_len, ctx->stream);
+    CG_CHECK_HIP(hipGetLastError());
+    if (loc == COVGRAM_HOST) {
+        CG_CHECK_HIP(hipMemcpyAsync(y, y_dev, (size_t)n * ts, hipMemcpyDeviceToHost, ctx->stream));
+        CG_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return COVGRAM_OK;
+}
 
 extern "C" {
 
@@ -730,50 +952,52 @@ int covgram_bh_moments(covgram_bh* F, const void* w, void* sums, void* com, int3
 
 int covgram_bh_mvm(covgram_bh* F, const void* a, void* y, double alpha, double beta, double theta, int32_t split, const void* diag, int64_t diag_len,
                    int32_t loc) {
+    return bh_product_call(F, a, y, beta, theta, diag, diag_len, loc,
+                           [&](const void* a_dev, void* y_dev, double th, const void* d_dev, int64_t dl, hipStream_t st) {
+        if (F->dtype == COVGRAM_F32) {
+            if (split) bh_product_dm<float, 2>(F, a_dev, y_dev, alpha, beta, th, d_dev, dl, st);
+            else bh_product_dm<float, 1>(F, a_dev, y_dev, alpha, beta, th, d_dev, dl, st);
+        } else {
+            if (split) bh_product_dm<double, 2>(F, a_dev, y_dev, alpha, beta, th, d_dev, dl, st);
+            else bh_product_dm<double, 1>(F, a_dev, y_dev, alpha, beta, th, d_dev, dl, st);
+        }
+    });
+}
+
+int covgram_bh_taylor_moments(covgram_bh* F, const void* w, int32_t use_com, void* sums, void* centers, void* m1, int32_t loc) {
     CG_REQUIRE(F != nullptr, COVGRAM_EINVAL, "Barnes-Hut handle is NULL");
     CG_REQUIRE(loc == COVGRAM_HOST || loc == COVGRAM_DEVICE, COVGRAM_EINVAL, "unknown loc %d", loc);
-    const int64_t n = F->n, m = F->m;
-    CG_REQUIRE((a != nullptr || m == 0) && (y != nullptr || n == 0), COVGRAM_EINVAL, "a or y is NULL");
-    CG_REQUIRE(!(theta != theta), COVGRAM_EINVAL, "BarnesHutFactorization: theta is NaN");
-    if (theta < 0) theta = F->theta;
-    if (diag == nullptr) diag_len = 0;
-    CG_REQUIRE(diag_len == 0 || (n == m && (diag_len == 1 || diag_len == n)), COVGRAM_EINVAL,
-               "DimensionMismatch: a diagonal of length %lld on a %lld x %lld factorization (square, one value or n values)", (long long)diag_len,
-               (long long)n, (long long)m);
-    if (n == 0) return COVGRAM_OK;
+    if (F->nnodes == 0) return COVGRAM_OK;
+    CG_REQUIRE(w != nullptr, COVGRAM_EINVAL, "w is NULL");
     covgram_ctx* ctx = F->ctx;
     const size_t ts = dtype_size(F->dtype);
     CG_DEVICE(ctx);
-    const void *a_dev = a, *d_dev = diag;
-    void* y_dev = y;
-    if (loc == COVGRAM_HOST) {                   // a is staged before anything is written back: any overlap of a and y is harmless
-        void *sa, *sy, *sd;
-        int rc = ws_reserve(ctx, 2, (size_t)std::max<int64_t>(m, 1) * ts, &sa); if (rc) return rc;
-        rc = ws_reserve(ctx, 3, (size_t)n * ts, &sy); if (rc) return rc;
-        if (m > 0) CG_CHECK_HIP(hipMemcpyAsync(sa, a, (size_t)m * ts, hipMemcpyHostToDevice, ctx->stream));
-        if (beta != 0.0) CG_CHECK_HIP(hipMemcpyAsync(sy, y, (size_t)n * ts, hipMemcpyHostToDevice, ctx->stream));
-        if (diag_len > 0) {
-            rc = ws_reserve(ctx, 4, (size_t)diag_len * ts, &sd); if (rc) return rc;
-            CG_CHECK_HIP(hipMemcpyAsync(sd, diag, (size_t)diag_len * ts, hipMemcpyHostToDevice, ctx->stream));
-            d_dev = sd;
-        }
-        a_dev = sa; y_dev = sy;
-    }
-    // (device pointers: y may be a itself — the walk reads the weights from the handle's tree-ordered copy, which the moments stage
-    //  has completed before the walk starts, and a lane reads a[i] for the diagonal term before it writes y[i])
-    if (F->dtype == COVGRAM_F32) {
-        if (split) bh_product_dm<float, 2>(F, a_dev, y_dev, alpha, beta, theta, d_dev, diag_len, ctx->stream);
-        else bh_product_dm<float, 1>(F, a_dev, y_dev, alpha, beta, theta, d_dev, diag_len, ctx->stream);
-    } else {
-        if (split) bh_product_dm<double, 2>(F, a_dev, y_dev, alpha, beta, theta, d_dev, diag_len, ctx->stream);
-        else bh_product_dm<double, 1>(F, a_dev, y_dev, alpha, beta, theta, d_dev, diag_len, ctx->stream);
-    }
-    CG_CHECK_HIP(hipGetLastError());
+    const void* w_dev = w;
     if (loc == COVGRAM_HOST) {
-        CG_CHECK_HIP(hipMemcpyAsync(y, y_dev, (size_t)n * ts, hipMemcpyDeviceToHost, ctx->stream));
-        CG_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+        void* sw;
+        int rc = ws_reserve(ctx, 2, (size_t)F->m * ts, &sw); if (rc) return rc;
+        CG_CHECK_HIP(hipMemcpyAsync(sw, w, (size_t)F->m * ts, hipMemcpyHostToDevice, ctx->stream));
+        w_dev = sw;
     }
+    if (F->dtype == COVGRAM_F32) bh_taylor_moments_dm<float>(F, w_dev, use_com != 0, ctx->stream);
+    else bh_taylor_moments_dm<double>(F, w_dev, use_com != 0, ctx->stream);
+    CG_CHECK_HIP(hipGetLastError());
+    const hipMemcpyKind kind = loc == COVGRAM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    const size_t row = (size_t)F->d * ts, pitch = (size_t)2 * F->DM * ts;       // per node: the centre, then m1, DM values each
+    if (sums) CG_CHECK_HIP(hipMemcpyAsync(sums, F->sums, (size_t)F->nnodes * ts, kind, ctx->stream));
+    if (centers) CG_CHECK_HIP(hipMemcpy2DAsync(centers, row, F->com, pitch, row, (size_t)F->nnodes, kind, ctx->stream));
+    if (m1) CG_CHECK_HIP(hipMemcpy2DAsync(m1, row, (const char*)F->com + (size_t)F->DM * ts, pitch, row, (size_t)F->nnodes, kind, ctx->stream));
+    if (loc == COVGRAM_HOST) CG_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     return COVGRAM_OK;
+}
+
+int covgram_bh_taylor_mvm(covgram_bh* F, const void* a, void* y, double alpha, double beta, double theta, int32_t use_com, const void* diag,
+                          int64_t diag_len, int32_t loc) {
+    return bh_product_call(F, a, y, beta, theta, diag, diag_len, loc,
+                           [&](const void* a_dev, void* y_dev, double th, const void* d_dev, int64_t dl, hipStream_t st) {
+        if (F->dtype == COVGRAM_F32) bh_taylor_dm<float>(F, a_dev, y_dev, alpha, beta, th, use_com != 0, d_dev, dl, st);
+        else bh_taylor_dm<double>(F, a_dev, y_dev, alpha, beta, th, use_com != 0, d_dev, dl, st);
+    });
 }
 
 int covgram_bh_destroy(covgram_bh* F) {

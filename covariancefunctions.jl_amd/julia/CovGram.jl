@@ -629,9 +629,9 @@ function SparseArrays.sparse(G::Gramian{T}, δ::Real = 1e-6; leafsize::Int = 16)
 end
 
 # --- src/barneshut.jl:8-143: BarnesHutFactorization -> covgram_bh_* (ball tree over y built on the device, tree-based approximate product) ---
-# Deviation from the reference (DESIGN.md, "Barnes-Hut"): its mul! sends signed weights to taylor!, which the library does not have; here
-# mul! and * are the SPLIT Barnes-Hut product BH(w+) - BH(w-), the default of the reference's own barneshut!.  ldiv! / `\` (minres!) is not
-# provided: IterativeSolvers.cg!(x, F, b) runs on mul!.
+# Deviation from the reference (DESIGN.md, "Barnes-Hut"): its mul! sends signed weights to taylor!; here mul! and * stay the SPLIT Barnes-Hut
+# product BH(w+) - BH(w-), the default of the reference's own barneshut!, and taylor!(b, F, w, alpha, beta, theta; use_com) is a method of its
+# own (src/taylor.jl:7-57 -> covgram_bh_taylor_mvm).  ldiv! / `\` run IterativeSolvers.minres! on the Taylor product (src/barneshut.jl:64-72).
 mutable struct DeviceBarnesHut{T} <: AbstractMatrix{T}
     handle::Ptr{Cvoid}
     k::Any; x::Any; y::Any
@@ -681,6 +681,38 @@ function barneshut!(b::StridedVector{T}, F::DeviceBarnesHut{T}, w::StridedVector
                                F.handle, w, b, Float64(α), Float64(β), Float64(θ), Int32(split), Dp, Int64(F.D === nothing ? 0 : length(F.D)), HOST))
     b
 end
+# node_sums, the expansion centres and the centred first moments of src/taylor.jl:14-18 in one call: (sums, centers d × nnodes, m1 d × nnodes)
+function taylor_moments(F::DeviceBarnesHut{T}, w::StridedVector{T}; use_com::Bool = true) where {T}
+    length(w) == F.m || throw(DimensionMismatch("length of w does not match second dimension of F: $(length(w)) ≠ $(F.m)"))
+    sums = Vector{T}(undef, F.nnodes); centers = Matrix{T}(undef, F.d, F.nnodes); m1 = Matrix{T}(undef, F.d, F.nnodes)
+    check(ccall((:covgram_bh_taylor_moments, libcovgram), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32),
+                F.handle, w, Int32(use_com), sums, centers, m1, HOST))
+    sums, centers, m1
+end
+function taylor!(b::StridedVector{T}, F::DeviceBarnesHut{T}, w::StridedVector{T}, α::Real = 1, β::Real = 0, θ::Real = F.θ;
+                 use_com::Bool = true) where {T <: DevFloat}
+    length(w) == F.m || throw(DimensionMismatch("length of w does not match second dimension of F: $(length(w)) ≠ $(F.m)"))
+    length(b) == F.n || throw(DimensionMismatch("length of b does not match first dimension of F: $(length(b)) ≠ $(F.n)"))
+    stride(b, 1) == 1 && stride(w, 1) == 1 || throw(ArgumentError("taylor!: contiguous vectors expected"))
+    Dp = F.D === nothing ? Ptr{Cvoid}(C_NULL) : Ptr{Cvoid}(pointer(F.D))
+    GC.@preserve F check(ccall((:covgram_bh_taylor_mvm, libcovgram), Cint,
+                               (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Int32, Ptr{Cvoid}, Int64, Int32),
+                               F.handle, w, b, Float64(α), Float64(β), Float64(θ), Int32(use_com), Dp, Int64(F.D === nothing ? 0 : length(F.D)), HOST))
+    b
+end
+# the operator minres! sees: the Taylor product of F (use_com = false: an exactly linear map)
+struct TaylorProduct{T} <: AbstractMatrix{T}
+    F::DeviceBarnesHut{T}
+    use_com::Bool
+end
+Base.size(A::TaylorProduct) = size(A.F)
+Base.getindex(A::TaylorProduct, i::Integer, j::Integer) = A.F[i, j]
+LinearAlgebra.mul!(b::StridedVector{T}, A::TaylorProduct{T}, w::StridedVector{T}, α::Real = 1, β::Real = 0) where {T <: DevFloat} =
+    taylor!(b, A.F, w, α, β; use_com = A.use_com)
+function LinearAlgebra.ldiv!(x::StridedVector{T}, F::DeviceBarnesHut{T}, b::StridedVector{T}; use_com::Bool = true, kwargs...) where {T <: DevFloat}
+    CovarianceFunctions.IterativeSolvers.minres!(x, TaylorProduct{T}(F, use_com), b; kwargs...)
+end
+Base.:\(F::DeviceBarnesHut{T}, b::StridedVector{T}; kwargs...) where {T <: DevFloat} = ldiv!(zeros(T, F.m), F, b; initially_zero = true, kwargs...)
 LinearAlgebra.mul!(b::StridedVector{T}, F::DeviceBarnesHut{T}, w::StridedVector{T}, α::Real = 1, β::Real = 0) where {T <: DevFloat} =
     barneshut!(b, F, w, α, β)
 function LinearAlgebra.mul!(B::StridedMatrix{T}, F::DeviceBarnesHut{T}, W::StridedMatrix{T}, α::Real = 1, β::Real = 0) where {T <: DevFloat}

@@ -22,6 +22,9 @@
  *   covgram_bh_create      replaces  BarnesHutFactorization(k, x, y, D; theta, leafsize)                 src/barneshut.jl:25-39
  *   covgram_bh_mvm         replaces  barneshut!(b, F, w, alpha, beta, theta; split) and mul!(b, F, w, alpha, beta)   src/barneshut.jl:45-143
  *   covgram_bh_moments     replaces  node_sums / compute_centers_of_mass                                 src/barneshut.jl:145-190
+ *   covgram_bh_taylor_mvm  replaces  taylor!(b, F, w, alpha, beta, theta; use_com), the signed branch of mul!      src/taylor.jl:7-57
+ *   covgram_bh_taylor_moments  replaces  its node_sums / weighted_node_sums / centring of the first moments      src/taylor.jl:15-18
+ *   (covgram_bh_taylor_mvm under a binding's MINRES replaces ldiv!(x, F, b) and F \ b               src/barneshut.jl:64-72)
  *   covgram_toeplitz_*     replaces  mul!(y, ::SymmetricToeplitz/Toeplitz/Circulant, a, α, β) of ToeplitzMatrices 0.7.1 as
  *                          constructed by gramian(k, x::StepRangeLen, y::StepRangeLen)            src/gramian.jl:167-189
  *   covgram_toeplitz_durbin / _levinson / _trench  replace durbin! / levinson! / trench!             src/toeplitz.jl:12-111
@@ -62,7 +65,8 @@ extern "C" {
                                the info key "last_matrix_path";
                                covgram_block_matrix, the COVGRAM_BLOCK_* kinds and the info key "last_block_matrix_path";
                                covgram_decay_radius and the covgram_sparse_* handle (sparse(G, delta));
-                               the covgram_bh_* handle (BarnesHutFactorization).
+                               the covgram_bh_* handle (BarnesHutFactorization);
+                               covgram_bh_taylor_moments and covgram_bh_taylor_mvm (taylor! on that handle).
                                A binding checks covgram_version() against the header it mirrors at load time */
 
 typedef enum covgram_status {
@@ -420,8 +424,8 @@ int covgram_sparse_destroy(covgram_sparse* S);
  *   criterion is evaluated per target; the terms a target receives are exactly the recursion's, added in pre-order.
  *   theta < 0: the handle's; theta = 0: the exact product.  split != 0: BH(a+) - BH(a-) with a+ = max(a, 0), a- = max(-a, 0)
  *   (src/barneshut.jl:101-112): both signs carry their own moments and share one walk; an empty sign adds exact zeros, so the weights are
- *   never inspected on the host.  split == 0: the single pass on a as it is.  (The reference's mul! sends signed weights to taylor!,
- *   which this library does not have: bindings map mul! to split = 1, the default of the reference's own barneshut!.)
+ *   never inspected on the host.  split == 0: the single pass on a as it is.  (The reference's mul! sends signed weights to taylor!:
+ *   that product is covgram_bh_taylor_mvm below.)
  *   diag: NULL, or diag_len = 1 or n scalars of the points' dtype (n == m): the diagonal D of src/barneshut.jl:92-94.
  *   With loc == DEVICE the product is stream-ordered, allocates nothing and never synchronises: a captured graph may contain it.
  *   m = 0: y <- beta y.  n = 0: returns at once.  Option "time_kernels" brackets the walk kernel. */
@@ -433,6 +437,21 @@ int covgram_bh_export(const covgram_bh* F, int32_t* indices, int32_t* lo, int32_
 int covgram_bh_moments(covgram_bh* F, const void* w, void* sums, void* com, int32_t loc);
 int covgram_bh_mvm(covgram_bh* F, const void* a, void* y, double alpha, double beta, double theta, int32_t split, const void* diag, int64_t diag_len,
                    int32_t loc);
+/* taylor! (src/taylor.jl:7-57): the first-order expansion of the far field, one pass for weights of any sign.
+ * covgram_bh_taylor_moments: per node sums[v] = sum w_j (signed), the expansion centre centers[v] (nnodes x d) — use_com != 0: the
+ *   |w|-weighted centre of mass of covgram_bh_moments; use_com == 0: the ball centre of covgram_bh_export, which does not depend on w —
+ *   and the centred signed first moment m1[v] = sum w_j y_j - sums[v] centers[v] (nnodes x d).  sum w_j y_j is accumulated in fp64 in the
+ *   schedule of covgram_bh_moments; m1 is centred in fp64 about the centre AS ROUNDED TO T and then rounded to T once.  A NULL output
+ *   pointer skips that array.
+ * covgram_bh_taylor_mvm: y <- alpha (T a) + beta y [+ alpha D a] with the walk, the arguments, the status codes and the m = 0 / n = 0
+ *   behaviour of covgram_bh_mvm.  A leaf adds its direct sum; an internal node with radius < theta |x_i - centers[v]| adds
+ *   f0(s) sums[v] - 2 f1(s) (x_i - centers[v]) . m1[v], s = |x_i - centers[v]|^2, f0 the kernel as a function of the squared distance
+ *   and f1 = d f0 / d s (src/taylor.jl:43-50).  The criterion is strict, so s > 0 wherever f1 is evaluated.  With use_com == 0 the
+ *   product is an exactly linear map of a (the centres and the set of compressed nodes do not depend on a); with use_com != 0 and
+ *   a >= 0 it is the single pass of covgram_bh_mvm up to rounding (m1 is then rounding-level). */
+int covgram_bh_taylor_moments(covgram_bh* F, const void* w, int32_t use_com, void* sums, void* centers, void* m1, int32_t loc);
+int covgram_bh_taylor_mvm(covgram_bh* F, const void* a, void* y, double alpha, double beta, double theta, int32_t use_com, const void* diag,
+                          int64_t diag_len, int32_t loc);
 int covgram_bh_destroy(covgram_bh* F);
 
 /* Toeplitz T[i,j] = vc[i-j] (i >= j), vr[j-i] (i < j); vr == NULL: symmetric (vr = vc, m = n).
