@@ -18,13 +18,14 @@ from .kernels import (AbstractKernel, MercerKernel, StationaryKernel, IsotropicK
                       SeparableProduct, separable, SeparableKernel, Separable, GradientKernel, ValueGradientKernel, HessianKernel, ValueGradientHessianKernel, InputTrait,
                       GenericInput, IsotropicInput, DotProductInput, StationaryInput, StationaryLinearFunctionalInput,
                       PeriodicInput, input_trait, register_input_trait, ismercer, isstationary, isisotropic, isdot,
-                      device_spec, require_hessian_spec, require_vgh_spec, DomainError)
+                      device_spec, require_hessian_spec, require_vgh_spec, require_pivchol_spec, DomainError)
 from .gramian import (Gramian, BlockGramian, HessianGramian, ValueGradientHessianGramian, SymmetricToeplitz, Toeplitz, Circulant, KroneckerProduct, kronecker,
                       SeparableGramian, LazyMatrixProduct, LazyMatrixSum, ScaledOperator, LinearMapBlockGramian, CosineBlockGramian, PointJacobianBlockGramian, Fill, LazyOperator, LazyGrid, StepRangeLen,
                       srange, gramian, mul_, get_ctx, set_option, get_info, kernel_time, SparseGramian, sparse, decay_radius,
                       BarnesHutFactorization, require_barneshut_spec)
 from .dist import ShardedGramian, shard_bounds
 from .solve import cg, minres, solve, toeplitz_solve, durbin, levinson, trench
-from .factorize import cholesky, factorize, diagonal, CholeskyFactor, PivotedCholesky
+from .factorize import (cholesky, factorize, diagonal, CholeskyFactor, PivotedCholesky, pivoted_cholesky, PivotedCholeskyPreconditioner,
+                        preconditioner)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -22,6 +22,7 @@ F32, F64 = 0, 1
 HOST, DEVICE = 0, 1
 OK, EINVAL, EUNSUPPORTED, EHIP, ENODEVICE, ENOMEM = 0, -1, -2, -3, -4, -5
 MATERNP_MAX_P = 8
+PIVCHOL_MAX_RANK = 1024   # COVGRAM_PIVCHOL_MAX_RANK
 COMM_ID_BYTES = 128
 BLOCK_GRADIENT, BLOCK_VALUE_GRADIENT, BLOCK_HESSIAN, BLOCK_VALUE_GRADIENT_HESSIAN = range(4)   # kinds of covgram_block_matrix
 ABI_VERSION = 113   # COVGRAM_VERSION of the include/covgram.h these prototypes mirror
@@ -140,6 +141,7 @@ PROTOTYPES = {
     "covgram_kron_mvm": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), _I32, _I32,
                                    _P, _I64, _P, _I64, _I32, _D, _D, _I32]),
     "covgram_lowrank_mvm": (C.c_int, [_P, _P, _I64, _P, _I64, _I64, _I64, _I64, _I32, _P, _I64, _P, _I64, _I32, _D, _D, _I32]),
+    "covgram_pivoted_cholesky": (C.c_int, [_P, _KP, _P, _I32, _D, _P, _I64, _P, _P, _P]),
     "covgram_debug_kernel_params": (C.c_int, [_KP, _I32, _I32, C.POINTER(_D)]),
 }
 

@@ -7,17 +7,21 @@ cholesky implementation to avoid instantiating G in the low rank case" (:191).  
                                    diagonal and one Gramian column per step (n kernel evaluations on the device each), so a
                                    rank-r factor of an n x n Gramian costs O(n r) kernel evaluations and O(n r^2) flops and
                                    never forms the matrix;
-  * `factorize(G)`              = pivoted Cholesky with tol = 1e-6 up to n = 2^14, else the lazy G itself (CG path).
+  * `factorize(G)`              = pivoted Cholesky with tol = 1e-6 up to n = 2^14, else the lazy G itself (CG path);
+  * `pivoted_cholesky(G, r)`    = the same factor by covgram_pivoted_cholesky (csrc/pivchol.hip): one launch per pivot, no host
+                                   synchronisation before the end — the set-up of
+  * `PivotedCholeskyPreconditioner(G, D, r)` = (L L' + D)^-1 for CG on G + D, applied through covgram_lowrank_mvm.
 Everything besides the kernel evaluations is torch plumbing on the same stream.
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import Optional, Union
 
 import torch
 
+from . import _ffi
 from . import kernels as K
-from .gramian import Gramian, LazyOperator
+from .gramian import Gramian, LazyOperator, _dtype_code
 
 DEFAULT_MAX_CHOLESKY_SIZE = 2 ** 14     # src/gramian.jl:201
 DEFAULT_TOL = 1e-6                      # src/gramian.jl:202
@@ -43,10 +47,12 @@ class CholeskyFactor(LazyOperator):
 
 
 class PivotedCholesky(LazyOperator):
-    """P' G P ≈ L L' of rank r: `L` is n x r in ORIGINAL row order (row piv[k] is the k-th pivot), `piv`, `rank`."""
+    """P' G P ≈ L L' of rank r: `L` is n x r in ORIGINAL row order (row piv[k] is the k-th pivot), `piv`, `rank`;
+    `residual_diagonal` = diag(G - L L') where the factorisation kept it (pivoted_cholesky), else None."""
 
-    def __init__(self, L: torch.Tensor, piv: torch.Tensor, rank: int):
+    def __init__(self, L: torch.Tensor, piv: torch.Tensor, rank: int, residual_diagonal: Optional[torch.Tensor] = None):
         self.L, self.piv, self.rank = L, piv, rank
+        self.residual_diagonal = residual_diagonal
         self.shape = (L.shape[0], L.shape[0])
         self.dtype, self.device = L.dtype, L.device
 
@@ -117,3 +123,117 @@ def factorize(G: LazyOperator, max_cholesky_size: int = DEFAULT_MAX_CHOLESKY_SIZ
     if n <= max_cholesky_size and isinstance(G, Gramian) and G.issymmetric():
         return cholesky(G, pivoted=True, check=False, tol=tol)
     return G
+
+
+# ----------------------------------------------------------------------------------------------
+# the device factorisation and the preconditioner built on it
+# ----------------------------------------------------------------------------------------------
+def pivoted_cholesky(G: Gramian, max_rank: int, tol: float = 0.0) -> PivotedCholesky:
+    """P' G P ≈ L L' of rank <= max_rank for a symmetric Gramian (x ≡ y) of one isotropic profile, fp32 or fp64, by
+    covgram_pivoted_cholesky: LAPACK pstrf's rule (stop at the first pivot <= tol, ties to the smallest index), one launch per pivot,
+    G never formed.  The only host read is `rank`, at the end.  Returns the PivotedCholesky of `cholesky(G, pivoted=True)`: L is
+    n x rank (rows in the original order), piv = the pivots followed by the remaining indices in ascending order, and
+    `residual_diagonal` = diag(G - L L')."""
+    if not isinstance(G, Gramian):
+        raise NotImplementedError("pivoted_cholesky: a Gramian is expected")
+    if G.y is not G.x:
+        raise _ffi.DimensionMismatch(_ffi.EINVAL, "pivoted_cholesky: a symmetric Gramian gramian(k, x) is expected (y is not x)")
+    spec = K.require_pivchol_spec(G.k)
+    n = G.shape[0]
+    max_rank = int(max_rank)
+    dev, dt = G.device, G.dtype
+    Lcm = torch.empty((max(max_rank, 0), n), dtype=dt, device=dev)        # column-major n x max_rank
+    piv = torch.empty(max(max_rank, 0), dtype=torch.int32, device=dev)
+    dres = torch.empty(n, dtype=dt, device=dev)
+    rk = torch.zeros(1, dtype=torch.int32, device=dev)
+    ctx = G._px.ctx.bind_stream()
+    P = _ffi._P
+    _ffi.check(_ffi.lib().covgram_pivoted_cholesky(ctx, _ffi.kref(spec), G._px.handle, max_rank, float(tol), P(Lcm.data_ptr()), max(n, 1),
+                                                   P(piv.data_ptr()), P(dres.data_ptr()), P(rk.data_ptr())))
+    rank = int(rk)                                            # the one synchronisation
+    live = torch.ones(n, dtype=torch.int8, device=dev)
+    head = piv[:rank].long()
+    live[head] = 0
+    rest = torch.sort(live, descending=True, stable=True).indices[:n - rank]   # the unpivoted indices, ascending (no host read)
+    return PivotedCholesky(Lcm[:rank].t(), torch.cat([head, rest]), rank, residual_diagonal=dres)
+
+
+class PivotedCholeskyPreconditioner(LazyOperator):
+    """M^-1 = (L L' + D)^-1 with L the rank-r pivoted Cholesky factor of the Gramian G and D a positive diagonal (a float, or a 1-D
+    tensor of length n): the preconditioner of CG on G + D.  Set-up: L by `pivoted_cholesky`, C = I_r + L' D^-1 L = R' R (r x r,
+    torch, factored on the host in fp64), W = D^-1 L R^-1.  By Woodbury's identity M^-1 = D^-1 - W W', so `P(r)` is one elementwise product and ONE
+    covgram_lowrank_mvm (alpha = -1, beta = 1 onto y = D^-1 r, a fresh tensor).  `logdet()` = log det(L L' + D) = log det C +
+    sum log D_i.  Callable: cg(G + D, b, precond=P), with or without graph=True."""
+
+    def __init__(self, G: Gramian, diag: Union[float, torch.Tensor], rank: int, tol: float = 0.0):
+        n = G.shape[0]
+        self.shape = (n, n)
+        self.dtype, self.device = G.dtype, G.device
+        if torch.is_tensor(diag):
+            if diag.dim() != 1 or diag.shape[0] != n:
+                raise _ffi.DimensionMismatch(_ffi.EINVAL, f"DimensionMismatch: diag has shape {tuple(diag.shape)}, expected ({n},)")
+            D = diag.to(device=self.device, dtype=self.dtype).contiguous()
+            if not bool((D > 0).all()):
+                raise ValueError("PivotedCholeskyPreconditioner: every entry of diag must be positive")
+        else:
+            if not float(diag) > 0:
+                raise ValueError(f"PivotedCholeskyPreconditioner: diag = {diag} must be positive")
+            D = torch.full((n,), float(diag), dtype=self.dtype, device=self.device)
+        self.factor = pivoted_cholesky(G, min(int(rank), n), tol)
+        self.rank = self.factor.rank
+        self.D, self.Dinv = D, 1.0 / D
+        L = self.factor.L
+        DL = self.Dinv[:, None] * L
+        Cm = L.T @ DL
+        Cm.diagonal().add_(1.0)
+        # The r x r part runs on the host, in fp64: the set-up has synchronised on `rank` already, r <= 1024, and the n x r operand then
+        # meets the device only in GEMMs (a right-sided triangular solve on the 131072 x 128 fp64 operand ran out of rocBLAS workspace and
+        # faulted, profiles/pivchol.txt).  C = R' R;  W = D^-1 L R^-1.
+        R64 = torch.linalg.cholesky(Cm.to(device="cpu", dtype=torch.float64), upper=True)
+        Rinv = torch.linalg.solve_triangular(R64, torch.eye(R64.shape[0], dtype=torch.float64), upper=True)
+        self.R = R64.to(device=self.device, dtype=self.dtype)
+        W = DL @ Rinv.to(device=self.device, dtype=self.dtype)
+        self._Wcm = W.t().contiguous()                                                # column-major n x r for the library
+
+    @property
+    def W(self):
+        return self._Wcm.t()
+
+    def __call__(self, r: torch.Tensor) -> torch.Tensor:
+        n, rk = self.shape[0], self.rank
+        if r.shape[0] != n:
+            raise _ffi.DimensionMismatch(_ffi.EINVAL, f"DimensionMismatch: r has length {r.shape[0]}, expected {n}")
+        r = r.to(device=self.device, dtype=self.dtype)
+        vec = r.dim() == 1
+        a = r.contiguous() if vec else r.t().contiguous()                             # column-major n x p
+        y = (self.Dinv * a).contiguous()                                              # fresh: never aliases a
+        if rk > 0 and n > 0:
+            from .gramian import get_ctx
+            ctx = get_ctx(self.device).bind_stream()
+            P = _ffi._P
+            _ffi.check(_ffi.lib().covgram_lowrank_mvm(ctx, P(self._Wcm.data_ptr()), n, P(self._Wcm.data_ptr()), n, n, n, rk, _dtype_code(self.dtype),
+                                                      P(a.data_ptr()), n, P(y.data_ptr()), n, 1 if vec else a.shape[0], -1.0, 1.0, _ffi.DEVICE))
+        return y if vec else y.t()
+
+    def mul_(self, y, a, alpha=1.0, beta=0.0):
+        t = self(a)
+        return y.mul_(beta).add_(t, alpha=alpha) if beta != 0 else y.copy_(alpha * t)
+
+    def logdet(self) -> torch.Tensor:
+        """log det(L L' + D) (a 0-dim device tensor)."""
+        return 2.0 * torch.log(self.R.diagonal()).sum() + torch.log(self.D).sum()
+
+    def to_dense(self):
+        """The dense M^-1 = D^-1 - W W' (tests)."""
+        return torch.diag(self.Dinv) - self.W @ self.W.T
+
+
+def preconditioner(A, rank: int, tol: float = 0.0) -> PivotedCholeskyPreconditioner:
+    """The pivoted-Cholesky preconditioner of A = G + Diagonal(d) (a Gramian plus a 1-D tensor, as `G + d` builds it) for
+    cg(A, b, precond=...).  Anything else raises UnsupportedKernel."""
+    from .solve import _split_shift
+    G, d = _split_shift(A)
+    if d is None or not isinstance(G, Gramian):
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"preconditioner: {type(A).__name__} is not a Gramian plus a diagonal (G + d with a 1-D "
+                                                        "tensor d); no preconditioner is defined for it")
+    return PivotedCholeskyPreconditioner(G, d, rank, tol)

@@ -782,6 +782,21 @@ def require_vgh_spec(k, d: Optional[int] = None):
     return spec
 
 
+def require_pivchol_spec(k):
+    """The covgram_kernel that covgram_pivoted_cholesky runs for gramian(k, x), checked on the host before any device call: ONE
+    isotropic profile (EQ, Exponential, RQ, GammaExponential, Cauchy, IMQ, MaternP, Matern) under Lengthscale, Constant and Power
+    wrappers.  Composites, dot-product and GenericInput kernels raise UnsupportedKernel naming the kernel."""
+    name = type(k).__name__
+    spec = device_spec(k)
+    if spec is None or not isinstance(spec, _ffi.covgram_kernel):
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"pivoted_cholesky({name}): only single isotropic profiles have a device "
+                                                        "factorisation, not composites (Sum, Product of profiles) or GenericInput kernels")
+    if spec.trait != _ffi.ISOTROPIC:
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"pivoted_cholesky({name}): dot-product kernels have no device factorisation (supported: "
+                                                        "EQ, Exponential, RQ, GammaExponential, Cauchy, InverseMultiQuadratic, MaternP, Matern)")
+    return spec
+
+
 # ----------------------------------------------------------------------------------------------
 # decay radius of exponentially decaying isotropic kernels (src/sparse.jl:24-38)
 # ----------------------------------------------------------------------------------------------

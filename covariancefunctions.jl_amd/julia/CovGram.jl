@@ -568,7 +568,23 @@ function gramian(k::FiniteBasis{T}, x::AbstractVector, y::AbstractVector) where 
     DeviceLowRank{T}(U, V)
 end
 
-# --- src/sparse.jl:5-38: sparse(G, δ) -> covgram_sparse_* (count / scan / fill on the device instead of the ball-tree range search) ------
+# --- src/gramian.jl:191 ("a special cholesky implementation to avoid instantiating G in the low rank case") -> covgram_pivoted_cholesky ----
+# The diagonally pivoted Cholesky factor of gramian(k, x) for one isotropic profile, on the device: one launch per pivot, nothing
+# synchronises with the host.  L (n × max_rank, column-major, leading dimension ldl), piv (max_rank Int32), dres (n entries of T) and
+# rank (one Int32) are DEVICE pointers; the caller reads `rank` when it needs it.  Returns false when the kernel has no device factorisation.
+const PIVCHOL_MAX_RANK = 1024                # COVGRAM_PIVCHOL_MAX_RANK
+function pivoted_cholesky!(L::Ptr{Cvoid}, ldl::Integer, piv::Ptr{Cvoid}, dres::Ptr{Cvoid}, rank::Ptr{Cvoid}, G::Gramian{T}, max_rank::Integer;
+                           tol::Real = 0.0) where {T <: DevFloat}
+    spec = device_kernel(G.k); (spec === nothing || !(spec isa CKernel) || spec.trait != ISO) && return false
+    G.x === G.y || throw(ArgumentError("pivoted_cholesky!: a symmetric Gramian gramian(k, x) is expected"))
+    X = points(G.x, T)
+    check(ccall((:covgram_pivoted_cholesky, libcovgram), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Float64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                ctx(), kref(spec), X.handle, Int32(max_rank), Float64(tol), L, Int64(ldl), piv, dres, rank))
+    return true
+end
+
+# --- src/sparse.jl:5-38: sparse(G, δ) -> covgram_sparse_*(count / scan / fill on the device instead of the ball-tree range search) ------
 # decay_radius as the LIBRARY defines it (include/covgram.h): l r0(δ / |c|) — src/sparse.jl:38 divides by l and drops δ, and ignores
 # Constant factors; both are put right there.
 function device_decay_radius(spec, δ::Real)

@@ -32,6 +32,7 @@
  *                                                                                                 src/algebra.jl:91-95, src/separable.jl:33-42
  *   covgram_lowrank_mvm    replaces  mul!(y, L::LazyMatrixProduct(U, V'), a, α, β)                src/lazy_linear_algebra.jl:78-85
  *                          as built by gramian(k::FiniteBasis, x, y)                              src/mercer.jl:61-70
+ *   covgram_pivoted_cholesky  replaces  cholesky(G::Gramian, Val(true); tol) without instantiating G (the reference's own TODO)   src/gramian.jl:191-199
  *   covgram_kernel         encodes   the kernel value k together with input_trait(k)              src/properties.jl:31-45
  *   covgram_kernel_composite encodes Sum / Product / Power of same-trait kernels                  src/algebra.jl:5-63, src/properties.jl:47-63
  *
@@ -66,7 +67,8 @@ extern "C" {
                                covgram_block_matrix, the COVGRAM_BLOCK_* kinds and the info key "last_block_matrix_path";
                                covgram_decay_radius and the covgram_sparse_* handle (sparse(G, delta));
                                the covgram_bh_* handle (BarnesHutFactorization);
-                               covgram_bh_taylor_moments and covgram_bh_taylor_mvm (taylor! on that handle).
+                               covgram_bh_taylor_moments and covgram_bh_taylor_mvm (taylor! on that handle);
+                               covgram_pivoted_cholesky and COVGRAM_PIVCHOL_MAX_RANK.
                                A binding checks covgram_version() against the header it mirrors at load time */
 
 typedef enum covgram_status {
@@ -508,6 +510,28 @@ int covgram_kron_mvm(covgram_ctx* ctx, const void* const* factors, const int64_t
 int covgram_lowrank_mvm(covgram_ctx* ctx, const void* U, int64_t ldu, const void* V, int64_t ldv, int64_t n, int64_t m,
                         int64_t r, int32_t dtype, const void* a, int64_t lda, void* y, int64_t ldy, int32_t nrhs,
                         double alpha, double beta, int32_t loc);
+
+/* P' G P ~= L L' by diagonal pivoting for the symmetric Gramian G = k(X, X) of ONE isotropic profile, never forming G: the set-up of a
+ * low-rank preconditioner for CG on G + D (covgram/factorize.py: PivotedCholeskyPreconditioner), entirely on the device.  The
+ * semantics are LAPACK pstrf's, as oracle.pivoted_cholesky restates them:
+ *   the residual diagonal starts at k(x_i, x_i) = scale phi(0);  step k: p = argmax of the residual diagonal, TIES TO THE SMALLEST
+ *   INDEX (inside a workgroup and across workgroups: results are reproducible), stop when !(dmax > tol) (a NaN stops too);
+ *   col_i = k(x_i, x_p) - sum_{j<k} L[i,j] L[p,j] (the sum in the order j = 0 .. k-1, fused multiply-adds of the data's type);
+ *   L[i,k] = col_i / sqrt(dmax);  dres[i] -= L[i,k]^2;  dres[p] = 0 exactly, and an entry that is exactly zero stays zero (p is retired:
+ *   with tol >= 0 a zero is never chosen).
+ * k(x_i, x_p) is evaluated with the arithmetic of covgram_matrix (direct differences, unfolded profiles).
+ * All outputs are DEVICE pointers: L column-major n x max_rank (ldl >= n, rows in the original order), piv max_rank entries, dres n
+ * entries of the points' type (the residual diagonal on return), rank ONE int32.  On return (stream order) rank = the number of columns
+ * written, piv[0:rank] = the pivots in order; columns >= rank of L and piv[rank:] are left untouched.
+ * One launch per pivot, max_rank launches enqueued back to back on the ctx stream; NOTHING in the call synchronises with the host (the
+ * caller reads rank when it needs it), and no workgroup ever waits for another: a launch starts by reducing the previous launch's <= 1024
+ * per-workgroup (value, index) partials, and once a launch has decided to stop, every later one returns on a `done` word.
+ * Supported: EQ, Exponential, RQ, GammaExponential, Cauchy, IMQ, MaternP, Matern(nu) with Lengthscale, Constant and Power wrappers.
+ * Composites and dot-product kernels: COVGRAM_EUNSUPPORTED; max_rank > COVGRAM_PIVCHOL_MAX_RANK: COVGRAM_EUNSUPPORTED; tol < 0 (or NaN),
+ * max_rank < 0, max_rank > n, ldl < n: COVGRAM_EINVAL — all checked before any device call.  n = 0 or max_rank = 0 writes rank = 0. */
+#define COVGRAM_PIVCHOL_MAX_RANK 1024
+int covgram_pivoted_cholesky(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, int32_t max_rank, double tol,
+                             void* L, int64_t ldl, int32_t* piv, void* dres, int32_t* rank);
 
 /* Test hook: the double-precision parameter block handed to the device kernels for `k`
  * (out45[0..8] = gamma, gamma^2, scale, param, c0, 2p+1, Taylor bound, d1, d2; then the MaternP tables
