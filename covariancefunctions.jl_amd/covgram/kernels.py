@@ -741,45 +741,37 @@ def require_device_spec(k):
 
 
 HESSIAN_MAX_D = 32
+# the families of COVGRAM_HESS_FAMILIES in csrc/hess_mvm.hpp, which the library's own checks and launchers are generated from
 _HESSIAN_FAMILIES = (_ffi.EQ, _ffi.RQ, _ffi.CAUCHY, _ffi.IMQ, _ffi.DOT, _ffi.EXPDOT)
+
+
+def _require_hess_spec(wrapper: str, k, d: Optional[int]):
+    name = type(k).__name__
+    spec = device_spec(k)
+    if spec is None or not isinstance(spec, _ffi.covgram_kernel):
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"{wrapper}({name}): only single profiles have a device path, "
+                                                        "not composites or GenericInput kernels")
+    if spec.family not in _HESSIAN_FAMILIES:
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"{wrapper}({name}): no closed-form fourth derivative is compiled for this profile "
+                                                        "(supported: EQ, RQ, Cauchy, InverseMultiQuadratic, ExponentialDot, Dot)")
+    if spec.power != 1:
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"{wrapper}({name}): Power wrappers (exponent {spec.power}) have no device path")
+    if d is not None and d > HESSIAN_MAX_D:
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"{wrapper}({name}): d = {d} exceeds the compiled maximum {HESSIAN_MAX_D}")
+    return spec
 
 
 def require_hessian_spec(k, d: Optional[int] = None):
     """The covgram_kernel that covgram_hess_mvm runs for HessianKernel(k), checked on the host before any device call: a single
     profile whose derivatives up to the fourth have closed forms in the library (EQ, RQ, Cauchy, IMQ with Lengthscale and Constant
     factors; ExponentialDot, Dot), no Power wrapper, d <= 32.  Everything else raises UnsupportedKernel naming the kernel."""
-    name = type(k).__name__
-    spec = device_spec(k)
-    if spec is None or not isinstance(spec, _ffi.covgram_kernel):
-        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"HessianKernel({name}): only single profiles have a Hessian device path, "
-                                                        "not composites or GenericInput kernels")
-    if spec.family not in _HESSIAN_FAMILIES:
-        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"HessianKernel({name}): no closed-form fourth derivative is compiled for this profile "
-                                                        "(supported: EQ, RQ, Cauchy, InverseMultiQuadratic, ExponentialDot, Dot)")
-    if spec.power != 1:
-        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"HessianKernel({name}): Power wrappers (exponent {spec.power}) have no Hessian device path")
-    if d is not None and d > HESSIAN_MAX_D:
-        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"HessianKernel({name}): d = {d} exceeds the compiled maximum {HESSIAN_MAX_D}")
-    return spec
+    return _require_hess_spec("HessianKernel", k, d)
 
 
 def require_vgh_spec(k, d: Optional[int] = None):
     """The covgram_kernel that covgram_valgradhess_mvm runs for ValueGradientHessianKernel(k), checked on the host before any device
     call: the kernels and the bound on d of require_hessian_spec.  Everything else raises UnsupportedKernel naming the kernel."""
-    name = type(k).__name__
-    spec = device_spec(k)
-    if spec is None or not isinstance(spec, _ffi.covgram_kernel):
-        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"ValueGradientHessianKernel({name}): only single profiles have a device path, "
-                                                        "not composites or GenericInput kernels")
-    if spec.family not in _HESSIAN_FAMILIES:
-        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"ValueGradientHessianKernel({name}): no closed-form fourth derivative is compiled for this "
-                                                        "profile (supported: EQ, RQ, Cauchy, InverseMultiQuadratic, ExponentialDot, Dot)")
-    if spec.power != 1:
-        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"ValueGradientHessianKernel({name}): Power wrappers (exponent {spec.power}) have no "
-                                                        "device path")
-    if d is not None and d > HESSIAN_MAX_D:
-        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"ValueGradientHessianKernel({name}): d = {d} exceeds the compiled maximum {HESSIAN_MAX_D}")
-    return spec
+    return _require_hess_spec("ValueGradientHessianKernel", k, d)
 
 
 def require_pivchol_spec(k):

@@ -15,7 +15,6 @@
 #include "grad_bcast.hpp"
 #include "grad_wide.hpp"
 #include "hess_mvm.hpp"
-#include "vgh_mvm.hpp"
 #include "block_matrix.hpp"
 
 namespace covgram {
@@ -60,48 +59,9 @@ dense_launch_fn dense_launcher(int family) {
         launch_dense_family_10, launch_dense_family_11, launch_dense_family_12};
     return (family >= 0 && family < NUM_TU_FAMILIES) ? t[family] : nullptr;
 }
-// Hessian-kernel MVM (hess_fam.hip: one translation unit per family that has one)
-int launch_hess_family_0(const HessArgs&, int dtype);
-int launch_hess_family_2(const HessArgs&, int dtype);
-int launch_hess_family_4(const HessArgs&, int dtype);
-int launch_hess_family_5(const HessArgs&, int dtype);
-int launch_hess_family_7(const HessArgs&, int dtype);
-int launch_hess_family_8(const HessArgs&, int dtype);
-hess_launch_fn hess_launcher(int family) {
-    switch (family) {
-        case COVGRAM_EQ: return launch_hess_family_0;
-        case COVGRAM_RQ: return launch_hess_family_2;
-        case COVGRAM_CAUCHY: return launch_hess_family_4;
-        case COVGRAM_IMQ: return launch_hess_family_5;
-        case COVGRAM_DOT: return launch_hess_family_7;
-        case COVGRAM_EXPDOT: return launch_hess_family_8;
-        default: return nullptr;
-    }
-}
-// value-gradient-Hessian-kernel MVM (vgh_fam.hip: the same families)
-int launch_vgh_family_0(const VghArgs&, int dtype);
-int launch_vgh_family_2(const VghArgs&, int dtype);
-int launch_vgh_family_4(const VghArgs&, int dtype);
-int launch_vgh_family_5(const VghArgs&, int dtype);
-int launch_vgh_family_7(const VghArgs&, int dtype);
-int launch_vgh_family_8(const VghArgs&, int dtype);
-vgh_launch_fn vgh_launcher(int family) {
-    switch (family) {
-        case COVGRAM_EQ: return launch_vgh_family_0;
-        case COVGRAM_RQ: return launch_vgh_family_2;
-        case COVGRAM_CAUCHY: return launch_vgh_family_4;
-        case COVGRAM_IMQ: return launch_vgh_family_5;
-        case COVGRAM_DOT: return launch_vgh_family_7;
-        case COVGRAM_EXPDOT: return launch_vgh_family_8;
-        default: return nullptr;
-    }
-}
 // dense block Gramians (block_fam.hip: one translation unit per family)
 #define CG_DECL(n) int launch_bm_family_##n(const BlockMatArgs&, int dtype);
 CG_DECL(0) CG_DECL(1) CG_DECL(2) CG_DECL(3) CG_DECL(4) CG_DECL(5) CG_DECL(6) CG_DECL(7) CG_DECL(8) CG_DECL(9) CG_DECL(10) CG_DECL(11) CG_DECL(12)
-#undef CG_DECL
-#define CG_DECL(n) int launch_bmh_family_##n(const BlockMatArgs&, int dtype);
-CG_DECL(0) CG_DECL(2) CG_DECL(4) CG_DECL(5) CG_DECL(7) CG_DECL(8)
 #undef CG_DECL
 bm_launch_fn block_matrix_launcher(int family) {
     static const bm_launch_fn t[NUM_TU_FAMILIES] = {
@@ -109,17 +69,24 @@ bm_launch_fn block_matrix_launcher(int family) {
         launch_bm_family_7, launch_bm_family_8, launch_bm_family_9, launch_bm_family_10, launch_bm_family_11, launch_bm_family_12};
     return (family >= 0 && family < NUM_TU_FAMILIES) ? t[family] : nullptr;
 }
-bm_launch_fn block_matrix_hess_launcher(int family) {
-    switch (family) {
-        case COVGRAM_EQ: return launch_bmh_family_0;
-        case COVGRAM_RQ: return launch_bmh_family_2;
-        case COVGRAM_CAUCHY: return launch_bmh_family_4;
-        case COVGRAM_IMQ: return launch_bmh_family_5;
-        case COVGRAM_DOT: return launch_bmh_family_7;
-        case COVGRAM_EXPDOT: return launch_bmh_family_8;
-        default: return nullptr;
+// Hessian and value-gradient-Hessian MVMs (hess_fam.hip) and the Hessian kinds of the block matrix (block_fam.hip): one translation
+// unit per family of COVGRAM_HESS_FAMILIES (hess_mvm.hpp); every other family has no launcher
+#define CG_DECL(name, n, arg)                                \
+    int launch_hess_family_##n(const HessArgs&, int dtype);  \
+    int launch_vgh_family_##n(const HessArgs&, int dtype);   \
+    int launch_bmh_family_##n(const BlockMatArgs&, int dtype);
+COVGRAM_HESS_FAMILIES(CG_DECL, )
+#undef CG_DECL
+#define CG_CASE(name, n, stem) case name: return launch_##stem##_family_##n;
+#define CG_HESS_LAUNCHER(fn_t, fn, stem)                                                  \
+    fn_t fn(int family) {                                                                 \
+        switch (family) { COVGRAM_HESS_FAMILIES(CG_CASE, stem) default: return nullptr; } \
     }
-}
+CG_HESS_LAUNCHER(hess_launch_fn, hess_launcher, hess)
+CG_HESS_LAUNCHER(hess_launch_fn, vgh_launcher, vgh)
+CG_HESS_LAUNCHER(bm_launch_fn, block_matrix_hess_launcher, bmh)
+#undef CG_HESS_LAUNCHER
+#undef CG_CASE
 dense_launch_fn dense_wide_launcher(int family) {
     static const dense_launch_fn t[NUM_TU_FAMILIES] = {
         launch_dense_wide_family_0, launch_dense_wide_family_1, launch_dense_wide_family_2, launch_dense_wide_family_3,
@@ -1667,22 +1634,35 @@ int covgram_valgrad_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram
     return grad_mvm_impl(ctx, k, X, Y, a, lda, y, ldy, nrhs, alpha, beta, loc, 1);
 }
 
-// Hessian-kernel Gramian (n d^2 x m d^2): hess_mvm.hpp.  Single profiles with closed-form derivatives up to the fourth only.
-int covgram_hess_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, const void* a, int64_t lda,
-                     void* y, int64_t ldy, int32_t nrhs, double alpha, double beta, int32_t loc) {
+// The kernels that HessianKernel(k) / ValueGradientHessianKernel(k) (w: the wrapper's name) have a device path for: single profiles with
+// closed-form derivatives up to the fourth, no Power wrapper, d <= HESS_MAX_D.  The refusals of covgram_hess_mvm,
+// covgram_valgradhess_mvm and the Hessian kinds of covgram_block_matrix.
+static const char* const kFamilyNames[COVGRAM_NFAMILY] = {"ExponentiatedQuadratic", "Exponential", "RationalQuadratic", "GammaExponential", "Cauchy",
+                                                          "InverseMultiQuadratic", "MaternP", "Dot", "ExponentialDot", "Matern", "AsinDot"};
+static int hess_refusal(const char* w, const covgram_kernel* k, int d) {
+    CG_REQUIRE(k->family != COVGRAM_COMPOSITE, COVGRAM_EUNSUPPORTED, "%s of a composite kernel (Sum / Product / Power) has no device path", w);
+    CG_REQUIRE(k->family >= 0 && k->family < COVGRAM_NFAMILY, COVGRAM_EUNSUPPORTED, "unknown kernel family %d", k->family);
+    CG_REQUIRE(hess_family_ok(k->family), COVGRAM_EUNSUPPORTED, "%s(%s) has no device path (no closed-form fourth derivative compiled)", w, kFamilyNames[k->family]);
+    CG_REQUIRE(k->power == 1, COVGRAM_EUNSUPPORTED, "%s(%s^%d): Power wrappers have no device path", w, kFamilyNames[k->family], k->power);
+    CG_REQUIRE(d <= HESS_MAX_D, COVGRAM_EUNSUPPORTED, "%s(%s): d = %d exceeds the compiled maximum %d", w, kFamilyNames[k->family], d, HESS_MAX_D);
+    return COVGRAM_OK;
+}
+
+// Hessian-kernel Gramian (vgh = 0: n d^2 x m d^2) and value-gradient-Hessian-kernel Gramian (vgh = 1: n (1 + d + d^2) x m (1 + d + d^2)):
+// hess_mvm.hpp.  One driver: the two differ in the block size, the column record, the launcher, the info key and in where the powers of
+// gamma go (Hessian: gamma^4 into alpha here; VGH: per part of the block in the pack launch and the kernel's epilogue, so only the
+// constant factor goes into alpha).
+static int hess_mvm_impl(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, const void* a, int64_t lda,
+                         void* y, int64_t ldy, int32_t nrhs, double alpha, double beta, int32_t loc, int vgh) {
     int rc = check_pair(ctx, X, Y);
     if (rc) return rc;
     CG_REQUIRE(k != nullptr, COVGRAM_EINVAL, "kernel is NULL");
-    static const char* const names[COVGRAM_NFAMILY] = {"ExponentiatedQuadratic", "Exponential", "RationalQuadratic", "GammaExponential", "Cauchy",
-                                                       "InverseMultiQuadratic", "MaternP", "Dot", "ExponentialDot", "Matern", "AsinDot"};
-    CG_REQUIRE(k->family != COVGRAM_COMPOSITE, COVGRAM_EUNSUPPORTED, "HessianKernel of a composite kernel (Sum / Product / Power) has no device path");
-    CG_REQUIRE(k->family >= 0 && k->family < COVGRAM_NFAMILY, COVGRAM_EUNSUPPORTED, "unknown kernel family %d", k->family);
-    CG_REQUIRE(hess_family_ok(k->family), COVGRAM_EUNSUPPORTED, "HessianKernel(%s) has no device path (no closed-form fourth derivative compiled)", names[k->family]);
-    CG_REQUIRE(k->power == 1, COVGRAM_EUNSUPPORTED, "HessianKernel(%s^%d): Power wrappers have no device path", names[k->family], k->power);
+    const char* w = vgh ? "ValueGradientHessianKernel" : "HessianKernel";
     const int d = X->d;
-    CG_REQUIRE(d <= HESS_MAX_D, COVGRAM_EUNSUPPORTED, "HessianKernel(%s): d = %d exceeds the compiled maximum %d", names[k->family], d, HESS_MAX_D);
+    rc = hess_refusal(w, k, d);
+    if (rc) return rc;
     CG_REQUIRE(nrhs >= 1, COVGRAM_EINVAL, "nrhs must be >= 1");
-    const int64_t n = X->n, m = Y->n, bd = (int64_t)d * d;
+    const int64_t n = X->n, m = Y->n, bd = (vgh ? 1 + (int64_t)d : 0) + (int64_t)d * d;
     CG_REQUIRE(lda >= m * bd && ldy >= n * bd, COVGRAM_EINVAL, "lda / ldy smaller than the block vectors (%lld, %lld)", (long long)(m * bd), (long long)(n * bd));
     CG_REQUIRE((a != nullptr || m == 0) && (y != nullptr || n == 0), COVGRAM_EINVAL, "a or y is NULL");
     const int dtype = X->dtype;
@@ -1690,14 +1670,15 @@ int covgram_hess_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram_po
     HostKernel hk;
     rc = make_host_kernel(k, dtype, true, &hk);
     if (rc) return rc;
-    hess_launch_fn launch = hess_launcher(hk.tu_family);
-    CG_REQUIRE(launch != nullptr, COVGRAM_EUNSUPPORTED, "HessianKernel(%s) has no device path", names[k->family]);
+    hess_launch_fn launch = vgh ? vgh_launcher(hk.tu_family) : hess_launcher(hk.tu_family);
+    CG_REQUIRE(launch != nullptr, COVGRAM_EUNSUPPORTED, "%s(%s) has no device path", w, kFamilyNames[k->family]);
     if (loc == COVGRAM_DEVICE) {   // a and y may overlap (include/covgram.h): everything below reads a private copy of a
         rc = unalias_input(ctx, &a, &lda, m * bd, nrhs, y, ldy, n * bd, ts);
         if (rc) return rc;
     }
     CG_DEVICE(ctx);
-    ctx->last_hess_path = 0;
+    int64_t& last_path = vgh ? ctx->last_vgh_path : ctx->last_hess_path;
+    last_path = 0;
     if (n == 0) return COVGRAM_OK;
 
     const void* a_all = a;
@@ -1713,15 +1694,15 @@ int covgram_hess_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram_po
     }
     const bool iso = (k->trait == COVGRAM_ISOTROPIC);
     const int D = hess_pad_dim(d);
-    const int rec = hess_rec(D);
-    // d^4 k / dx dx dy dy in the pre-scaled coordinates gamma (x - c): gamma^4 by the chain rule (dot product: gamma = 1)
-    const double alpha_eff = alpha * hk.kp.scale * (iso ? hk.kp.gamma2 * hk.kp.gamma2 : 1.0);
+    const int rec = hess_rec(D, vgh != 0);
+    // Hessian: d^4 k / dx dx dy dy in the pre-scaled coordinates gamma (x - c): gamma^4 by the chain rule (dot product: gamma = 1)
+    const double alpha_eff = vgh ? alpha * hk.kp.scale : alpha * hk.kp.scale * (iso ? hk.kp.gamma2 * hk.kp.gamma2 : 1.0);
     const int64_t total = n * bd;
     // Column split: a workgroup holds 256 / D row points, so small n leaves most of the chip idle; split the columns over up to
-    // ~8 workgroups per CU, at least 4 staged chunks each, with the partial slabs (split x n d^2 scalars) within 256 MB
+    // ~8 workgroups per CU, at least 4 staged chunks each, with the partial slabs (split x n bd scalars) within 256 MB
     const int ppw = HESS_THREADS / D;
     const int64_t rowwgs = (n + ppw - 1) / ppw;
-    const int64_t minchunk = 4 * (int64_t)hess_jc(D, (int)ts);
+    const int64_t minchunk = 4 * (int64_t)hess_jc(D, (int)ts, vgh != 0);
     int64_t split = std::max<int64_t>(1, ((int64_t)ctx->num_cus * 8 + rowwgs - 1) / rowwgs);
     split = std::min(split, std::max<int64_t>(1, m / minchunk));
     split = std::min(split, std::max<int64_t>(1, (int64_t)(256.0e6 / ((double)total * ts))));
@@ -1737,12 +1718,13 @@ int covgram_hess_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram_po
         void* y_dev = (char*)y_all + (size_t)c0 * ldy_d * ts;
         if (m > 0) {
             const int64_t pe = m * (int64_t)rec;
-            if (dtype == COVGRAM_F32)
-                hipLaunchKernelGGL(hess_pack_kernel<float>, dim3((unsigned)((pe + 255) / 256)), dim3(256), 0, ctx->stream, (const float*)Y->dptr, m, d,
-                                   (const float*)a_dev, (float*)P, D, (float)hk.kp.gamma, (const float*)Cn);
-            else
-                hipLaunchKernelGGL(hess_pack_kernel<double>, dim3((unsigned)((pe + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)Y->dptr, m, d,
-                                   (const double*)a_dev, (double*)P, D, hk.kp.gamma, (const double*)Cn);
+            auto pack = [&](auto t) {
+                using T = decltype(t);
+                auto kern = vgh ? hess_pack_kernel<T, true> : hess_pack_kernel<T, false>;
+                hipLaunchKernelGGL(kern, dim3((unsigned)((pe + 255) / 256)), dim3(256), 0, ctx->stream, (const T*)Y->dptr, m, d, (const T*)a_dev, (T*)P, D,
+                                   (T)hk.kp.gamma, (const T*)Cn);
+            };
+            if (dtype == COVGRAM_F32) pack(0.0f); else pack(0.0);
             HessArgs ha;
             ha.X = X->dptr; ha.n = n; ha.d = d; ha.P = P; ha.m = m; ha.out = jsplit > 1 ? slab : y_dev; ha.Dpad = D; ha.jchunk = jchunk; ha.jsplit = jsplit;
             ha.C = Cn; ha.alpha = alpha_eff; ha.beta = beta; ha.hk = &hk; ha.stream = ctx->stream;
@@ -1750,7 +1732,7 @@ int covgram_hess_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram_po
             if (tm) (void)hipEventRecord(tm->first, ctx->stream);
             rc = launch(ha, dtype); if (rc) return rc;
             if (tm) (void)hipEventRecord(tm->second, ctx->stream);
-            ctx->last_hess_path = 1;
+            last_path = 1;
         }
         if (jsplit != 1) {   // several column chunks: fixed-order sum of their slabs; no columns: y <- beta y
             const dim3 rg((unsigned)((total + 255) / 256));
@@ -1768,108 +1750,14 @@ int covgram_hess_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram_po
     return COVGRAM_OK;
 }
 
-// Value-gradient-Hessian-kernel Gramian (n (1 + d + d^2) x m (1 + d + d^2)): vgh_mvm.hpp.  The kernels, the argument checks, the column
-// split and the slab reduce of covgram_hess_mvm; the powers of gamma are applied per part of the block by the pack launch and the
-// kernel's epilogue, so only the constant factor goes into alpha.
+int covgram_hess_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, const void* a, int64_t lda,
+                     void* y, int64_t ldy, int32_t nrhs, double alpha, double beta, int32_t loc) {
+    return hess_mvm_impl(ctx, k, X, Y, a, lda, y, ldy, nrhs, alpha, beta, loc, 0);
+}
+
 int covgram_valgradhess_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, const void* a, int64_t lda,
                             void* y, int64_t ldy, int32_t nrhs, double alpha, double beta, int32_t loc) {
-    int rc = check_pair(ctx, X, Y);
-    if (rc) return rc;
-    CG_REQUIRE(k != nullptr, COVGRAM_EINVAL, "kernel is NULL");
-    static const char* const names[COVGRAM_NFAMILY] = {"ExponentiatedQuadratic", "Exponential", "RationalQuadratic", "GammaExponential", "Cauchy",
-                                                       "InverseMultiQuadratic", "MaternP", "Dot", "ExponentialDot", "Matern", "AsinDot"};
-    CG_REQUIRE(k->family != COVGRAM_COMPOSITE, COVGRAM_EUNSUPPORTED,
-               "ValueGradientHessianKernel of a composite kernel (Sum / Product / Power) has no device path");
-    CG_REQUIRE(k->family >= 0 && k->family < COVGRAM_NFAMILY, COVGRAM_EUNSUPPORTED, "unknown kernel family %d", k->family);
-    CG_REQUIRE(hess_family_ok(k->family), COVGRAM_EUNSUPPORTED,
-               "ValueGradientHessianKernel(%s) has no device path (no closed-form fourth derivative compiled)", names[k->family]);
-    CG_REQUIRE(k->power == 1, COVGRAM_EUNSUPPORTED, "ValueGradientHessianKernel(%s^%d): Power wrappers have no device path", names[k->family], k->power);
-    const int d = X->d;
-    CG_REQUIRE(d <= HESS_MAX_D, COVGRAM_EUNSUPPORTED, "ValueGradientHessianKernel(%s): d = %d exceeds the compiled maximum %d", names[k->family], d,
-               HESS_MAX_D);
-    CG_REQUIRE(nrhs >= 1, COVGRAM_EINVAL, "nrhs must be >= 1");
-    const int64_t n = X->n, m = Y->n, bd = 1 + (int64_t)d + (int64_t)d * d;
-    CG_REQUIRE(lda >= m * bd && ldy >= n * bd, COVGRAM_EINVAL, "lda / ldy smaller than the block vectors (%lld, %lld)", (long long)(m * bd), (long long)(n * bd));
-    CG_REQUIRE((a != nullptr || m == 0) && (y != nullptr || n == 0), COVGRAM_EINVAL, "a or y is NULL");
-    const int dtype = X->dtype;
-    const size_t ts = dtype_size(dtype);
-    HostKernel hk;
-    rc = make_host_kernel(k, dtype, true, &hk);
-    if (rc) return rc;
-    vgh_launch_fn launch = vgh_launcher(hk.tu_family);
-    CG_REQUIRE(launch != nullptr, COVGRAM_EUNSUPPORTED, "ValueGradientHessianKernel(%s) has no device path", names[k->family]);
-    if (loc == COVGRAM_DEVICE) {   // a and y may overlap (include/covgram.h): everything below reads a private copy of a
-        rc = unalias_input(ctx, &a, &lda, m * bd, nrhs, y, ldy, n * bd, ts);
-        if (rc) return rc;
-    }
-    CG_DEVICE(ctx);
-    ctx->last_vgh_path = 0;
-    if (n == 0) return COVGRAM_OK;
-
-    const void* a_all = a;
-    void* y_all = y;
-    int64_t lda_d = lda, ldy_d = ldy;
-    if (loc == COVGRAM_HOST) {
-        void *sa, *sy;
-        rc = ws_reserve(ctx, 2, (size_t)std::max<int64_t>(m, 1) * bd * nrhs * ts, &sa); if (rc) return rc;
-        rc = ws_reserve(ctx, 3, (size_t)n * bd * nrhs * ts, &sy); if (rc) return rc;
-        if (m > 0) CG_CHECK_HIP(hipMemcpy2DAsync(sa, (size_t)m * bd * ts, a, (size_t)lda * ts, (size_t)m * bd * ts, nrhs, hipMemcpyHostToDevice, ctx->stream));
-        if (beta != 0.0) CG_CHECK_HIP(hipMemcpy2DAsync(sy, (size_t)n * bd * ts, y, (size_t)ldy * ts, (size_t)n * bd * ts, nrhs, hipMemcpyHostToDevice, ctx->stream));
-        a_all = sa; y_all = sy; lda_d = m * bd; ldy_d = n * bd;
-    }
-    const bool iso = (k->trait == COVGRAM_ISOTROPIC);
-    const int D = hess_pad_dim(d);
-    const int rec = vgh_rec(D);
-    const double alpha_eff = alpha * hk.kp.scale;
-    const int64_t total = n * bd;
-    // the column split of covgram_hess_mvm: up to ~8 workgroups per CU, at least 4 staged chunks each, partial slabs within 256 MB
-    const int ppw = HESS_THREADS / D;
-    const int64_t rowwgs = (n + ppw - 1) / ppw;
-    const int64_t minchunk = 4 * (int64_t)vgh_jc(D, (int)ts);
-    int64_t split = std::max<int64_t>(1, ((int64_t)ctx->num_cus * 8 + rowwgs - 1) / rowwgs);
-    split = std::min(split, std::max<int64_t>(1, m / minchunk));
-    split = std::min(split, std::max<int64_t>(1, (int64_t)(256.0e6 / ((double)total * ts))));
-    if (ctx->jsplit > 0) split = std::min<int64_t>(ctx->jsplit, std::max<int64_t>(1, m));
-    int64_t jchunk = std::max<int64_t>(1, (m + split - 1) / split);
-    const int jsplit = m > 0 ? (int)((m + jchunk - 1) / jchunk) : 0;
-    void *P = nullptr, *slab = nullptr;
-    if (m > 0) { rc = ws_reserve(ctx, 0, (size_t)m * rec * ts, &P); if (rc) return rc; }
-    if (jsplit > 1) { rc = ws_reserve(ctx, 1, (size_t)jsplit * total * ts, &slab); if (rc) return rc; }
-    const void* Cn = iso ? Y->center : nullptr;
-    for (int c0 = 0; c0 < nrhs; ++c0) {
-        const void* a_dev = (const char*)a_all + (size_t)c0 * lda_d * ts;
-        void* y_dev = (char*)y_all + (size_t)c0 * ldy_d * ts;
-        if (m > 0) {
-            const int64_t pe = m * (int64_t)rec;
-            if (dtype == COVGRAM_F32)
-                hipLaunchKernelGGL(vgh_pack_kernel<float>, dim3((unsigned)((pe + 255) / 256)), dim3(256), 0, ctx->stream, (const float*)Y->dptr, m, d,
-                                   (const float*)a_dev, (float*)P, D, (float)hk.kp.gamma, (const float*)Cn);
-            else
-                hipLaunchKernelGGL(vgh_pack_kernel<double>, dim3((unsigned)((pe + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)Y->dptr, m, d,
-                                   (const double*)a_dev, (double*)P, D, hk.kp.gamma, (const double*)Cn);
-            VghArgs va;
-            va.X = X->dptr; va.n = n; va.d = d; va.P = P; va.m = m; va.out = jsplit > 1 ? slab : y_dev; va.Dpad = D; va.jchunk = jchunk; va.jsplit = jsplit;
-            va.C = Cn; va.alpha = alpha_eff; va.beta = beta; va.hk = &hk; va.stream = ctx->stream;
-            auto* tm = timer_next(ctx);
-            if (tm) (void)hipEventRecord(tm->first, ctx->stream);
-            rc = launch(va, dtype); if (rc) return rc;
-            if (tm) (void)hipEventRecord(tm->second, ctx->stream);
-            ctx->last_vgh_path = 1;
-        }
-        if (jsplit != 1) {   // several column chunks: fixed-order sum of their slabs; no columns: y <- beta y
-            const dim3 rg((unsigned)((total + 255) / 256));
-            if (dtype == COVGRAM_F32)
-                hipLaunchKernelGGL(hess_reduce_kernel<float>, rg, dim3(256), 0, ctx->stream, (const float*)slab, jsplit, total, (float*)y_dev, (float)alpha_eff, (float)beta);
-            else
-                hipLaunchKernelGGL(hess_reduce_kernel<double>, rg, dim3(256), 0, ctx->stream, (const double*)slab, jsplit, total, (double*)y_dev, alpha_eff, beta);
-        }
-    }
-    CG_CHECK_HIP(hipGetLastError());
-    if (loc == COVGRAM_HOST) {
-        CG_CHECK_HIP(hipMemcpy2DAsync(y, (size_t)ldy * ts, y_all, (size_t)n * bd * ts, (size_t)n * bd * ts, nrhs, hipMemcpyDeviceToHost, ctx->stream));
-        CG_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return COVGRAM_OK;
+    return hess_mvm_impl(ctx, k, X, Y, a, lda, y, ldy, nrhs, alpha, beta, loc, 1);
 }
 
 // Dense instantiation of a block Gramian (block_matrix.hpp): the matrix covgram_grad_mvm / covgram_valgrad_mvm / covgram_hess_mvm /
@@ -1883,15 +1771,9 @@ int covgram_block_matrix(covgram_ctx* ctx, int32_t kind, const covgram_kernel* k
     const bool hess = kind == COVGRAM_BLOCK_HESSIAN || kind == COVGRAM_BLOCK_VALUE_GRADIENT_HESSIAN;
     const int vflag = (kind == COVGRAM_BLOCK_VALUE_GRADIENT || kind == COVGRAM_BLOCK_VALUE_GRADIENT_HESSIAN) ? 1 : 0;
     const int d = X->d;
-    if (hess) {   // the refusals of covgram_hess_mvm / covgram_valgradhess_mvm, word for word
-        static const char* const names[COVGRAM_NFAMILY] = {"ExponentiatedQuadratic", "Exponential", "RationalQuadratic", "GammaExponential", "Cauchy",
-                                                           "InverseMultiQuadratic", "MaternP", "Dot", "ExponentialDot", "Matern", "AsinDot"};
-        const char* w = vflag ? "ValueGradientHessianKernel" : "HessianKernel";
-        CG_REQUIRE(k->family != COVGRAM_COMPOSITE, COVGRAM_EUNSUPPORTED, "%s of a composite kernel (Sum / Product / Power) has no device path", w);
-        CG_REQUIRE(k->family >= 0 && k->family < COVGRAM_NFAMILY, COVGRAM_EUNSUPPORTED, "unknown kernel family %d", k->family);
-        CG_REQUIRE(hess_family_ok(k->family), COVGRAM_EUNSUPPORTED, "%s(%s) has no device path (no closed-form fourth derivative compiled)", w, names[k->family]);
-        CG_REQUIRE(k->power == 1, COVGRAM_EUNSUPPORTED, "%s(%s^%d): Power wrappers have no device path", w, names[k->family], k->power);
-        CG_REQUIRE(d <= HESS_MAX_D, COVGRAM_EUNSUPPORTED, "%s(%s): d = %d exceeds the compiled maximum %d", w, names[k->family], d, HESS_MAX_D);
+    if (hess) {
+        rc = hess_refusal(vflag ? "ValueGradientHessianKernel" : "HessianKernel", k, d);
+        if (rc) return rc;
     }
     const int64_t n = X->n, m = Y->n;
     const int64_t B = vflag + (kind == COVGRAM_BLOCK_HESSIAN ? 0 : (int64_t)d) + (hess ? (int64_t)d * d : 0);

@@ -1,6 +1,6 @@
 // block_fam.hip — compiled once per family (-DCOVGRAM_FAM=<covgram_family>, 11 / 12 = the composite pseudo-families): exports
-// launch_bm_family_<FAM> (gradient / value-gradient blocks) and, for the families with a Hessian MVM (EQ, RQ, Cauchy, IMQ, Dot,
-// ExponentialDot), launch_bmh_family_<FAM> (Hessian / value-gradient-Hessian blocks).
+// launch_bm_family_<FAM> (gradient / value-gradient blocks) and, for the families with a Hessian MVM (COVGRAM_HESS_FAMILIES,
+// hess_mvm.hpp), launch_bmh_family_<FAM> (Hessian / value-gradient-Hessian blocks).
 #include "block_matrix.hpp"
 
 #ifndef COVGRAM_FAM
@@ -13,7 +13,8 @@ namespace covgram {
 int CG_CAT(launch_bm_family_, COVGRAM_FAM)(const BlockMatArgs& a, int dtype) {
     return launch_bm_family<COVGRAM_FAM, false>(a, dtype);
 }
-#if COVGRAM_FAM == 0 || COVGRAM_FAM == 2 || COVGRAM_FAM == 4 || COVGRAM_FAM == 5 || COVGRAM_FAM == 7 || COVGRAM_FAM == 8
+#define CG_OR_FAM(name, n, arg) || COVGRAM_FAM == n
+#if 0 COVGRAM_HESS_FAMILIES(CG_OR_FAM, )
 int CG_CAT(launch_bmh_family_, COVGRAM_FAM)(const BlockMatArgs& a, int dtype) {
     return launch_bm_family<COVGRAM_FAM, true>(a, dtype);
 }

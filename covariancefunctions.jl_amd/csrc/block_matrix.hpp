@@ -20,6 +20,7 @@
 #pragma once
 #include "common.hpp"
 #include "profiles.hpp"
+#include "hess_mvm.hpp"   // COVGRAM_HESS_FAMILIES: the families of the Hessian kinds
 #include <type_traits>
 
 namespace covgram {

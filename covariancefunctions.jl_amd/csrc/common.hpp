@@ -305,7 +305,7 @@ struct covgram_ctx {
     int64_t last_grad_jsplit = 0; // column split of the last lane-per-row gradient launch (0: the last gradient MVM did not run it)
     int64_t last_hess_path = 0;   // 1: the last covgram_hess_mvm ran hess_mvm_kernel (0: none yet, or no columns / rows)
     int64_t last_matrix_path = 0; // covgram_matrix: route + 10 DM + 1000 VR (include/covgram.h, "last_matrix_path"); 0: none yet, or n m == 0
-    int64_t last_vgh_path = 0;    // 1: the last covgram_valgradhess_mvm ran vgh_mvm_kernel (0: none yet, or no columns / rows)
+    int64_t last_vgh_path = 0;    // 1: the last covgram_valgradhess_mvm ran hess_mvm_kernel<VGH = true> (0: none yet, or no columns / rows)
     int64_t last_block_matrix_path = 0; // covgram_block_matrix: (kind + 1) + 10 VR (include/covgram.h, "last_block_matrix_path"); 0: none yet, or an empty product
     int64_t last_mfma_lds = 0;   // the last matrix-core EQ MVM shared its column tiles through LDS
     // optional HIP-event bracketing of the dominant kernel of each MVM (bench.py's live roofline measurement)

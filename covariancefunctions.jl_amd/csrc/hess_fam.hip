@@ -1,5 +1,5 @@
-// hess_fam.hip — compiled once per family that has a Hessian MVM (-DCOVGRAM_FAM=<covgram_family>: EQ, RQ, Cauchy, IMQ, Dot,
-// ExponentialDot); exports launch_hess_family_<FAM>.
+// hess_fam.hip — compiled once per family of COVGRAM_HESS_FAMILIES (hess_mvm.hpp; -DCOVGRAM_FAM=<covgram_family>); exports
+// launch_hess_family_<FAM> (Hessian MVM) and launch_vgh_family_<FAM> (value-gradient-Hessian MVM).
 #include "hess_mvm.hpp"
 
 #ifndef COVGRAM_FAM
@@ -10,6 +10,9 @@ namespace covgram {
 #define CG_CAT2(a, b) a##b
 #define CG_CAT(a, b) CG_CAT2(a, b)
 int CG_CAT(launch_hess_family_, COVGRAM_FAM)(const HessArgs& a, int dtype) {
-    return launch_hess_family<COVGRAM_FAM>(a, dtype);
+    return launch_hess_family<COVGRAM_FAM, false>(a, dtype);
+}
+int CG_CAT(launch_vgh_family_, COVGRAM_FAM)(const HessArgs& a, int dtype) {
+    return launch_hess_family<COVGRAM_FAM, true>(a, dtype);
 }
 }  // namespace covgram

@@ -799,7 +799,7 @@ struct DPhi4<COVGRAM_EXPDOT, T> {
     static __device__ __forceinline__ void eval(T s, const KParams<T>&, T& f2, T& f3, T& f4) { f2 = cg_exp(s); f3 = f2; f4 = f2; }
 };
 
-// ---- (phi, phi', ..., phi'''') w.r.t. the pre-scaled argument: the full jet of the value-gradient-Hessian blocks (vgh_mvm.hpp), the
+// ---- (phi, phi', ..., phi'''') w.r.t. the pre-scaled argument: the full jet of the value-gradient-Hessian blocks (hess_mvm.hpp, VGH), the
 // profile's transcendentals evaluated once.  The families of DPhi4.
 template <int FAM, typename T>
 struct DPhi5;

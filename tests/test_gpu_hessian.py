@@ -212,6 +212,59 @@ def test_readme_shape_and_a_larger_one_on_a_row_subset(cg, n):
     run_case(cg, PROFILES[0], n, n, 16, F64, seed=80 + n, same=True, rows=row_subset(n, 16, rng))
 
 
+@pytest.mark.parametrize("i,dt,d,n,m,jsplit", [(0, F64, 3, 37, 29, 3), (0, F32, 5, 19, 23, 2), (4, F32, 5, 19, 23, 2)])
+def test_forced_column_split(cg, i, dt, d, n, m, jsplit):
+    """Option jsplit: partial slabs and the fixed-order reduce meet the same bar on all rows.  Three slabs in fp64 at d = 3; two in fp32
+    at d = 5, which is padded to 8: the padded lanes a >= d and the padding of the column records are live."""
+    cg.set_option("jsplit", jsplit)
+    try:
+        run_case(cg, PROFILES[i], n, m, d, dt, seed=90 + d)
+    finally:
+        cg.set_option("jsplit", 0)
+
+
+def abi_mvm(cg, n, m, d, a, y, alpha, beta):
+    """covgram_hess_mvm through the C ABI on device pointers, fp64 EQ with a lengthscale, lda = max(1, m d^2), ldy = max(1, n d^2); the
+    return code."""
+    from covgram import _ffi
+    from covgram.gramian import _Points
+    rng = np.random.default_rng(7)
+    k, kern = make_kernel(cg, PROFILES[0], d)
+    px = _Points(torch.from_numpy(rng.standard_normal((n, d))).cuda())
+    py = _Points(torch.from_numpy(rng.standard_normal((m, d))).cuda())
+    bd = d * d
+    rc = _ffi.lib().covgram_hess_mvm(px.ctx.bind_stream(), _ffi.kref(cg.require_hessian_spec(k, d)), px.handle, py.handle,
+                                     C.c_void_p(a.data_ptr()), max(1, m * bd), C.c_void_p(y.data_ptr()), max(1, n * bd), 1, alpha, beta,
+                                     _ffi.DEVICE)
+    torch.cuda.synchronize()
+    return rc
+
+
+def test_no_columns_scales_y_and_no_rows_writes_nothing(cg):
+    """m = 0: y <- beta y exactly (the reduce launch with no slabs), beta = 0 never reads y; n = 0: nothing is launched or written.
+    Either way the call succeeds and last_hess_path is 0 afterwards."""
+    from covgram import _ffi
+    rng = np.random.default_rng(95)
+    n, d = 5, 2
+    bd = d * d
+    a = torch.from_numpy(rng.standard_normal(4 * bd)).cuda()
+    run_case(cg, PROFILES[0], 6, 6, d, F64, seed=96)                      # leaves last_hess_path at 1
+    y0 = rng.standard_normal(n * bd)
+    y = torch.from_numpy(y0.copy()).cuda()
+    assert abi_mvm(cg, n, 0, d, a, y, 0.9, -0.4) == _ffi.OK
+    assert cg.get_info("last_hess_path") == 0
+    assert np.array_equal(y.cpu().numpy(), -0.4 * y0)
+    y = torch.full((n * bd,), NANV, dtype=torch.float64, device="cuda")
+    assert abi_mvm(cg, n, 0, d, a, y, 0.9, 0.0) == _ffi.OK
+    assert cg.get_info("last_hess_path") == 0
+    assert np.array_equal(y.cpu().numpy(), np.zeros(n * bd))
+    run_case(cg, PROFILES[0], 6, 6, d, F64, seed=96)
+    y = torch.from_numpy(y0.copy()).cuda()
+    assert abi_mvm(cg, 0, 4, d, a, y, 0.9, -0.4) == _ffi.OK
+    assert cg.get_info("last_hess_path") == 0
+    assert np.array_equal(y.cpu().numpy(), y0)
+
+
 def test_unsupported_kernels_and_dimensions_raise(cg):
     X = torch.randn(10, 3, dtype=torch.float64, device="cuda")
     a = torch.randn(90, dtype=torch.float64, device="cuda")

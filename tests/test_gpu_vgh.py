@@ -1,4 +1,4 @@
-"""Entry-wise parity of the value-gradient-Hessian-kernel Gramian MVM (covgram_valgradhess_mvm, csrc/vgh_mvm.hpp) with the fp64 numpy
+"""Entry-wise parity of the value-gradient-Hessian-kernel Gramian MVM (covgram_valgradhess_mvm, csrc/hess_mvm.hpp with VGH = true) with the fp64 numpy
 reference of tests/vgh_ref.py (itself pinned against torch.func in tests/test_vgh_host.py).  Case for case tests/test_gpu_hessian.py.
 
 Error measure, as there: for every checked entry  e = |b - ref| / (|alpha| absref + |beta| |y0|), absref = the same product with every
@@ -237,6 +237,59 @@ def test_forced_column_split(cg, i, dt, d):
         run_case(cg, PROFILES[i], 193, 131, d, dt, seed=90 + d)
     finally:
         cg.set_option("jsplit", 0)
+
+
+@pytest.mark.parametrize("i", [0, 4])
+def test_forced_column_split_fp32_padded_dimension(cg, i):
+    """jsplit = 2 in fp32 at d = 5, which is padded to 8 (the padded lanes a >= d and the padding of the column records are live),
+    n = 19, m = 23, all rows."""
+    cg.set_option("jsplit", 2)
+    try:
+        run_case(cg, PROFILES[i], 19, 23, 5, F32, seed=95)
+    finally:
+        cg.set_option("jsplit", 0)
+
+
+def abi_mvm(cg, n, m, d, a, y, alpha, beta):
+    """covgram_valgradhess_mvm through the C ABI on device pointers, fp64 EQ with a lengthscale, lda = max(1, m bd), ldy = max(1, n bd);
+    the return code."""
+    from covgram import _ffi
+    from covgram.gramian import _Points
+    rng = np.random.default_rng(7)
+    k, kern = make_kernel(cg, PROFILES[0], d)
+    px = _Points(torch.from_numpy(rng.standard_normal((n, d))).cuda())
+    py = _Points(torch.from_numpy(rng.standard_normal((m, d))).cuda())
+    bd = blk(d)
+    rc = _ffi.lib().covgram_valgradhess_mvm(px.ctx.bind_stream(), _ffi.kref(cg.require_vgh_spec(k, d)), px.handle, py.handle,
+                                            C.c_void_p(a.data_ptr()), max(1, m * bd), C.c_void_p(y.data_ptr()), max(1, n * bd), 1, alpha,
+                                            beta, _ffi.DEVICE)
+    torch.cuda.synchronize()
+    return rc
+
+
+def test_no_columns_scales_y_and_no_rows_writes_nothing(cg):
+    """m = 0: y <- beta y exactly (the reduce launch with no slabs), beta = 0 never reads y; n = 0: nothing is launched or written.
+    Either way the call succeeds and last_vgh_path is 0 afterwards."""
+    from covgram import _ffi
+    rng = np.random.default_rng(95)
+    n, d = 5, 2
+    bd = blk(d)
+    a = torch.from_numpy(rng.standard_normal(4 * bd)).cuda()
+    run_case(cg, PROFILES[0], 6, 6, d, F64, seed=96)                      # leaves last_vgh_path at 1
+    y0 = rng.standard_normal(n * bd)
+    y = torch.from_numpy(y0.copy()).cuda()
+    assert abi_mvm(cg, n, 0, d, a, y, 0.9, -0.4) == _ffi.OK
+    assert cg.get_info("last_vgh_path") == 0
+    assert np.array_equal(y.cpu().numpy(), -0.4 * y0)
+    y = torch.full((n * bd,), NANV, dtype=torch.float64, device="cuda")
+    assert abi_mvm(cg, n, 0, d, a, y, 0.9, 0.0) == _ffi.OK
+    assert cg.get_info("last_vgh_path") == 0
+    assert np.array_equal(y.cpu().numpy(), np.zeros(n * bd))
+    run_case(cg, PROFILES[0], 6, 6, d, F64, seed=96)
+    y = torch.from_numpy(y0.copy()).cuda()
+    assert abi_mvm(cg, 0, 4, d, a, y, 0.9, -0.4) == _ffi.OK
+    assert cg.get_info("last_vgh_path") == 0
+    assert np.array_equal(y.cpu().numpy(), y0)
 
 
 def test_unsupported_kernels_and_dimensions_raise(cg):
