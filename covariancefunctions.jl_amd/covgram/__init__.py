@@ -24,7 +24,8 @@ from .gramian import (Gramian, BlockGramian, HessianGramian, ValueGradientHessia
                       srange, gramian, mul_, get_ctx, set_option, get_info, kernel_time, SparseGramian, sparse, decay_radius,
                       BarnesHutFactorization, require_barneshut_spec)
 from .dist import ShardedGramian, shard_bounds
-from .solve import cg, minres, solve, toeplitz_solve, durbin, levinson, trench
+from .solve import (cg, mbcg, cg_tridiagonals, lanczos_quadrature, logdet, inv_quad_logdet, minres, solve, toeplitz_solve, durbin, levinson,
+                    trench)
 from .factorize import (cholesky, factorize, diagonal, CholeskyFactor, PivotedCholesky, pivoted_cholesky, PivotedCholeskyPreconditioner,
                         preconditioner)
 

@@ -24,6 +24,8 @@ OK, EINVAL, EUNSUPPORTED, EHIP, ENODEVICE, ENOMEM = 0, -1, -2, -3, -4, -5
 MATERNP_MAX_P = 8
 PIVCHOL_MAX_RANK = 1024   # COVGRAM_PIVCHOL_MAX_RANK
 COMM_ID_BYTES = 128
+BCG_SLAB, BCG_FIELDS = 64, 8   # COVGRAM_BCG_SLAB, COVGRAM_BCG_FIELDS
+BCG_RZ, BCG_TOL2, BCG_RR, BCG_ACTIVE, BCG_ITERS = range(5)   # COVGRAM_BCG_*: the fields of the batched CG state
 BLOCK_GRADIENT, BLOCK_VALUE_GRADIENT, BLOCK_HESSIAN, BLOCK_VALUE_GRADIENT_HESSIAN = range(4)   # kinds of covgram_block_matrix
 ABI_VERSION = 113   # COVGRAM_VERSION of the include/covgram.h these prototypes mirror
 
@@ -135,6 +137,10 @@ PROTOTYPES = {
     "covgram_toeplitz_destroy": (C.c_int, [_P]),
     "covgram_cg_step": (C.c_int, [_P, _I64, _I32, _P, _P, _P, _P, _P]),
     "covgram_cg_step_shifted": (C.c_int, [_P, _I64, _I32, _P, _P, _P, _P, _P, _P]),
+    "covgram_bcg_init": (C.c_int, [_P, _I64, _I64, _I32, _P, _I64, _P, _I64, _D, _D, _P, _P]),
+    "covgram_bcg_step": (C.c_int, [_P, _I64, _I64, _I32, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _I64]),
+    "covgram_bcg_update": (C.c_int, [_P, _I64, _I64, _I32, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _I64]),
+    "covgram_bcg_direction": (C.c_int, [_P, _I64, _I64, _I32, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _I64]),
     "covgram_toeplitz_durbin": (C.c_int, [_P, _P, _I64, _P, _I32, _I32]),
     "covgram_toeplitz_levinson": (C.c_int, [_P, _P, _P, _I64, _P, _I32, _I32]),
     "covgram_toeplitz_trench": (C.c_int, [_P, _P, _I64, _P, _I64, _I32, _I32]),

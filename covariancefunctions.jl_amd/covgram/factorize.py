@@ -223,6 +223,15 @@ class PivotedCholeskyPreconditioner(LazyOperator):
         """log det(L L' + D) (a 0-dim device tensor)."""
         return 2.0 * torch.log(self.R.diagonal()).sum() + torch.log(self.D).sum()
 
+    def sample(self, p: int, generator=None) -> torch.Tensor:
+        """(n, p) draws L g₁ + √D g₂ ~ N(0, L L' + D), g₁ and g₂ standard normal: the probes under which `logdet`'s preconditioned
+        estimate is unbiased.  `generator`: a torch.Generator (the draws are made on its device), or None."""
+        n, p = self.shape[0], int(p)
+        gdev = generator.device if generator is not None else self.device
+        g1 = torch.randn((self.rank, p), generator=generator, device=gdev, dtype=self.dtype).to(self.device)
+        g2 = torch.randn((n, p), generator=generator, device=gdev, dtype=self.dtype).to(self.device)
+        return self.factor.L @ g1 + self.D.sqrt()[:, None] * g2
+
     def to_dense(self):
         """The dense M^-1 = D^-1 - W W' (tests)."""
         return torch.diag(self.Dinv) - self.W @ self.W.T

@@ -7,6 +7,10 @@ the GPU.  Without a preconditioner the O(n) vector updates and the two dot produ
 diagonal term of G + σ²I and ‖r‖ ride along) — as torch ops they were eleven small launches, 45 us next to a 40 us MVM at
 n = 16384; with a preconditioner they stay torch ops on the same stream.  One host synchronisation per
 iteration (the convergence test), none inside the MVM.
+
+A block of right-hand sides goes through `mbcg`: p independent recurrences over ONE matrix right-hand-side MVM per iteration, their vector
+work and per-column stopping in covgram_bcg_* (csrc/bcg.hip).  The coefficients it logs are Lanczos coefficients: `logdet` and
+`inv_quad_logdet` (stochastic Lanczos quadrature) are built on the same solve.
 """
 from __future__ import annotations
 
@@ -71,7 +75,15 @@ def cg(A: LazyOperator, b: torch.Tensor, x0: Optional[torch.Tensor] = None, relt
 
     graph=True (small, launch-bound systems): `check_every` iterations — the MVM's kernels and the vector updates — are captured
     once into a HIP graph and replayed; the residual is read back between replays, so the solve may run up to
-    check_every − 1 iterations past the tolerance (they only refine x)."""
+    check_every − 1 iterations past the tolerance (they only refine x).
+
+    A matrix b (n, p) is solved by `mbcg`: p independent recurrences over one matrix right-hand-side MVM per iteration (graph=True is
+    not available for it)."""
+    if torch.is_tensor(b) and b.dim() == 2:
+        if graph:
+            raise ValueError("cg: graph=True is restricted to a vector right-hand side; the batched iteration of a matrix right-hand side "
+                             "(mbcg) is not captured")
+        return mbcg(A, b, x0, reltol, abstol, maxiter, precond, check_every)
     if graph:
         return _cg_graph(A, b, x0, reltol, abstol, maxiter, precond, max(1, int(check_every)))
     n = A.shape[0]
@@ -177,6 +189,188 @@ def _cg_graph(A, b, x0, reltol, abstol, maxiter, precond, check_every):
         it += 1
         resf = float(res)
     return x, {"iterations": it, "residual_norm": resf, "converged": resf <= tol, "graph": True}
+
+
+# ---- batched CG on a block of right-hand sides, and what its coefficients give: log det by stochastic Lanczos quadrature --------------
+def _rows(M: torch.Tensor) -> torch.Tensor:
+    """The (p, n) row-major tensor whose transpose is the (n, p) matrix M: column-major n x p for the library (no copy when M is the
+    transpose of a contiguous tensor, which is what every matrix `mul_` and the preconditioner return)."""
+    return M.t().contiguous()
+
+
+def mbcg(A: LazyOperator, B: torch.Tensor, x0: Optional[torch.Tensor] = None, reltol: float = 1e-8, abstol: float = 0.0,
+         maxiter: Optional[int] = None, precond=None, check_every: int = 8, lanczos: bool = False) -> Tuple[torch.Tensor, dict]:
+    """Solve A X = B for an (n, p) block of right-hand sides: p INDEPENDENT conjugate-gradient recurrences (the iteration of `cg`, per
+    column) that share one matrix right-hand-side `mul_` per iteration.  Column j stops — its x_j and r_j frozen — when
+    ‖r_j‖ ≤ max(reltol·‖r₀ⱼ‖, abstol); the solve ends when every column has, or after `maxiter` iterations.
+
+    The vector work of an iteration is covgram_bcg_step (one launch for columns that fit a workgroup's registers, three above), or with
+    a preconditioner covgram_bcg_update / `precond` on the whole block / covgram_bcg_direction; the diagonal of A = G + d is folded into
+    the step.  All scalars live on the device in fp64; the one host synchronisation is the read of the number of active columns every
+    `check_every` iterations (a finished column does no work meanwhile, so nothing runs past its tolerance).
+
+    Returns (X, info): "iterations" (the total), "column_iterations", "residual_norm" (per column, the recurrence's), "converged" and
+    "column_converged".  lanczos=True adds the CG coefficients "alpha", "beta" (iterations x p, fp64, 0 where a column was frozen), "rz0"
+    (r₀ⱼᵀM⁻¹r₀ⱼ) and "tridiagonals" (cg_tridiagonals)."""
+    n = A.shape[0]
+    if A.shape[0] != A.shape[1]:
+        raise _ffi.DimensionMismatch(_ffi.EINVAL, f"DimensionMismatch: mbcg needs a square operator, got {tuple(A.shape)}")
+    if not torch.is_tensor(B) or B.dim() != 2 or B.shape[0] != n:
+        raise _ffi.DimensionMismatch(_ffi.EINVAL, f"DimensionMismatch: B has shape {tuple(getattr(B, 'shape', ()))}, expected ({n}, p)")
+    if x0 is not None and tuple(x0.shape) != tuple(B.shape):
+        raise _ffi.DimensionMismatch(_ffi.EINVAL, f"DimensionMismatch: x0 has shape {tuple(x0.shape)}, expected {tuple(B.shape)}")
+    dev, dt, p = A.device, A.dtype, B.shape[1]
+    code = _dtype_code(dt)
+    Rt = torch.empty((p, n), dtype=dt, device=dev)             # every block is (p, n) row-major: column-major n x p, ld = n
+    Rt.copy_(B.t())
+    Xt = torch.zeros_like(Rt)
+    APt = torch.empty_like(Rt)
+    G, diag = _split_shift(A)
+    if diag is not None:
+        diag = diag.to(device=dev, dtype=dt).contiguous()
+        if diag.shape[0] != n:
+            G, diag = A, None
+    if x0 is not None:
+        Xt.copy_(x0.t())
+        A.mul_(APt.t(), Xt.t())
+        Rt -= APt
+    Zt = _rows(precond(Rt.t())) if precond is not None else Rt
+    Pt = Zt.clone()
+    maxiter = n if maxiter is None else int(maxiter)
+    check_every = max(1, int(check_every))
+    state = torch.zeros(max(p, 1) * (_ffi.BCG_FIELDS + 2 * _ffi.BCG_SLAB), dtype=torch.float64, device=dev)
+    nact = torch.zeros(1, dtype=torch.int32, device=dev)
+    alog = torch.zeros((max(maxiter, 1), p), dtype=torch.float64, device=dev) if lanczos else None
+    blog = torch.zeros_like(alog) if lanczos else None
+    lib, ctx, P = _ffi.lib(), get_ctx(dev), _ffi._P
+    ld = max(n, 1)
+    ptr = lambda t: P(t.data_ptr()) if t is not None else None
+    _ffi.check(lib.covgram_bcg_init(ctx.bind_stream(), n, p, code, ptr(Rt), ld, ptr(Zt), ld, float(reltol), float(abstol), ptr(state), ptr(nact)))
+    field = lambda f: state[f * p:(f + 1) * p]
+    rz0 = field(_ffi.BCG_RZ).clone() if lanczos else None
+    it = 0
+    active = int(nact) if n > 0 and p > 0 else 0
+    while it < maxiter and active > 0:
+        G.mul_(APt.t(), Pt.t())                                 # the hot path: one product for all p columns
+        if precond is None:
+            _ffi.check(lib.covgram_bcg_step(ctx.bind_stream(), n, p, code, ptr(Xt), ld, ptr(Rt), ld, ptr(Pt), ld, ptr(APt), ld, ptr(diag),
+                                            ptr(state), ptr(nact), ptr(alog), ptr(blog), it))
+        else:
+            _ffi.check(lib.covgram_bcg_update(ctx.bind_stream(), n, p, code, ptr(Xt), ld, ptr(Rt), ld, ptr(Pt), ld, ptr(APt), ld, ptr(diag),
+                                              ptr(state), ptr(alog), it))
+            Zt = _rows(precond(Rt.t()))
+            _ffi.check(lib.covgram_bcg_direction(ctx.bind_stream(), n, p, code, ptr(Rt), ld, ptr(Zt), ld, ptr(Pt), ld, ptr(state), ptr(nact),
+                                                 ptr(blog), it))
+        it += 1
+        if it % check_every == 0 or it == maxiter:
+            active = int(nact)                                  # the only synchronisation
+    host = state[:_ffi.BCG_FIELDS * p].cpu().reshape(_ffi.BCG_FIELDS, p)
+    iters = host[_ffi.BCG_ITERS].to(torch.int64)
+    conv = host[_ffi.BCG_RR] <= host[_ffi.BCG_TOL2]
+    info = {"iterations": it, "column_iterations": iters.tolist(), "residual_norm": host[_ffi.BCG_RR].sqrt(),
+            "converged": bool(conv.all()), "column_converged": conv.tolist()}
+    if lanczos:
+        info["alpha"], info["beta"], info["rz0"] = alog[:it].cpu(), blog[:it].cpu(), rz0.cpu()
+        info["tridiagonals"] = cg_tridiagonals(info["alpha"], info["beta"], iters)
+    return Xt.t(), info
+
+
+def cg_tridiagonals(alpha, beta, iters):
+    """The Lanczos matrices of p CG recurrences from their coefficients (alpha, beta: iterations x p; column j took iters[j] steps):
+    T_j = tridiag with  T[i, i] = 1/α_i + β_{i−1}/α_{i−1}  (the second term for i > 0)  and  T[i, i+1] = T[i+1, i] = √β_i / α_i,
+    of order iters[j] — or up to the first α_i = 0 (a recurrence that broke down or was frozen).  T_j is the projection of M^-1/2 A M^-1/2
+    onto the Krylov space of the (preconditioned) start residual.  Host, fp64: a list of p CPU tensors."""
+    alpha = torch.as_tensor(alpha).to(device="cpu", dtype=torch.float64)
+    alpha = alpha[:, None] if alpha.dim() == 1 else alpha
+    beta = torch.as_tensor(beta).to(device="cpu", dtype=torch.float64).reshape(alpha.shape)
+    p = alpha.shape[1]
+    iters = [int(v) for v in torch.as_tensor(iters).reshape(-1).tolist()]
+    if len(iters) != p:
+        raise _ffi.DimensionMismatch(_ffi.EINVAL, f"DimensionMismatch: {len(iters)} iteration counts for {p} columns")
+    out = []
+    for j in range(p):
+        m = min(iters[j], alpha.shape[0])
+        a, b = alpha[:m, j], beta[:m, j]
+        zero = torch.nonzero(a == 0).flatten()
+        if zero.numel():
+            m = int(zero[0])
+            a, b = a[:m], b[:m]
+        T = torch.zeros((m, m), dtype=torch.float64)
+        if m:
+            d = 1.0 / a
+            d[1:] += b[:-1] / a[:-1]
+            off = b[:-1].sqrt() / a[:-1]
+            T.diagonal().copy_(d)
+            T.diagonal(1).copy_(off)
+            T.diagonal(-1).copy_(off)
+        out.append(T)
+    return out
+
+
+def lanczos_quadrature(T: torch.Tensor, f) -> float:
+    """e₁ᵀ f(T) e₁ = Σ_k (first component of eigenvector k)² f(λ_k) of a symmetric (tridiagonal) T, by `eigh` on the host in fp64 — the
+    Gauss quadrature of the unit start vector's spectral measure.  An empty T gives 0."""
+    T = torch.as_tensor(T, dtype=torch.float64, device="cpu")
+    if T.shape[0] == 0:
+        return 0.0
+    lam, V = torch.linalg.eigh(T)
+    return float((V[0] ** 2 * f(lam)).sum())
+
+
+def _probes(A, probes, precond, generator):
+    n = A.shape[0]
+    if torch.is_tensor(probes):
+        if probes.dim() != 2 or probes.shape[0] != n:
+            raise _ffi.DimensionMismatch(_ffi.EINVAL, f"DimensionMismatch: probes have shape {tuple(probes.shape)}, expected ({n}, p)")
+        return probes.to(device=A.device, dtype=A.dtype)
+    p = int(probes)
+    if p < 1:
+        raise ValueError(f"logdet: probes = {probes} must be at least 1")
+    if precond is not None:
+        if not hasattr(precond, "sample") or not hasattr(precond, "logdet"):
+            raise TypeError("logdet: the preconditioner must offer sample(p, generator) and logdet() (PivotedCholeskyPreconditioner)")
+        return precond.sample(p, generator)
+    gdev = generator.device if generator is not None else A.device
+    Z = torch.randint(0, 2, (n, p), generator=generator, device=gdev)           # Rademacher: ±1
+    return (2 * Z - 1).to(device=A.device, dtype=A.dtype)
+
+
+def _slq(info, cols, precond):
+    """(estimate, values, stderr) of log det from the Lanczos matrices of the probe columns `cols` of an mbcg run."""
+    vals = torch.tensor([float(info["rz0"][j]) * lanczos_quadrature(info["tridiagonals"][j], torch.log) for j in cols], dtype=torch.float64)
+    base = float(precond.logdet()) if precond is not None else 0.0
+    stderr = float(vals.std(unbiased=True) / len(cols) ** 0.5) if len(cols) > 1 else float("nan")
+    return base + float(vals.mean()), vals, stderr
+
+
+def logdet(A: LazyOperator, probes=16, maxiter: Optional[int] = None, reltol: float = 1e-6, precond=None, generator=None):
+    """log det A of a symmetric positive definite lazy operator by stochastic Lanczos quadrature: with probes z_j,
+    log det A = log det M + tr log(M^-1/2 A M^-1/2) ≈ precond.logdet() + (1/p) Σ_j rz₀ⱼ · e₁ᵀ log(T_j) e₁, where T_j is the Lanczos matrix
+    of column j of ONE mbcg(A, Z, precond=precond) and rz₀ⱼ = z_jᵀM⁻¹z_j (= n for Rademacher probes without a preconditioner).
+    `probes`: an (n, p) tensor, or a count — Rademacher draws without a preconditioner, precond.sample(p) ~ N(0, M) with one (the
+    distribution under which the estimate is unbiased).  Returns (estimate, info): info["values"] the per-probe terms, "stderr" their
+    standard error, and the solve's info."""
+    Z = _probes(A, probes, precond, generator)
+    _, info = mbcg(A, Z, reltol=reltol, maxiter=maxiter, precond=precond, lanczos=True)
+    est, vals, stderr = _slq(info, range(Z.shape[1]), precond)
+    info.update(values=vals, stderr=stderr, probes=Z.shape[1])
+    return est, info
+
+
+def inv_quad_logdet(A: LazyOperator, b: torch.Tensor, probes=16, maxiter: Optional[int] = None, reltol: float = 1e-6, precond=None,
+                    generator=None):
+    """(bᵀA⁻¹b, log det A, x = A⁻¹b, info) — the two terms of a Gaussian process's negative log marginal likelihood — from ONE
+    mbcg on the block [b | Z]: column 0 is the solve, the probe columns give the log-determinant as in `logdet`."""
+    n = A.shape[0]
+    if not torch.is_tensor(b) or b.dim() != 1 or b.shape[0] != n:
+        raise _ffi.DimensionMismatch(_ffi.EINVAL, f"DimensionMismatch: b has shape {tuple(getattr(b, 'shape', ()))}, expected ({n},)")
+    Z = _probes(A, probes, precond, generator)
+    b = b.to(device=A.device, dtype=A.dtype)
+    X, info = mbcg(A, torch.cat([b[:, None], Z], dim=1), reltol=reltol, maxiter=maxiter, precond=precond, lanczos=True)
+    x = X[:, 0].contiguous()
+    est, vals, stderr = _slq(info, range(1, Z.shape[1] + 1), precond)
+    info.update(values=vals, stderr=stderr, probes=Z.shape[1])
+    return torch.dot(b, x), est, x, info
 
 
 def minres(A: LazyOperator, b: torch.Tensor, x0: Optional[torch.Tensor] = None, reltol: Optional[float] = None, abstol: float = 0.0,

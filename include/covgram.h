@@ -68,7 +68,9 @@ extern "C" {
                                covgram_decay_radius and the covgram_sparse_* handle (sparse(G, delta));
                                the covgram_bh_* handle (BarnesHutFactorization);
                                covgram_bh_taylor_moments and covgram_bh_taylor_mvm (taylor! on that handle);
-                               covgram_pivoted_cholesky and COVGRAM_PIVCHOL_MAX_RANK.
+                               covgram_pivoted_cholesky and COVGRAM_PIVCHOL_MAX_RANK;
+                               covgram_bcg_init, covgram_bcg_step, covgram_bcg_update, covgram_bcg_direction and the
+                               COVGRAM_BCG_* layout of their state (batched CG on a block of right-hand sides).
                                A binding checks covgram_version() against the header it mirrors at load time */
 
 typedef enum covgram_status {
@@ -492,6 +494,57 @@ int covgram_cg_step(covgram_ctx* ctx, int64_t n, int32_t dtype, void* x, void* r
  * last one leaves |r| = sqrt(rho') in scal[2 + 512] — the diagonal term and the residual norm cost no launch of their own (a graph-replayed
  * iteration at n = 16384 is launch-bound: tools/cg_rate.py).  diag: n device entries, or NULL (no shift).  scal: 2 + 512 + 1 elements. */
 int covgram_cg_step_shifted(covgram_ctx* ctx, int64_t n, int32_t dtype, void* x, void* r, void* p, void* Ap, void* scal, const void* diag);
+
+/* Batched CG: the vector work of ONE iteration of nrhs INDEPENDENT conjugate-gradient recurrences that share the caller's matrix
+ * right-hand-side product AP = G P (covgram_mvm & co. with nrhs columns) and stop column by column (covgram/solve.py: mbcg).  The
+ * recurrences are those of covgram_cg_step per column; their coefficients are the Lanczos coefficients of stochastic Lanczos
+ * quadrature (covgram/solve.py: cg_tridiagonals, logdet).  X, R, P, AP, Z: column-major n x nrhs DEVICE arrays of `dtype` with leading
+ * dimensions >= n (the layout of covgram_mvm); diag: n entries or NULL.
+ * state: COVGRAM_BCG_STATE_DOUBLES(nrhs) DEVICE doubles, fp64 whatever the vectors' type; field f of column j is
+ * state[f * nrhs + j]:
+ *   COVGRAM_BCG_RZ      rz_j = R_j . Z_j of the current direction          COVGRAM_BCG_TOL2    the absolute threshold on |r_j|^2
+ *   COVGRAM_BCG_RR      rr_j = R_j . R_j                                    COVGRAM_BCG_ACTIVE  1 while column j iterates, else 0
+ *   COVGRAM_BCG_ITERS   the iterations column j has taken
+ * and the rest (three more fields and two slabs of COVGRAM_BCG_SLAB workgroup partials per column) is scratch.
+ * n_active: ONE device int32, the number of active columns — the only word a caller needs to read back.
+ * alpha_log, beta_log: DEVICE doubles, row-major (iterations x nrhs), or NULL; a step writes row `it` (it >= 0).
+ *
+ * Update phase, after AP = G P:   AP_j += diag .* P_j (diag != NULL);  gamma_j = P_j . AP_j;
+ *     alpha_j = (active_j && rz_j != 0 && gamma_j != 0) ? rz_j / gamma_j : 0;  X_j += alpha_j P_j;  R_j -= alpha_j AP_j;  rr_j = R_j . R_j.
+ * Direction phase, Z = R without a preconditioner, else the caller's Z = M^-1 R:   rz'_j = R_j . Z_j;
+ *     beta_j = (active_j && rz_j != 0) ? rz'_j / rz_j : 0;  P_j = Z_j + beta_j P_j;  alpha_j, beta_j logged at row `it`;
+ *     for active columns rz_j <- rz'_j and iters_j += 1;  active_j &= rr_j > tol2_j;  n_active = the number of active columns.
+ * An inactive column is frozen: X_j, R_j, rr_j, rz_j are not written (bitwise unchanged), its logged coefficients are 0 and P_j = Z_j;
+ * the 0 / 0 guards are covgram_cg_step's, per column, so no NaN reaches X and a column with R = P = 0 stays exactly 0.
+ * Every sum runs in a fixed order (wave shuffles, LDS, then a per-column slab of workgroup partials that the NEXT launch reduces; no
+ * floating-point atomic), column j's outputs depend on column j's inputs alone: equal columns and repeated calls give equal bits.
+ *
+ *   covgram_bcg_init       rz_j = R_j . Z_j, rr_j = R_j . R_j, tol2_j = max(reltol^2 rr_j, abstol^2), active_j = rr_j > tol2_j,
+ *                          iters_j = 0, n_active (Z = R without a preconditioner).  One launch, one workgroup per column.
+ *   covgram_bcg_step       both phases with Z = R (rz' = rr: the second dot is free).  Columns of at most 16384 fp32 / 8192 fp64 entries
+ *                          whose addresses are all multiples of 16 bytes: ONE launch of nrhs workgroups, each holding its column of P, AP
+ *                          and R in registers.  Otherwise three launches on a (row blocks x columns) grid.
+ *   covgram_bcg_update     the update phase alone (two launches); rr_j is committed by the direction phase that follows.
+ *   covgram_bcg_direction  the direction phase alone with the caller's Z (two launches).
+ * n, nrhs >= 0, every leading dimension >= n, it >= 0, dtype F32 / F64 — else COVGRAM_EINVAL, checked before any device call.  n = 0 or
+ * nrhs = 0: nothing is done.  Nothing synchronises with the host. */
+#define COVGRAM_BCG_SLAB 64
+#define COVGRAM_BCG_RZ 0
+#define COVGRAM_BCG_TOL2 1
+#define COVGRAM_BCG_RR 2
+#define COVGRAM_BCG_ACTIVE 3
+#define COVGRAM_BCG_ITERS 4
+#define COVGRAM_BCG_FIELDS 8
+#define COVGRAM_BCG_STATE_DOUBLES(nrhs) ((int64_t)(nrhs) * (COVGRAM_BCG_FIELDS + 2 * COVGRAM_BCG_SLAB))
+int covgram_bcg_init(covgram_ctx* ctx, int64_t n, int64_t nrhs, int32_t dtype, const void* R, int64_t ldr, const void* Z, int64_t ldz,
+                     double reltol, double abstol, double* state, int32_t* n_active);
+int covgram_bcg_step(covgram_ctx* ctx, int64_t n, int64_t nrhs, int32_t dtype, void* X, int64_t ldx, void* R, int64_t ldr, void* P,
+                     int64_t ldp, void* AP, int64_t ldap, const void* diag, double* state, int32_t* n_active, double* alpha_log,
+                     double* beta_log, int64_t it);
+int covgram_bcg_update(covgram_ctx* ctx, int64_t n, int64_t nrhs, int32_t dtype, void* X, int64_t ldx, void* R, int64_t ldr, const void* P,
+                       int64_t ldp, void* AP, int64_t ldap, const void* diag, double* state, double* alpha_log, int64_t it);
+int covgram_bcg_direction(covgram_ctx* ctx, int64_t n, int64_t nrhs, int32_t dtype, const void* R, int64_t ldr, const void* Z, int64_t ldz,
+                          void* P, int64_t ldp, double* state, int32_t* n_active, double* beta_log, int64_t it);
 
 /* Y <- alpha * (F_1 ⊗ F_2 ⊗ ... ⊗ F_q) A + beta * Y, standard Kronecker order (F_1 = slowest index).
  * factors[i]: dense rows[i]×cols[i] column-major matrix with leading dimension lds[i] (device or host per loc).
