@@ -21,7 +21,7 @@ import torch
 
 from . import _ffi
 from . import kernels as K
-from .gramian import Gramian, LazyOperator, _dtype_code
+from .gramian import Gramian, LazyOperator, SpectralMixtureGramian, _dtype_code
 
 DEFAULT_MAX_CHOLESKY_SIZE = 2 ** 14     # src/gramian.jl:201
 DEFAULT_TOL = 1e-6                      # src/gramian.jl:202
@@ -67,6 +67,10 @@ class PivotedCholesky(LazyOperator):
 def diagonal(G: Gramian) -> torch.Tensor:
     """diag(G) for a square Gramian with x ≡ y: k(x_i, x_i) evaluated on the device (n kernel evaluations)."""
     n = G.shape[0]
+    if isinstance(G, SpectralMixtureGramian):                 # cos(0) exp(0) = 1 for every component: the constant sum of the weights
+        if not G.issymmetric():
+            raise ValueError("diagonal: a Gramian with x = y expected")
+        return torch.full((n,), float(G.w.sum()), dtype=G.dtype, device=G.device)
     tr = K.input_trait(G.k)
     if isinstance(tr, K.IsotropicInput):                      # phi(0) for every point
         v = Gramian(G.k, G.x[:1], G.x[:1]).to_dense()[0, 0]

@@ -388,6 +388,107 @@ class Gramian(LazyOperator):
         return sub
 
 
+class SpectralMixtureGramian(LazyOperator):
+    """Lazy Gramian of a spectral mixture Σ_q w_q Cosine(μ_q) ARD(EQ(), l_q) (src/stationary.jl:213-217), a GenericInput kernel in the
+    reference's terms: holds (k, x, y), the point handles and the covgram_sm handle with the mixture's parameters; `mul!` and
+    Matrix(G) are ONE fused pass each (covgram_sm_mvm / covgram_sm_matrix).  `gramian` builds it for exactly the kernels that
+    kernels.spectral_mixture_spec recognises and kernels.device_spec does not."""
+
+    def __init__(self, k, x, y=None, spec=None):
+        self.k = k
+        self.x = _as_points(x)
+        self.y = self.x if (y is None or y is x) else _as_points(y, device=self.x.device, dtype=self.x.dtype)
+        if self.x.shape[1] != self.y.shape[1]:
+            raise _ffi.DimensionMismatch(_ffi.EINVAL, f"inputs have to have the same length: {self.x.shape[1]}, {self.y.shape[1]}")
+        d = self.x.shape[1]
+        self.w, self.mu, self.inv_l = spec if spec is not None else K.require_sm_spec(k, d)   # refusals come before any device call
+        self.dtype, self.device = self.x.dtype, self.x.device
+        self.shape = (self.x.shape[0], self.y.shape[0])
+        self._px = _Points(self.x)
+        self._py = self._px if self.y is self.x else _Points(self.y)
+        self.handle = _ffi._P()
+        as_d = lambda v: np.ascontiguousarray(v, dtype=np.float64).ctypes.data_as(C.POINTER(C.c_double))
+        _ffi.check(_ffi.lib().covgram_sm_create(self._px.ctx.bind_stream(), C.byref(self.handle), int(self.w.shape[0]), int(d), as_d(self.w),
+                                                as_d(self.mu), as_d(self.inv_l), _dtype_code(self.dtype)))
+
+    def __del__(self):
+        try:
+            if self.handle:
+                _ffi.lib().covgram_sm_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+    @property
+    def T(self):
+        return SpectralMixtureGramian(self.k, self.y, self.x, (self.w, self.mu, self.inv_l))   # cos is even: k(y, x) = k(x, y)
+
+    adjoint = T
+
+    def issymmetric(self):
+        return self.x is self.y or (self.x.shape == self.y.shape and bool(torch.equal(self.x, self.y)))
+
+    def isposdef(self):
+        return self.issymmetric() and bool(np.all(self.w >= 0))
+
+    def isotropic(self) -> bool:
+        """covgram_sm_info's flag: every component has one lengthscale over all dimensions."""
+        iso = C.c_int32(0)
+        _ffi.check(_ffi.lib().covgram_sm_info(self.handle, None, None, None, C.byref(iso)))
+        return bool(iso.value)
+
+    def mul_(self, y, a, alpha=1.0, beta=0.0):
+        """y ← α G a + β y for a vector or a matrix a; β == 0 ⇒ y's previous contents (NaN included) are ignored."""
+        n, m = self.shape
+        a = _vec_arg(a, m, self.dtype, self.device, "a")
+        if y.shape[0] != n or y.dtype != self.dtype or tuple(y.shape[1:]) != tuple(a.shape[1:]):
+            raise _ffi.DimensionMismatch(_ffi.EINVAL, f"DimensionMismatch: y has shape {tuple(y.shape)}, expected ({n}, ...) of {self.dtype}")
+        self._px.ctx.bind_stream()
+        fn = _ffi.lib().covgram_sm_mvm
+        if a.dim() == 1:
+            a_c = a.contiguous()
+            y_c = y if y.is_contiguous() else y.contiguous()
+            _ffi.check(fn(self.handle, self._px.handle, self._py.handle, _ffi._P(a_c.data_ptr()), max(m, 1), _ffi._P(y_c.data_ptr()), max(n, 1), 1,
+                          float(alpha), float(beta), _ffi.DEVICE))
+            if y_c is not y:
+                y.copy_(y_c)
+            return y
+        p = a.shape[1]
+        if p == 0:                                             # no columns: nothing to do (the ABI requires nrhs >= 1)
+            return y
+        a_cm = a.t().contiguous()                              # (p, m) row-major == m×p column-major
+        direct = y.t().is_contiguous()
+        y_cm = y.t() if direct else y.t().contiguous()
+        _ffi.check(fn(self.handle, self._px.handle, self._py.handle, _ffi._P(a_cm.data_ptr()), max(m, 1), _ffi._P(y_cm.data_ptr()), max(n, 1), p,
+                      float(alpha), float(beta), _ffi.DEVICE))
+        if not direct:
+            y.copy_(y_cm.t())
+        return y
+
+    def to_dense(self):
+        """Matrix(G) on the device, with the per-pair arithmetic of the product."""
+        n, m = self.shape
+        buf = torch.empty((m, n), dtype=self.dtype, device=self.device)   # column-major n×m
+        if n * m:
+            self._px.ctx.bind_stream()
+            _ffi.check(_ffi.lib().covgram_sm_matrix(self.handle, self._px.handle, self._py.handle, _ffi._P(buf.data_ptr()), n, _ffi.DEVICE))
+        return buf.t()
+
+    def __getitem__(self, ij):
+        """G[i, j] = k(x[i], y[j]) and sub-block indexing, evaluated on the device from the sliced point sets."""
+        i, j = ij
+        xi = self.x[i] if not isinstance(i, int) else self.x[i:i + 1]
+        yj = self.y[j] if not isinstance(j, int) else self.y[j:j + 1]
+        sub = SpectralMixtureGramian(self.k, xi.reshape(-1, self.x.shape[1]), yj.reshape(-1, self.y.shape[1]), (self.w, self.mu, self.inv_l)).to_dense()
+        if isinstance(i, int) and isinstance(j, int):
+            return sub[0, 0]
+        if isinstance(i, int):
+            return sub[0]
+        if isinstance(j, int):
+            return sub[:, 0]
+        return sub
+
+
 BLOCK_MATRIX_MAX_D = 64     # covgram_block_matrix, gradient kinds: rows in registers (include/covgram.h)
 
 
@@ -1188,7 +1289,17 @@ class Fill(LazyOperator):
 # ----------------------------------------------------------------------------------------------
 def _first_column(k, x: torch.Tensor, y0: torch.Tensor) -> torch.Tensor:
     """k.(x, y0) for n points x against ONE point y0 — n kernel evaluations on the device."""
-    return Gramian(k, x, y0.reshape(1, -1)).to_dense()[:, 0].contiguous()
+    return _plain_gramian(k, x, y0.reshape(1, -1)).to_dense()[:, 0].contiguous()
+
+
+def _plain_gramian(k, x, y=None):
+    """The lazy Gramian without structure: the fused spectral-mixture operator exactly when k has no covgram_kernel encoding but is a
+    mixture the covgram_sm kernels take; otherwise Gramian (whose products raise UnsupportedKernel for a kernel without a device path)."""
+    if isinstance(k, K.AbstractKernel) and K.device_spec(k) is None:
+        spec = K.spectral_mixture_spec(k, _point_dim(x))
+        if spec is not None:
+            return SpectralMixtureGramian(k, x, y, spec)
+    return Gramian(k, x, y)
 
 
 def _transform_points(k, p: torch.Tensor) -> torch.Tensor:
@@ -1316,7 +1427,7 @@ def gramian(k, x=None, y=None, trait: Optional[K.InputTrait] = None):
         if periodic and isinstance(k, K.StationaryKernel):      # :186-189
             xt = _as_points(x, dev)
             return Circulant(_first_column(k, xt, xt[0]))
-        if isinstance(tr, (K.IsotropicInput, K.StationaryInput)) and K.device_spec(k) is not None:
+        if isinstance(tr, (K.IsotropicInput, K.StationaryInput)) and (K.device_spec(k) is not None or K.spectral_mixture_spec(k, 1) is not None):
             xt = _as_points(x, dev)
             if same:
                 return SymmetricToeplitz(_first_column(k, xt, xt[0]))          # k.(x[1], x)
@@ -1325,6 +1436,6 @@ def gramian(k, x=None, y=None, trait: Optional[K.InputTrait] = None):
                 vc = _first_column(k, xt, yt[0])                                  # k.(x, y[1])
                 vr = _first_column(k, yt, xt[0])                                  # k.(x[1], y)
                 return Toeplitz(vc, vr)
-        return Gramian(k, x, None if same else y)               # different step / GenericInput: plain Gramian
+        return _plain_gramian(k, x, None if same else y)        # different step / GenericInput: plain Gramian
 
-    return Gramian(k, x, None if same else y)
+    return _plain_gramian(k, x, None if same else y)

@@ -294,6 +294,25 @@ class CosineKernel(StationaryKernel):
 Cosine = Cos = CosineKernel
 
 
+def Spectral(w, mu, l):
+    """Spectral(w, μ, l) = prod((w, Cosine(μ), ARD(EQ(), l))) (src/stationary.jl:215): a Product of Constant(w), Cosine(μ) and the EQ
+    kernel under a scalar (Lengthscale) or per-dimension (ScaledInputKernel) lengthscale.  A weight of either sign is taken as it is
+    (Constant(w, check = False)): a mixture may carry negative weights."""
+    return Product((Constant(w, False), CosineKernel(mu), ARD(ExponentiatedQuadratic(), l)))
+
+
+def SpectralMixture(w, mu, l):
+    """SpectralMixture(w, μ, l) = sum(Spectral.(w, μ, l)) (src/stationary.jl:216): w of length Q, μ and l with one entry (a number or a
+    length-d vector) per component."""
+    w = list(np.atleast_1d(np.asarray(w, dtype=np.float64)))
+    if not (len(mu) == len(w) and len(l) == len(w)):
+        raise _ffi.DimensionMismatch(_ffi.EINVAL, f"SpectralMixture: {len(w)} weights, {len(mu)} frequencies and {len(l)} lengthscales")
+    return Sum(tuple(Spectral(wq, mq, lq) for wq, mq, lq in zip(w, mu, l)))
+
+
+SM = SpectralMixture
+
+
 class Periodic(StationaryKernel):
     """Periodic(k)(τ) = k((2 sin(πτ))²) for 1-D inputs (src/transformation.jl:54-65): the isotropic kernel k on the circle
     embedding e(x) = (cos 2πx, sin 2πx), since |e(x) − e(y)|² = 4 sin²(π(x − y))."""
@@ -737,6 +756,126 @@ def require_device_spec(k):
             _ffi.EUNSUPPORTED,
             f"{type(k).__name__} has input_trait {input_trait(k)!r} / no compiled device profile; the reference would run its "
             "generic threaded loop (src/gramian.jl:78-87) here — this engine has no CPU fallback")
+    return spec
+
+
+# ----------------------------------------------------------------------------------------------
+# spectral mixtures: Σ_q w_q cos(2π μ_q·r) exp(−½ Σ_k (r_k / l_qk)²), the parameters of covgram_sm_create
+# ----------------------------------------------------------------------------------------------
+SM_MAX_COMPONENTS, SM_MAX_D = _ffi.SM_MAX_COMPONENTS, _ffi.SM_MAX_D
+
+
+def _sm_eq_factor(k):
+    """Squared inverse lengthscale(s) of an EQ factor — a number (isotropic) or a length-d vector — or None if k is not one:
+    EQ(), Lengthscale(EQ, l) (nesting multiplies) or ScaledInputKernel(EQ-factor, diagonal U)."""
+    if isinstance(k, ExponentiatedQuadratic):
+        return 1.0
+    if isinstance(k, Lengthscale):
+        inner = _sm_eq_factor(k.k)
+        return None if inner is None else inner / k.l ** 2
+    if isinstance(k, ScaledInputKernel):
+        inner = _sm_eq_factor(k.k)
+        if inner is None or not k.diagonal or np.ndim(inner) != 0:
+            return None
+        return inner * k.U ** 2
+    return None
+
+
+def _sm_term(k, d):
+    """(w, mu[d], inv_l2[d]) of one term — a Product, or a bare factor, of Constants, at most one Cosine and EQ factors — or None."""
+    w, mu, il2 = 1.0, None, np.zeros(d)
+    factors = []
+
+    def flatten(f):                                          # a * b * c is Product((Product((a, b)), c))
+        if isinstance(f, Product):
+            for a in f.args:
+                flatten(a)
+        else:
+            factors.append(f)
+    flatten(k)
+    for f in factors:
+        if isinstance(f, Constant):
+            w *= f.c
+        elif isinstance(f, CosineKernel):
+            if mu is not None or f.c.size not in (1, d):
+                return None
+            mu = np.broadcast_to(f.c, (d,)).astype(np.float64)
+        else:
+            e = _sm_eq_factor(f)
+            if e is None or (np.ndim(e) != 0 and np.size(e) != d):
+                return None
+            il2 = il2 + e
+    return w, (np.zeros(d) if mu is None else mu), il2
+
+
+def _sm_dim(k):
+    """The dimension a mixture's own parameters fix (the length of a vector-valued c or U), 1 if they are all scalars, None if they disagree."""
+    dims = set()
+
+    def walk(f):
+        if isinstance(f, (Sum, Product)):
+            for a in f.args:
+                walk(a)
+        elif isinstance(f, CosineKernel) and f.c.size > 1:
+            dims.add(int(f.c.size))
+        elif isinstance(f, ScaledInputKernel):
+            if f.diagonal:
+                dims.add(int(f.U.size))
+            walk(f.k)
+        elif isinstance(f, Lengthscale):
+            walk(f.k)
+    walk(k)
+    return None if len(dims) > 1 else (dims.pop() if dims else 1)
+
+
+def spectral_mixture_spec(k, d=None):
+    """(w[Q], mu[Q, d], inv_l[Q, d]) as float64 arrays if k is a spectral mixture the fused kernels of covgram_sm_mvm take, else None.
+
+    Accepted: a Sum (nested Sums are flattened) of terms, or one term; a term is a Product (or a bare factor) of any number of
+    Constants (they multiply into w), at most one Cosine (a scalar c broadcasts to d; none: μ = 0) and any number of EQ factors —
+    EQ(), Lengthscale(EQ, l), ScaledInputKernel(EQ, diagonal U) — whose squared inverse lengthscales add (none: inv_l = 0).
+    Anything else (a non-diagonal U, Power, other profiles, two Cosines in a term), lengths that disagree with d, Q > 32 or d > 16
+    give None.  Products are not distributed over Sums.  d = None: the dimension the parameters themselves fix (1 if all are scalars)."""
+    if not isinstance(k, AbstractKernel):
+        return None
+    if d is None:
+        d = _sm_dim(k)
+        if d is None:
+            return None
+    d = int(d)
+    if not 1 <= d <= SM_MAX_D:
+        return None
+    terms = []
+
+    def flatten(f):
+        if isinstance(f, Sum):
+            for a in f.args:
+                flatten(a)
+        else:
+            terms.append(f)
+    flatten(k)
+    if not 1 <= len(terms) <= SM_MAX_COMPONENTS:
+        return None
+    out = []
+    for t in terms:
+        r = _sm_term(t, d)
+        if r is None:
+            return None
+        out.append(r)
+    w = np.array([r[0] for r in out], dtype=np.float64)
+    mu = np.stack([r[1] for r in out]).astype(np.float64)
+    inv_l = np.sqrt(np.stack([r[2] for r in out]).astype(np.float64))
+    return w, mu, inv_l
+
+
+def require_sm_spec(k, d=None):
+    spec = spectral_mixture_spec(k, d)
+    if spec is None:
+        raise _ffi.UnsupportedKernel(
+            _ffi.EUNSUPPORTED,
+            f"{type(k).__name__} is not a spectral mixture with a device path: a Sum of at most {SM_MAX_COMPONENTS} terms, each a Product of "
+            f"Constants, at most one Cosine and EQ factors under Lengthscale or a diagonal ScaledInputKernel, on points of d <= {SM_MAX_D} "
+            f"dimensions (here d = {d}); products are not distributed over sums")
     return spec
 
 

@@ -750,4 +750,46 @@ function BarnesHutFactorization(k, x, y = x, D = nothing; θ::Real = 1 / 4, leaf
 end
 BarnesHutFactorization(G::Gramian; θ::Real = 1 / 4, leafsize::Int = 16) = BarnesHutFactorization(G.k, G.x, G.y; θ = θ, leafsize = leafsize)
 
+# --- src/stationary.jl:213-217: SpectralMixture(w, μ, l) = Σ_q w_q Cosine(μ_q) ARD(EQ(), l_q) -> covgram_sm_* (one fused pass) --------
+# The kernel is GenericInput in the reference (its factors mix two traits), so it has no CKernel encoding: the handle carries the
+# parameters.  w: Q weights, μ and invl: d × Q (column q = component q, which is the library's row-major Q × d), invl = 1 ./ l.
+const SM_MAX_COMPONENTS, SM_MAX_D = 32, 16   # COVGRAM_SM_MAX_COMPONENTS, COVGRAM_SM_MAX_D
+mutable struct DeviceSpectralMixture{T} <: AbstractMatrix{T}
+    handle::Ptr{Cvoid}
+    X::Points; Y::Points
+    n::Int; m::Int
+    w::Vector{Float64}; μ::Matrix{Float64}; invl::Matrix{Float64}
+    function DeviceSpectralMixture(w::AbstractVector, μ::AbstractMatrix, invl::AbstractMatrix, x, y, ::Type{T}) where {T <: DevFloat}
+        size(μ) == size(invl) && size(μ, 2) == length(w) || throw(DimensionMismatch("SpectralMixture: μ and invl must be d × Q"))
+        wd = Vector{Float64}(w); μd = Matrix{Float64}(μ); ld = Matrix{Float64}(invl)
+        X = points(x, T); Y = x === y ? X : points(y, T)
+        h = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ccall((:covgram_sm_create, libcovgram), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32),
+                    ctx(), h, length(wd), size(μd, 1), wd, μd, ld, T === Float32 ? Int32(0) : Int32(1)))
+        S = new{T}(h[], X, Y, length(x), length(y), wd, μd, ld)
+        finalizer(q -> ccall((:covgram_sm_destroy, libcovgram), Cint, (Ptr{Cvoid},), q.handle), S)
+        S
+    end
+end
+Base.size(S::DeviceSpectralMixture) = (S.n, S.m)
+function sm_isotropic(S::DeviceSpectralMixture)
+    q = Ref{Int32}(0); d = Ref{Int32}(0); dt = Ref{Int32}(0); iso = Ref{Int32}(0)
+    check(ccall((:covgram_sm_info, libcovgram), Cint, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}, Ref{Int32}, Ref{Int32}), S.handle, q, d, dt, iso))
+    iso[] != 0
+end
+function LinearAlgebra.mul!(y::StridedVecOrMat{T}, S::DeviceSpectralMixture{T}, a::StridedVecOrMat{T}, α::Real = 1, β::Real = 0) where {T <: DevFloat}
+    size(a, 1) == S.m && size(y, 1) == S.n && size(y, 2) == size(a, 2) || throw(DimensionMismatch("mul!: size mismatch"))
+    size(a, 2) == 0 && return y                        # no columns: nothing to do (the ABI requires nrhs >= 1)
+    check(ccall((:covgram_sm_mvm, libcovgram), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int32, Float64, Float64, Int32),
+                S.handle, S.X.handle, S.Y.handle, a, max(stride(a, 2), S.m), y, max(stride(y, 2), S.n), size(a, 2), Float64(α), Float64(β), HOST))
+    return y
+end
+function Base.Matrix(S::DeviceSpectralMixture{T}) where {T <: DevFloat}
+    out = Matrix{T}(undef, S.n, S.m)
+    check(ccall((:covgram_sm_matrix, libcovgram), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32),
+                S.handle, S.X.handle, S.Y.handle, out, max(S.n, 1), HOST))
+    out
+end
+Base.getindex(S::DeviceSpectralMixture, i::Integer, j::Integer) = Matrix(S)[i, j]   # (for show and tests; not a hot path)
+
 end # module

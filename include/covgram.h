@@ -70,7 +70,8 @@ extern "C" {
                                covgram_bh_taylor_moments and covgram_bh_taylor_mvm (taylor! on that handle);
                                covgram_pivoted_cholesky and COVGRAM_PIVCHOL_MAX_RANK;
                                covgram_bcg_init, covgram_bcg_step, covgram_bcg_update, covgram_bcg_direction and the
-                               COVGRAM_BCG_* layout of their state (batched CG on a block of right-hand sides).
+                               COVGRAM_BCG_* layout of their state (batched CG on a block of right-hand sides);
+                               the covgram_sm_* handle (SpectralMixture Gramians: one fused product and Matrix(G)).
                                A binding checks covgram_version() against the header it mirrors at load time */
 
 typedef enum covgram_status {
@@ -585,6 +586,37 @@ int covgram_lowrank_mvm(covgram_ctx* ctx, const void* U, int64_t ldu, const void
 #define COVGRAM_PIVCHOL_MAX_RANK 1024
 int covgram_pivoted_cholesky(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, int32_t max_rank, double tol,
                              void* L, int64_t ldl, int32_t* piv, void* dres, int32_t* rank);
+
+/* ---- SpectralMixture(w, mu, l) = sum_q w_q Cosine(mu_q) ARD(EQ(), l_q) (src/stationary.jl:213-217): the Gramian
+ *     G_ij = sum_q w_q cos(2 pi mu_q . (x_i - y_j)) exp(-1/2 sum_k ((x_ik - y_jk) inv_l_qk)^2)
+ * in ONE pass over the pairs (csrc/sm.hip).  The kernel mixes two input traits (c . r and |r|^2) and is GenericInput in the reference's
+ * terms, so it has no covgram_kernel encoding: a handle carries its parameters instead.
+ * covgram_sm_create: w[ncomp], mu and inv_l ncomp x d row-major, HOST arrays of doubles (the only copy from the host on this path);
+ *   they are rounded ONCE to `dtype` here.  inv_l = 0 is a component without an EQ factor, mu = 0 one without a Cosine; weights may
+ *   have either sign.  ncomp < 1, d < 1, a negative inv_l or a non-finite parameter: COVGRAM_EINVAL; ncomp > COVGRAM_SM_MAX_COMPONENTS
+ *   or d > COVGRAM_SM_MAX_D: COVGRAM_EUNSUPPORTED naming the limits.  No kernel is launched.
+ * covgram_sm_info: any output pointer may be NULL; isotropic = 1 when every component has one inverse lengthscale over all dimensions
+ *   (what Spectral(w, mu, l::Real) gives): the kernels then scale the pair's shared |x - y|^2 instead of its d squared differences.
+ * covgram_sm_mvm: y <- alpha G a + beta y with the semantics of covgram_mvm: column-major a (m x nrhs, lda >= m) and y (n x nrhs,
+ *   ldy >= n), loc applies to both; beta == 0 never reads y; m == 0 gives y <- beta y, n == 0 returns at once; a and y may overlap in
+ *   any way (a is then read from a private copy); any nrhs >= 1 (four right-hand sides share one pass over the pairs).  X and Y must
+ *   belong to the handle's ctx and have its dtype and its d (COVGRAM_EINVAL otherwise).  Differences are direct, x_ik - y_jk in the
+ *   points' precision: no centring, no expanded form, no radius gate.  With loc == DEVICE the product is stream-ordered, allocates
+ *   nothing after the first call of a shape (workspace of the ctx) and never synchronises: a captured graph may contain it.
+ *   Column-split partial sums are added in a fixed order, no atomics: bit-identical from run to run.
+ * covgram_sm_matrix: out[i + j ldo] = G_ij with the same per-pair arithmetic, column-major, ldo >= n; rows n <= i < ldo of out are
+ *   never touched, with loc == HOST (a staged tile copied back column by column) as with loc == DEVICE.  n m == 0: nothing is written.
+ * Option "time_kernels" brackets the pair kernel(s) of a call. */
+typedef struct covgram_sm covgram_sm;   /* device-resident parameters of one mixture */
+#define COVGRAM_SM_MAX_COMPONENTS 32
+#define COVGRAM_SM_MAX_D 16
+int covgram_sm_create(covgram_ctx* ctx, covgram_sm** out, int32_t ncomp, int32_t d, const double* w, const double* mu, const double* inv_l,
+                      int32_t dtype);
+int covgram_sm_info(const covgram_sm* S, int32_t* ncomp, int32_t* d, int32_t* dtype, int32_t* isotropic);
+int covgram_sm_mvm(covgram_sm* S, const covgram_points* X, const covgram_points* Y, const void* a, int64_t lda, void* y, int64_t ldy,
+                   int32_t nrhs, double alpha, double beta, int32_t loc);
+int covgram_sm_matrix(covgram_sm* S, const covgram_points* X, const covgram_points* Y, void* out, int64_t ldo, int32_t loc);
+int covgram_sm_destroy(covgram_sm* S);
 
 /* Test hook: the double-precision parameter block handed to the device kernels for `k`
  * (out45[0..8] = gamma, gamma^2, scale, param, c0, 2p+1, Taylor bound, d1, d2; then the MaternP tables
