@@ -388,6 +388,148 @@ class Gramian(LazyOperator):
         return sub
 
 
+# ----------------------------------------------------------------------------------------------
+# hyper-parameter gradients of bilinear forms (include/covgram.h: covgram_bilinear_grad)
+# ----------------------------------------------------------------------------------------------
+BILINEAR_MAX_NVEC, BILINEAR_MAX_D = _ffi.BILINEAR_MAX_NVEC, _ffi.BILINEAR_MAX_D
+
+
+def _bilinear_term(k):
+    """(spec, rules) of one simple isotropic term: the covgram_kernel the device runs and, per leaf of hyperparameters(k) in its
+    order, the chain rule ("scale", power, c) | ("l", l) | ("param",).  Raises UnsupportedKernel naming what is not supported."""
+    rules = []
+    def unsupported(what):
+        return _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"bilinear_gradient: {what} is not supported (simple isotropic kernels and Sums of them only)")
+    def walk(node, power):
+        if isinstance(node, K.Product):
+            rest = [a for a in node.args if not isinstance(a, K.Constant)]
+            if len(rest) != 1:
+                raise unsupported("a Product of two non-constant kernels" if len(rest) > 1 else "a Product of Constants")
+            for a in node.args:
+                if isinstance(a, K.Constant):
+                    rules.append(("scale", power, a.c))
+                else:
+                    walk(a, power)
+        elif isinstance(node, K.Power):
+            if node.p < 1:
+                raise unsupported(f"Power with exponent {node.p}")
+            walk(node.k, power * node.p)
+        elif isinstance(node, K.Lengthscale):
+            walk(node.k, power)
+            rules.append(("l", node.l))
+        elif isinstance(node, (K.DotProductKernel,)):
+            raise unsupported(f"the dot-product kernel {type(node).__name__}")
+        elif isinstance(node, K.Matern) and not (float(node.nu - 0.5).is_integer() and 0 <= int(node.nu - 0.5) <= _ffi.MATERNP_MAX_P):
+            raise unsupported(f"Matern with real nu = {node.nu}")
+        elif type(node) in K._OWN_PARAMETER:
+            rules.append(("param",))
+        elif isinstance(node, K._NO_PARAMETER):
+            pass
+        else:
+            raise unsupported(type(node).__name__)
+    walk(k, 1)
+    spec = K._simple_spec(k)
+    if spec is None or spec.trait != _ffi.ISOTROPIC:
+        raise unsupported(type(k).__name__)
+    return spec, rules
+
+
+def _bilinear_plan(k):
+    """Terms of `k` (a simple kernel, or a Sum of simple kernels and Constants, nested Sums flattened in walk order)."""
+    if isinstance(k, K.Sum):
+        return [t for a in k.args for t in _bilinear_plan(a)]
+    if isinstance(k, K.Constant):
+        return [(None, [("const", k.c)])]
+    return [_bilinear_term(k)]
+
+
+def bilinear_chain_rules(rules, out, scaled=None):
+    """The host chain rules of bilinear_gradient for one term: `out` = the numbers of covgram_bilinear_grad (fp64), `rules` from
+    _bilinear_term, `scaled` = the diagonal ScaledInputKernel in front of the term (out is then per dimension, on the transformed
+    points).  Returns the term's gradient entries in hyperparameters order (the ARD entries last)."""
+    out = [float(v) for v in out]
+    ssum = math.fsum(out[2:])
+    g = []
+    for r in rules:
+        if r[0] == "scale":
+            g.append(r[1] * out[0] / r[2])                     # k ∝ c^power
+        elif r[0] == "l":
+            g.append(-2.0 / r[1] * ssum)                       # k = f(s / l²)
+        elif r[0] == "param":
+            g.append(out[1])
+        else:                                                  # a Constant term of a Sum: Σ W
+            g.append(out[0])
+    if scaled is not None:
+        if scaled.l is not None:
+            g += [-2.0 / float(l) * out[2 + c] for c, l in enumerate(scaled.l)]
+        else:                                                  # s = Σ_c (U_c Δ_c)²: ∂/∂U_c = (2 / U_c) (∂k/∂s) (U_c Δ_c)²
+            g += [(2.0 / float(u) * out[2 + c]) if u != 0 else 0.0 for c, u in enumerate(scaled.U)]
+    return g
+
+
+def bilinear_gradient(G, U, A):
+    """(value, grad) of the bilinear form Σ_t U[:, t]ᵀ G A[:, t] = Σ_ij W_ij k(x_i, y_j), W = U Aᵀ, with respect to the
+    hyper-parameters of the kernel G was built from, in ONE fused pass over the pairs per term (csrc/bilin_grad.hip): W is formed per
+    pair in registers, nothing of size n × m exists.  `G` is the Gramian of gramian(k, x[, y]); U is (n,) or (n, nvec), A (m,) or
+    (m, nvec).  `grad` is a float64 CPU tensor in hyperparameters(k) order, `value` a float64 0-dim CPU tensor.
+
+    The device returns, per term, out[0] = Σ W k, out[1] = Σ W ∂k/∂param and out[2 + c] = Σ W (∂k/∂s)(x_c − y_c)² (one number Σ W (∂k/∂s) s
+    without ARD); the chain rules are applied here (bilinear_chain_rules):
+        ∂/∂scale = power · out[0] / scale          (Constant(c) · k under Power: k ∝ c^power)
+        ∂/∂l     = −(2 / l) Σ_c out[2 + c]         (Lengthscale; nested lengthscales each get this with their own l)
+        ∂/∂param = out[1]                          (RQ α, γ-exponential γ, IMQ c)
+        ∂/∂l_c   = −(2 / l_c) out[2 + c]           (ARD(k, l): on the points as gramian pre-scaled them; ScaledInputKernel(k, U) stores
+                                                    the multipliers: ∂/∂U_c = +(2 / U_c) out[2 + c])
+    A Sum of such terms takes one launch per term, gradients concatenate; a Constant term's derivative is Σ W.  More than 32 columns
+    run in chunks of 32 summed in fp64.  Everything else — a Product of two non-constant kernels, dot-product kernels, Matérn with real
+    ν, spectral mixtures, block Gramians, Toeplitz / Kronecker / sparse / Barnes–Hut operators, ShardedGramian — raises
+    UnsupportedKernel by name before any device call."""
+    if type(G) is not Gramian:
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"bilinear_gradient: {type(G).__name__} is not supported (the Gramian of gramian(k, x[, y]) only)")
+    scaled = getattr(G, "scaled_input", None)
+    if scaled is not None and not scaled.diagonal:
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, "bilinear_gradient: ScaledInputKernel with a full matrix U is not supported")
+    plan = _bilinear_plan(G.k)
+    if scaled is not None and (len(plan) != 1 or plan[0][0] is None):
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, "bilinear_gradient: ARD over a Sum is not supported")
+    n, m = G.shape
+    d = G.x.shape[1]
+    if d > BILINEAR_MAX_D:
+        raise _ffi.DimensionMismatch(_ffi.EINVAL, f"bilinear_gradient: d = {d} exceeds {BILINEAR_MAX_D}")
+    U = _vec_arg(U, n, G.dtype, G.device, "U")
+    A = _vec_arg(A, m, G.dtype, G.device, "A")
+    U = U[:, None] if U.dim() == 1 else U
+    A = A[:, None] if A.dim() == 1 else A
+    if U.dim() != 2 or A.dim() != 2 or U.shape[1] != A.shape[1] or U.shape[1] < 1:
+        raise _ffi.DimensionMismatch(_ffi.EINVAL, f"DimensionMismatch: U has shape {tuple(U.shape)}, A {tuple(A.shape)}: equal column counts expected")
+    nvec = U.shape[1]
+    per_dim = 1 if scaled is not None else 0
+    nout = 2 + (d if per_dim else 1)
+    Ut, At = U.t().contiguous(), A.t().contiguous()            # (nvec, n) row-major == n × nvec column-major
+    lib = _ffi.lib()
+    ctx = G._px.ctx.bind_stream()
+    py = None if G._py is G._px else G._py.handle
+    value, grad = 0.0, []
+    for spec, rules in plan:
+        if spec is None:                                       # Constant term c: value c Σ W, derivative Σ W = Σ_t (1ᵀu_t)(1ᵀa_t)
+            sw = float((U.sum(0).double() * A.sum(0).double()).sum())
+            out = [sw] + [0.0] * (nout - 1)
+            value += rules[0][1] * sw
+        else:
+            acc = torch.zeros(nout, dtype=torch.float64)
+            for c0 in range(0, nvec, BILINEAR_MAX_NVEC):
+                nv = min(BILINEAR_MAX_NVEC, nvec - c0)
+                o = torch.empty(nout, dtype=torch.float64, device=G.device)
+                _ffi.check(lib.covgram_bilinear_grad(ctx, _ffi.kref(spec), G._px.handle, py, _ffi._P(Ut[c0:].data_ptr()), max(n, 1),
+                                                     _ffi._P(At[c0:].data_ptr()), max(m, 1), nv, per_dim,
+                                                     C.cast(o.data_ptr(), C.POINTER(C.c_double)), _ffi.DEVICE))
+                acc += o.cpu()
+            out = acc.tolist()
+            value += out[0]
+        grad += bilinear_chain_rules(rules, out, scaled)
+    return torch.tensor(value, dtype=torch.float64), torch.tensor(grad, dtype=torch.float64)
+
+
 class SpectralMixtureGramian(LazyOperator):
     """Lazy Gramian of a spectral mixture Σ_q w_q Cosine(μ_q) ARD(EQ(), l_q) (src/stationary.jl:213-217), a GenericInput kernel in the
     reference's terms: holds (k, x, y), the point handles and the covgram_sm handle with the mixture's parameters; `mul!` and
@@ -1374,7 +1516,10 @@ def gramian(k, x=None, y=None, trait: Optional[K.InputTrait] = None):
         px = _as_points(x)
         py = px if same else _as_points(y, device=px.device, dtype=px.dtype)
         tx = _transform_points(k, px)
-        return gramian(k.k, tx, None if same else _transform_points(k, py))
+        g = gramian(k.k, tx, None if same else _transform_points(k, py))
+        if isinstance(k, K.ScaledInputKernel) and type(g) is Gramian:
+            g.scaled_input = k                                  # bilinear_gradient's chain rule to the entries of U / l
+        return g
     if isinstance(k, K.NeuralNetwork) or (isinstance(k, K.GradientKernel) and isinstance(k.k, K.NeuralNetwork)):
         nn = k if isinstance(k, K.NeuralNetwork) else k.k          # src/mercer.jl:82-85 on normalised augmented inputs
         px = _as_points(x)

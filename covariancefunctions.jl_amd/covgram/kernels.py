@@ -331,10 +331,11 @@ class ScaledInputKernel(AbstractKernel):
     """ScaledInputKernel(k, U)(x, y) = k(U x, U y) (src/transformation.jl:71-79); `gramian` pre-multiplies the points once
     (:82-90).  ARD(k, l) (:42-46) is the diagonal case U = Diagonal(1 ./ l)."""
 
-    def __init__(self, k, U):
+    def __init__(self, k, U, l=None):
         self.k = k
         self.U = np.asarray(U, dtype=np.float64)
         self.diagonal = self.U.ndim == 1
+        self.l = None if l is None else np.asarray(l, dtype=np.float64)   # ARD(k, l): the lengthscales it was built from (hyperparameters)
 
     def __call__(self, x, y):
         x = np.atleast_1d(np.asarray(x, dtype=np.float64)); y = np.atleast_1d(np.asarray(y, dtype=np.float64))
@@ -348,7 +349,7 @@ def ARD(k, l):
     l = np.asarray(l, dtype=np.float64)
     if not np.all(l > 0):
         raise DomainError(f"l = {l} is non-positive")
-    return ScaledInputKernel(k, 1.0 / l)
+    return ScaledInputKernel(k, 1.0 / l, l=l)
 
 
 class Warped(AbstractKernel):
@@ -757,6 +758,68 @@ def require_device_spec(k):
             f"{type(k).__name__} has input_trait {input_trait(k)!r} / no compiled device profile; the reference would run its "
             "generic threaded loop (src/gramian.jl:78-87) here — this engine has no CPU fallback")
     return spec
+
+
+# ----------------------------------------------------------------------------------------------
+# hyper-parameters: the ordered leaves of a kernel expression (the role of parameters / Base.similar in src/parameters.jl)
+# ----------------------------------------------------------------------------------------------
+_OWN_PARAMETER = {RationalQuadratic: "alpha", GammaExponential: "gamma", InverseMultiQuadratic: "c"}
+_NO_PARAMETER = (ExponentiatedQuadratic, Exponential, Cauchy, MaternP, Matern, Dot, ExponentialDot, AsinDot)   # p, nu: structure
+
+
+def hyperparameters(k):
+    """[(path, name, value)]: the leaves of the kernel expression `k` in a fixed order — depth first, arguments left to right, a
+    wrapper's own parameter after its inner kernel's.  Leaves: Constant.c ("scale"), Lengthscale.l ("l"), RationalQuadratic.alpha,
+    GammaExponential.gamma, InverseMultiQuadratic.c ("c"), and the entries of a diagonal ScaledInputKernel in the parametrisation the
+    object stores: "l" for ARD(k, l) (lengthscales), "U" for ScaledInputKernel(k, U) (the multipliers).  `path` is the tuple of steps
+    from the root (argument index of a Sum / Product, "k" into a wrapper, the dimension of an ARD entry).  MaternP's p, Matern's nu
+    and Power's exponent are structure, not parameters.  Any other node raises UnsupportedKernel naming it."""
+    def walk(k, path):
+        if isinstance(k, Constant):
+            return [(path, "scale", k.c)]
+        if isinstance(k, (Sum, Product)):
+            return [leaf for i, a in enumerate(k.args) for leaf in walk(a, path + (i,))]
+        if isinstance(k, Power):
+            return walk(k.k, path + ("k",))
+        if isinstance(k, Lengthscale):
+            return walk(k.k, path + ("k",)) + [(path, "l", k.l)]
+        if isinstance(k, ScaledInputKernel) and k.diagonal:
+            name, vals = ("l", k.l) if k.l is not None else ("U", k.U)
+            return walk(k.k, path + ("k",)) + [(path + (c,), name, float(v)) for c, v in enumerate(vals)]
+        if type(k) in _OWN_PARAMETER:
+            name = _OWN_PARAMETER[type(k)]
+            return [(path, name, getattr(k, name))]
+        if isinstance(k, _NO_PARAMETER):
+            return []
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"hyperparameters: {type(k).__name__} is not a node of a parameter tree")
+    return walk(k, ())
+
+
+def with_hyperparameters(k, theta):
+    """The kernel `k` rebuilt with the flat vector `theta` in the order of hyperparameters(k) (Base.similar(k, θ), src/parameters.jl:24-48)."""
+    theta = [float(v) for v in np.asarray(theta, dtype=np.float64).reshape(-1)]
+    nparam = len(hyperparameters(k))
+    if len(theta) != nparam:
+        raise _ffi.DimensionMismatch(_ffi.EINVAL, f"length(θ) = {len(theta)} ≠ {nparam} = nparameters(k)")   # src/parameters.jl:15
+    it = iter(theta)
+    def build(k):
+        if isinstance(k, Constant):
+            return Constant(next(it))
+        if isinstance(k, (Sum, Product)):
+            return type(k)(tuple(build(a) for a in k.args))
+        if isinstance(k, Power):
+            return Power(build(k.k), k.p)
+        if isinstance(k, Lengthscale):
+            inner = build(k.k)
+            return Lengthscale(inner, next(it))
+        if isinstance(k, ScaledInputKernel):
+            inner = build(k.k)
+            vals = np.array([next(it) for _ in range(len(k.U))])
+            return ARD(inner, vals) if k.l is not None else ScaledInputKernel(inner, vals)
+        if type(k) in _OWN_PARAMETER:
+            return type(k)(next(it))
+        return k
+    return build(k)
 
 
 # ----------------------------------------------------------------------------------------------

@@ -792,4 +792,18 @@ function Base.Matrix(S::DeviceSpectralMixture{T}) where {T <: DevFloat}
 end
 Base.getindex(S::DeviceSpectralMixture, i::Integer, j::Integer) = Matrix(S)[i, j]   # (for show and tests; not a hot path)
 
+# --- hyper-parameter gradients of Σ_t U[:, t]' G A[:, t] in one pass (covgram_bilinear_grad): out = [Σ W k, Σ W ∂k/∂param, Σ W (∂k/∂s) Δ_c² ...]
+#     (one number Σ W (∂k/∂s) s for per_dim = false) in Float64, W = U A'; simple isotropic kernels only (include/covgram.h)
+function bilinear_grad(G::Gramian{T}, U::StridedVecOrMat{T}, A::StridedVecOrMat{T}; per_dim::Bool = false) where {T <: DevFloat}
+    spec = device_kernel_for(G.k)
+    spec isa CKernel || throw(ArgumentError("bilinear_grad: simple isotropic kernels only"))
+    n, m = size(G)
+    size(U, 1) == n && size(A, 1) == m && size(U, 2) == size(A, 2) || throw(DimensionMismatch("bilinear_grad: U is n × nvec, A is m × nvec"))
+    X = points(G.x, T); Y = G.x === G.y ? X : points(G.y, T)
+    out = Vector{Float64}(undef, 2 + (per_dim ? length(first(G.x)) : 1))
+    check(ccall((:covgram_bilinear_grad, libcovgram), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int32, Int32, Ptr{Float64}, Int32),
+                ctx(), kref(spec), X.handle, Y.handle, U, max(stride(U, 2), n), A, max(stride(A, 2), m), size(U, 2), Int32(per_dim), out, HOST))
+    return out
+end
+
 end # module

@@ -71,7 +71,8 @@ extern "C" {
                                covgram_pivoted_cholesky and COVGRAM_PIVCHOL_MAX_RANK;
                                covgram_bcg_init, covgram_bcg_step, covgram_bcg_update, covgram_bcg_direction and the
                                COVGRAM_BCG_* layout of their state (batched CG on a block of right-hand sides);
-                               the covgram_sm_* handle (SpectralMixture Gramians: one fused product and Matrix(G)).
+                               the covgram_sm_* handle (SpectralMixture Gramians: one fused product and Matrix(G));
+                               covgram_bilinear_grad (hyper-parameter gradients of bilinear forms in one pass).
                                A binding checks covgram_version() against the header it mirrors at load time */
 
 typedef enum covgram_status {
@@ -617,6 +618,25 @@ int covgram_sm_mvm(covgram_sm* S, const covgram_points* X, const covgram_points*
                    int32_t nrhs, double alpha, double beta, int32_t loc);
 int covgram_sm_matrix(covgram_sm* S, const covgram_points* X, const covgram_points* Y, void* out, int64_t ldo, int32_t loc);
 int covgram_sm_destroy(covgram_sm* S);
+
+/* ---- Hyper-parameter gradients of the bilinear forms sum_t u_t' G a_t in ONE pass over the pairs (csrc/bilin_grad.hip), with
+ * W = U A' (n x m, rank nvec) formed per pair in registers and never stored:
+ *     out[0]     = sum_ij W_ij k_ij                          the value: d/dscale = out[0] / scale
+ *     out[1]     = sum_ij W_ij dk_ij / dparam                param = the struct's `param`: RQ alpha, gamma-exponential gamma, IMQ c;
+ *                                                            0 for the families without one
+ *     out[2 + c] = sum_ij W_ij (dk/ds)_ij (x_ic - y_jc)^2     c < d, per_dim != 0; per_dim == 0: the one number out[2] = sum_ij W_ij (dk/ds)_ij s_ij
+ * s is the RAW squared distance, formed by direct differences: dk/ds includes scale, power and lengthscale (d/dl = -(2 / l) sum_c out[2 + c]).
+ * `out` holds 2 + (per_dim ? d : 1) DOUBLES whatever the points' dtype (host or device memory, `loc`, which also applies to U and A).
+ * U is n x nvec (ldu >= n), A is m x nvec (lda >= m), column-major, in the points' dtype; Y == NULL means Y = X.
+ * k: a simple isotropic kernel of any family except COVGRAM_MATERN, any power >= 1, scale and lengthscale.  Composites, dot-product
+ *   families and COVGRAM_MATERN: COVGRAM_EUNSUPPORTED.  nvec outside 1 .. 32 or d outside 1 .. 64: COVGRAM_EINVAL.
+ * A pair at distance 0 (with Y == NULL the whole diagonal) adds exactly 0 to out[2 ..] for every family, also those whose dk/ds is
+ *   unbounded at 0, and the finite limit of dk/dparam to out[1].
+ * A lane adds at most 128 pairs in the points' precision before the sum continues in fp64; partial sums are added in a fixed order, no
+ *   atomics: two calls with the same arguments agree bit for bit.  n m == 0 gives zeros.  With loc == DEVICE the call is stream-ordered
+ *   and never synchronises.  Option "time_kernels" brackets the pair kernel and its reduction. */
+int covgram_bilinear_grad(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, const void* U, int64_t ldu,
+                          const void* A, int64_t lda, int32_t nvec, int32_t per_dim, double* out, int32_t loc);
 
 /* Test hook: the double-precision parameter block handed to the device kernels for `k`
  * (out45[0..8] = gamma, gamma^2, scale, param, c0, 2p+1, Taylor bound, d1, d2; then the MaternP tables
