@@ -20,7 +20,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "common.hpp"
+#include "driver.hpp"
 #include "profiles.hpp"
 
 namespace covgram {
@@ -286,11 +286,9 @@ static int bg_run(covgram_ctx* ctx, const HostKernel& hk, const covgram_points* 
     const int ds_w = std::min<int>(g.dpad, BG_DS);
     const int xs_w = ((ds_w >> 2) & 1) ? ds_w : ds_w + 4;
     const size_t lds = ((size_t)BG_TI * xs_w + (size_t)BG_TJ * ds_w + (size_t)nvec * (BG_TI + BG_TJ)) * sizeof(T);
-    auto* tm = timer_next(ctx);
-    if (tm) (void)hipEventRecord(tm->first, ctx->stream);
+    TimerScope tm(ctx);
     hipLaunchKernelGGL((bg_pair_kernel<T>), dim3((unsigned)rowtiles, (unsigned)jsplit), dim3(BG_TI * BG_WAVES), lds, ctx->stream, g);
     hipLaunchKernelGGL(bg_reduce_kernel, dim3((unsigned)nout), dim3(256), 0, ctx->stream, (const double*)slab, nblk, nout, out_dev);
-    if (tm) (void)hipEventRecord(tm->second, ctx->stream);
     return COVGRAM_OK;
 }
 

@@ -250,7 +250,6 @@ struct covgram_ctx {
     int64_t grad_keep_r = -1;    // -1 auto
     int64_t grad_bcast = -1;     // fp64 expanded-form gradient MVM with the column records in VGPRs (v_fmac_f64_dpp row_newbcast): -1 auto, 0 never, 1 / 4 = always with that many waves per workgroup
     int64_t last_grad_bcast = 0;
-    int64_t lds_pad = 0;         // occupancy experiments: dynamic LDS bytes per dense workgroup
     int64_t mfma_sym_rt = -1;    // symmetric matrix-core EQ kernel: row tiles per wave (-1 / 2: two, 4-wave workgroups, dense_mfma_sym2.hpp; 1: one, 8-wave workgroups)
     int64_t last_mfma_sym_rt = 0;
     int64_t mfma_sym_st = 0;     // symmetric matrix-core kernels with 4-wave workgroups: column tiles per stage (0 = auto: 8 where three workgroups still fit a CU's LDS, 4 = always four)
@@ -270,7 +269,6 @@ struct covgram_ctx {
     int64_t last_inkernel_reduce = 0;
     unsigned* tickets = nullptr;  // one arrival counter per row block, zero between launches (pack.hpp: last_arrival)
     size_t tickets_cap = 0;
-    int32_t sym_part_rank = 0, sym_part_world = 0;   // set by covgram_mvm_sym_partial around its fp64 call of covgram_mvm: world > 0 = partial form
     int64_t mfma_sym = -1;       // matrix-core EQ path on gramian(k, x): evaluate the upper triangle once (-1 auto, 0 never, 1 always)
     int64_t mfma_lds = -1;       // matrix-core EQ path: 4 waves share the column tiles through LDS (-1 auto, 0 never, 1 always)
     int64_t mfma_stamp = 0;      // 1: the general matrix-core EQ kernel runs its clock-stamping diagnostic build (info key "last_clock_khz")
@@ -290,7 +288,7 @@ struct covgram_ctx {
     int64_t toeplitz_fused = 1;  // 1: row FFT + spectral step + inverse row FFT as one kernel when M' = 4^L <= 4096; 0: rocFFT batches
     void* comm = nullptr;        // ncclComm_t of covgram_comm_create (comm.hip): the MVM's one collective runs on `stream`
     int32_t comm_rank = 0, comm_world = 0;
-    int num_cus = 256;
+    int64_t num_cus = 256;       // (int64_t: every option and info key is one, covgram_ctx_get_info)
     void* blas = nullptr;        // rocblas_handle of the compute-bound Kronecker mode products (kron.hip), created on first use
     int live_handles = 0;
     int64_t last_dense_path = 0; // 1 lane-per-row, 2 matrix cores, 3 wide rows, 4 factored dot product X (Y' a)
@@ -356,7 +354,7 @@ int ws_reserve(covgram_ctx* ctx, int slot, size_t bytes, void** out);
 int unalias_input(covgram_ctx* ctx, const void** a, int64_t* lda, int64_t rows_a, int64_t cols, const void* y, int64_t ldy, int64_t rows_y, size_t ts);
 // >= count zeroed arrival counters (grown stream-ordered; they return to zero by themselves after every launch that uses them)
 int tickets_reserve(covgram_ctx* ctx, size_t count, unsigned** out);
-// returns an event pair to record around the dominant kernel, or nullptr when timing is off / the pool is full
+// returns an event pair to record around the dominant kernel, or nullptr when timing is off / the pool is full (driver.hpp: TimerScope)
 std::pair<hipEvent_t, hipEvent_t>* timer_next(covgram_ctx* ctx);
 inline size_t dtype_size(int dtype) { return dtype == COVGRAM_F64 ? 8 : 4; }
 
@@ -368,7 +366,6 @@ struct DenseArgs {
     int64_t npad; int64_t ldy;
     int32_t nrhs; int32_t Dpad; int32_t NRpad;
     int64_t jchunk; int32_t jsplit; int32_t rows_per_lane; int32_t variant;
-    int32_t lds_pad = 0;                   // dynamic LDS bytes requested only to cap waves per CU (occupancy experiments)
     const void* C = nullptr;               // common centre (d scalars on the device) subtracted from both sides by isotropic kernels
     int32_t bcast = 0; const void* Ex = nullptr;   // fp64 wide points: dense_bcast_kernel (expanded distance, records in VGPRs); P = [mpad][D] points, Ex = [mpad][2] (|y'|^2, a)
     unsigned* tickets = nullptr; void* yfinal = nullptr;   // jsplit > 1: the last workgroup of a row block sums the slab into yfinal (pack.hpp: last_arrival)

@@ -49,6 +49,7 @@
 //                                            the MFMA yields the profile argument s (dense_mfma.hpp).
 //   dense_mfma_sym_kernel / _sym_wide_kernel gramian(k, x), one point set: the upper triangle once, row AND column sums
 //                                            ("Symmetric Gramian" below); also rank r of P's share for the multi-GPU form.
+#include "driver.hpp"
 #include "dense_mfma.hpp"
 #include "dense_mfma_sym2.hpp"
 
@@ -782,17 +783,17 @@ int mvm_eq_mfma(covgram_ctx* ctx, const HostKernel& hk, const covgram_points* X,
     const bool ikr = inkernel_reduce_on(ctx, true, n, js);
     ctx->last_inkernel_reduce = ikr ? 1 : 0;
     if (ikr) { rc = tickets_reserve(ctx, (size_t)rowtiles, &tickets); if (rc) return rc; }
-    auto* tm = timer_next(ctx);
-    if (tm) (void)hipEventRecord(tm->first, ctx->stream);
     ctx->last_mfma_lds = lds4 ? 1 : 0;
     dim3 launched;
+    {
+    TimerScope tm(ctx);
 #define CG_MFMA_CASE(K) case K: if (fmt) { if constexpr (K <= 8) launch_mfma<K, 1>(rt, lds4, grid, ctx->stream, (const float*)X->dptr, n, d, PB, W, ntile, out, npad, tchunk, g, (float)alpha_eff, (float)beta, fs, Cn, stamps, &launched, tickets, y, EFk, m, &ctx->last_mfma_instance); } else launch_mfma<K>(rt, lds4, grid, ctx->stream, (const float*)X->dptr, n, d, PB, W, ntile, out, npad, tchunk, g, (float)alpha_eff, (float)beta, fs, Cn, stamps, &launched, tickets, y, EFk, m, &ctx->last_mfma_instance); break;
     switch (K2) {
         CG_MFMA_CASE(1) CG_MFMA_CASE(2) CG_MFMA_CASE(3) CG_MFMA_CASE(4) CG_MFMA_CASE(6) CG_MFMA_CASE(8) CG_MFMA_CASE(12) CG_MFMA_CASE(16)
         default: set_error("dense_mfma: K2 = %d not compiled", K2); return COVGRAM_EUNSUPPORTED;
     }
 #undef CG_MFMA_CASE
-    if (tm) (void)hipEventRecord(tm->second, ctx->stream);
+    }
     if (stamps) ctx->stamp_count = (size_t)launched.x * launched.y;
     if (js > 1 && !ikr)
         hipLaunchKernelGGL(dense_reduce_kernel<float>, dim3((unsigned)((n + 63) / 64), 1), dim3(256), 0, ctx->stream, (const float*)out, npad, 1,
@@ -1017,8 +1018,8 @@ int mvm_eq_mfma_sym(covgram_ctx* ctx, const HostKernel& hk, const covgram_points
         ctx->sym_map_len = list.size();
     }
     const dim3 grid((unsigned)std::max<size_t>(ctx->sym_map_len, 1));
-    auto* tm = timer_next(ctx);
-    if (tm) (void)hipEventRecord(tm->first, ctx->stream);
+    {
+    TimerScope tm(ctx);
 #define CG_SYM_CASE(K) case K: hipLaunchKernelGGL((dense_mfma_sym_kernel<FAM_EQFAST, K>), grid, dim3(512), 0, ctx->stream, (const float*)X->dptr, n, d, \
                                                   PBu, W, ntile, (float*)Rp, (float*)Sp, npad, (int)tchunk, g, Cn, pfirst, pstride, ctx->sym_map, \
                                                   KParams<float>{}, EF); break;
@@ -1081,7 +1082,7 @@ int mvm_eq_mfma_sym(covgram_ctx* ctx, const HostKernel& hk, const covgram_points
 #undef CG_SYMW_CASE
 #undef CG_SYMH_CASE
 #undef CG_SYMWH_CASE
-    if (tm) (void)hipEventRecord(tm->second, ctx->stream);
+    }
     hipLaunchKernelGGL(dense_mfma_sym_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(1024), 0, ctx->stream, n, (const float*)Rp,
                        (const float*)Sp, npad, ntile, (int)tchunk, EF, y, (float)alpha_eff, (float)beta, pfirst, pstride, tpp);
     hipError_t e = hipGetLastError();
@@ -1307,11 +1308,8 @@ int mvm_mfma_gen(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points
         ma.X = (const float*)X->dptr; ma.n = n; ma.d = d; ma.PB = PB; ma.W = AP; ma.ntile = ntile; ma.out = out; ma.npad = npad; ma.ldy = ldy;
         ma.nrhs = nr; ma.tchunk = tchunk; ma.alpha = (float)alpha_eff; ma.beta = (float)beta; ma.final_store = js == 1 ? 1 : 0;
         ma.grid = dim3((unsigned)rowtiles, (unsigned)js);
-        auto* tm = timer_next(ctx);
-        if (tm) (void)hipEventRecord(tm->first, ctx->stream);
-        rc = launch(ma, false);
+        { TimerScope tm(ctx); rc = launch(ma, false); }
         if (rc) return rc;
-        if (tm) (void)hipEventRecord(tm->second, ctx->stream);
         if (js > 1)
             hipLaunchKernelGGL(dense_reduce_kernel<float>, dim3((unsigned)((n + 63) / 64), nr), dim3(256), 0, ctx->stream, (const float*)out, npad,
                                32 * NB, (int)js, y_c, n, ldy, nr, (float)alpha_eff, (float)beta);
@@ -1356,11 +1354,8 @@ int mvm_mfma_gen(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points
         // (tools/mfma_lds_ab.py <kernel>: 11-28 % faster at d = 12 .. 24; at d <= 8 the barrier per tile costs 5-18 %, so not there)
         ma.lds = (ctx->mfma_lds == 1 || (ctx->mfma_lds < 0 && K2 > 4 && tchunk >= MFMA_LDS_MIN_TILES && rowtiles >= 64)) ? 1 : 0;
         ctx->last_mfma_lds = ma.lds;
-        auto* tm = timer_next(ctx);
-        if (tm) (void)hipEventRecord(tm->first, ctx->stream);
-        rc = launch(ma, false);
+        { TimerScope tm(ctx); rc = launch(ma, false); }
         if (rc) return rc;
-        if (tm) (void)hipEventRecord(tm->second, ctx->stream);
         if (js > 1)
             hipLaunchKernelGGL(dense_reduce_kernel<float>, dim3((unsigned)((n + 63) / 64), nr), dim3(256), 0, ctx->stream, (const float*)out, npad,
                                NR, (int)js, y_c, n, ldy, nr, (float)alpha_eff, (float)beta);

@@ -19,6 +19,7 @@
 
 #include <algorithm>
 
+#include "driver.hpp"
 #include "profiles.hpp"
 
 namespace covgram {
@@ -231,11 +232,7 @@ int covgram_pivoted_cholesky(covgram_ctx* ctx, const covgram_kernel* k, const co
     w.idx[1] = w.idx[0] + PC_MAX_WGS;
     CG_CHECK_HIP(hipMemsetAsync(w.done, 0, PC_WS_HEAD, ctx->stream));
     const unsigned nwg = (unsigned)std::min<int64_t>((n + PC_THREADS - 1) / PC_THREADS, PC_MAX_WGS);
-    auto* tm = timer_next(ctx);
-    if (tm) (void)hipEventRecord(tm->first, ctx->stream);
-    if (dtype == COVGRAM_F32) pivchol_launch<float>(X, hk, max_rank, tol, L, ldl, piv, dres, rank, w, nwg, ctx->stream);
-    else pivchol_launch<double>(X, hk, max_rank, tol, L, ldl, piv, dres, rank, w, nwg, ctx->stream);
-    if (tm) (void)hipEventRecord(tm->second, ctx->stream);
+    { TimerScope tm(ctx); by_dtype(dtype, [&](auto t) { pivchol_launch<decltype(t)>(X, hk, max_rank, tol, L, ldl, piv, dres, rank, w, nwg, ctx->stream); }); }
     CG_CHECK_HIP(hipGetLastError());
     return COVGRAM_OK;
 }

@@ -409,7 +409,7 @@ struct Phi<COVGRAM_MATERNP, T, false> {
 };
 // ---- Matern with real nu (src/stationary.jl:87-114): modified Bessel function of the second kind -----------------------
 // K_a(x), a >= 0, x > 0.  hc[0..6] = round(a), mu = a - round(a), and the mu-only constants of Temme's method
-// (gam1, gam2, 1/Gamma(1+mu), 1/Gamma(1-mu), pi mu / sin(pi mu)), prepared by the host (api.hip).  x < 2: Temme's series
+// (gam1, gam2, 1/Gamma(1+mu), 1/Gamma(1-mu), pi mu / sin(pi mu)), prepared by the host (kernel_params.hip).  x < 2: Temme's series
 // for K_mu and K_mu+1; x >= 2: Steed's continued fraction (CF2); then the upward recurrence K_{b+1} = K_{b-1} + (2b/x) K_b,
 // which is the stable direction for K.  The iteration counts depend on the lane's x; the loops stop at eps(T).
 template <typename T>
@@ -866,7 +866,7 @@ __device__ __forceinline__ void power_jet(int q, T& v, T& d1, T& d2) {
 }
 
 // LIGHT: without Matern(nu) — its Bessel series, inlined into the per-pair interpreter loop of the lane-per-row gradient kernel, costs
-// every composite registers and instruction cache; composites that do contain it take the panel path (api.hip)
+// every composite registers and instruction cache; composites that do contain it take the panel path (block_mvm.hip)
 template <typename T, bool LIGHT = false>
 __device__ __forceinline__ void jet_any(int family, T s, const KParams<T>& kp, T& v, T& d1, T& d2) {
     switch (family) {

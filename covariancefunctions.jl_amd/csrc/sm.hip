@@ -19,7 +19,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "common.hpp"
+#include "driver.hpp"
 #include "profiles.hpp"
 
 // the column loop asks for two pairs per trip; where the body is too large for that (wide points) the request is dropped, silently
@@ -306,8 +306,7 @@ static int sm_mvm_t(covgram_sm* S, const covgram_points* X, const covgram_points
     g.jchunk = jchunk; g.direct = jsplit == 1 ? 1 : 0;
     g.alpha = (T)alpha; g.beta = (T)beta;
     const dim3 grid((unsigned)rowblocks, (unsigned)jsplit);
-    auto* tm = timer_next(ctx);
-    if (tm) (void)hipEventRecord(tm->first, ctx->stream);
+    TimerScope tm(ctx);
     for (int c0 = 0; c0 < nrhs; c0 += 4) {                        // four right-hand sides share one pass over the pairs
         const int nr = std::min(4, nrhs - c0);
         T* yc = (T*)y + (size_t)c0 * ldy;
@@ -319,7 +318,6 @@ static int sm_mvm_t(covgram_sm* S, const covgram_points* X, const covgram_points
             hipLaunchKernelGGL((sm_reduce_kernel<T>), dim3((unsigned)((n + 255) / 256), (unsigned)nr), dim3(256), 0, ctx->stream, (const T*)slab, (int)jsplit, nr, n,
                                yc, ldy, (T)alpha, (T)beta);
     }
-    if (tm) (void)hipEventRecord(tm->second, ctx->stream);
     return COVGRAM_OK;
 }
 
@@ -335,10 +333,8 @@ static int sm_matrix_t(covgram_sm* S, const covgram_points* X, const covgram_poi
     while ((m + jchunk - 1) / jchunk > 65535) jchunk *= 2;
     g.jchunk = jchunk; g.out = (T*)out; g.ldo = ldo;
     const dim3 grid((unsigned)((n + SM_ROWS - 1) / SM_ROWS), (unsigned)((m + jchunk - 1) / jchunk));
-    auto* tm = timer_next(ctx);
-    if (tm) (void)hipEventRecord(tm->first, ctx->stream);
+    TimerScope tm(ctx);
     sm_launch_pairs<T, 0>(S, g, grid, ctx->stream);
-    if (tm) (void)hipEventRecord(tm->second, ctx->stream);
     return COVGRAM_OK;
 }
 
@@ -440,35 +436,20 @@ int covgram_sm_mvm(covgram_sm* S, const covgram_points* X, const covgram_points*
     covgram_ctx* ctx = S->ctx;
     const size_t ts = dtype_size(S->dtype);
     CG_DEVICE(ctx);
-    const void* a_dev = a;
-    void* y_dev = y;
-    int64_t lda_d = lda, ldy_d = ldy;
-    if (loc == COVGRAM_HOST) {                   // a is staged before anything is written back: any overlap of a and y is harmless
-        void *sa, *sy;
-        rc = ws_reserve(ctx, 2, (size_t)std::max<int64_t>(m, 1) * nrhs * ts, &sa); if (rc) return rc;
-        rc = ws_reserve(ctx, 3, (size_t)n * nrhs * ts, &sy); if (rc) return rc;
-        if (m > 0) CG_CHECK_HIP(hipMemcpy2DAsync(sa, (size_t)m * ts, a, (size_t)lda * ts, (size_t)m * ts, nrhs, hipMemcpyHostToDevice, ctx->stream));
-        if (beta != 0.0) CG_CHECK_HIP(hipMemcpy2DAsync(sy, (size_t)n * ts, y, (size_t)ldy * ts, (size_t)n * ts, nrhs, hipMemcpyHostToDevice, ctx->stream));
-        a_dev = sa; y_dev = sy; lda_d = std::max<int64_t>(m, 1); ldy_d = n;
-    } else {
-        rc = unalias_input(ctx, &a_dev, &lda_d, m, nrhs, y, ldy, n, ts);
-        if (rc) return rc;
-    }
+    Staged st;
+    rc = st.begin(ctx, loc, ts, a, lda, m, y, ldy, n, nrhs, beta);
+    if (rc) return rc;
     if (m == 0) {                                // an empty sum: y <- beta y
         const dim3 grid((unsigned)((n + 255) / 256), (unsigned)nrhs);
-        if (S->dtype == COVGRAM_F32) hipLaunchKernelGGL((sm_scale_kernel<float>), grid, dim3(256), 0, ctx->stream, (float*)y_dev, n, ldy_d, (float)beta);
-        else hipLaunchKernelGGL((sm_scale_kernel<double>), grid, dim3(256), 0, ctx->stream, (double*)y_dev, n, ldy_d, beta);
-    } else {
-        rc = S->dtype == COVGRAM_F32 ? sm_mvm_t<float>(S, X, Y, a_dev, lda_d, y_dev, ldy_d, nrhs, alpha, beta)
-                                     : sm_mvm_t<double>(S, X, Y, a_dev, lda_d, y_dev, ldy_d, nrhs, alpha, beta);
-        if (rc) return rc;
-    }
+        by_dtype(S->dtype, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((sm_scale_kernel<T>), grid, dim3(256), 0, ctx->stream, (T*)st.y, n, st.ldy, (T)beta);
+        });
+    } else
+        rc = by_dtype(S->dtype, [&](auto t) { return sm_mvm_t<decltype(t)>(S, X, Y, st.a, st.lda, st.y, st.ldy, nrhs, alpha, beta); });
+    if (rc) return rc;
     CG_CHECK_HIP(hipGetLastError());
-    if (loc == COVGRAM_HOST) {
-        CG_CHECK_HIP(hipMemcpy2DAsync(y, (size_t)ldy * ts, y_dev, (size_t)n * ts, (size_t)n * ts, nrhs, hipMemcpyDeviceToHost, ctx->stream));
-        CG_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return COVGRAM_OK;
+    return st.finish();
 }
 
 int covgram_sm_matrix(covgram_sm* S, const covgram_points* X, const covgram_points* Y, void* out, int64_t ldo, int32_t loc) {
@@ -482,20 +463,13 @@ int covgram_sm_matrix(covgram_sm* S, const covgram_points* X, const covgram_poin
     covgram_ctx* ctx = S->ctx;
     const size_t ts = dtype_size(S->dtype);
     CG_DEVICE(ctx);
-    void* o_dev = out;
-    int64_t ldo_d = ldo;
-    if (loc == COVGRAM_HOST) {                   // a staged n x m tile, copied back column by column: rows n <= i < ldo stay untouched
-        rc = ws_reserve(ctx, 3, (size_t)n * m * ts, &o_dev); if (rc) return rc;
-        ldo_d = n;
-    }
-    rc = S->dtype == COVGRAM_F32 ? sm_matrix_t<float>(S, X, Y, o_dev, ldo_d) : sm_matrix_t<double>(S, X, Y, o_dev, ldo_d);
+    Staged st;
+    rc = st.begin_tile(ctx, loc, ts, out, ldo, n, m);
+    if (rc) return rc;
+    rc = by_dtype(S->dtype, [&](auto t) { return sm_matrix_t<decltype(t)>(S, X, Y, st.y, st.ldy); });
     if (rc) return rc;
     CG_CHECK_HIP(hipGetLastError());
-    if (loc == COVGRAM_HOST) {
-        CG_CHECK_HIP(hipMemcpy2DAsync(out, (size_t)ldo * ts, o_dev, (size_t)n * ts, (size_t)n * ts, m, hipMemcpyDeviceToHost, ctx->stream));
-        CG_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return COVGRAM_OK;
+    return st.finish();
 }
 
 int covgram_sm_destroy(covgram_sm* S) {

@@ -15,6 +15,7 @@
 
 #include <algorithm>
 
+#include "driver.hpp"
 #include "profiles.hpp"
 
 namespace covgram {
@@ -443,8 +444,7 @@ int covgram_sparse_create(covgram_ctx* ctx, covgram_sparse** out, const covgram_
     const double R2 = R * R;
 
     // 1. count
-    if (dtype == COVGRAM_F32) launch_sparse_sweep<float, false>(X, Y, g, R2, counts, nullptr, nullptr, nullptr, nullptr, hk, ctx->stream);
-    else launch_sparse_sweep<double, false>(X, Y, g, R2, counts, nullptr, nullptr, nullptr, nullptr, hk, ctx->stream);
+    by_dtype(dtype, [&](auto t) { launch_sparse_sweep<decltype(t), false>(X, Y, g, R2, counts, nullptr, nullptr, nullptr, nullptr, hk, ctx->stream); });
     // 2. scan in (row, chunk) order
     hipLaunchKernelGGL(sparse_scan_sums_kernel, dim3((unsigned)nb), dim3(256), 0, ctx->stream, counts, slots, bsum);
     hipLaunchKernelGGL(sparse_scan_top_kernel, dim3(1), dim3(256), 0, ctx->stream, bsum, nb);
@@ -465,11 +465,7 @@ int covgram_sparse_create(covgram_ctx* ctx, covgram_sparse** out, const covgram_
             return fail(COVGRAM_ENOMEM);
         }
         // 3. fill
-        auto* tm = timer_next(ctx);
-        if (tm) (void)hipEventRecord(tm->first, ctx->stream);
-        if (dtype == COVGRAM_F32) launch_sparse_sweep<float, true>(X, Y, g, R2, nullptr, off, S->colind, S->vals, flag, hk, ctx->stream);
-        else launch_sparse_sweep<double, true>(X, Y, g, R2, nullptr, off, S->colind, S->vals, flag, hk, ctx->stream);
-        if (tm) (void)hipEventRecord(tm->second, ctx->stream);
+        { TimerScope tm(ctx); by_dtype(dtype, [&](auto t) { launch_sparse_sweep<decltype(t), true>(X, Y, g, R2, nullptr, off, S->colind, S->vals, flag, hk, ctx->stream); }); }
         CG_SP_HIP(hipGetLastError());
     }
     // the fill has read X and Y for the last time when this returns (the handle keeps no reference to them), and its flag is known
@@ -520,32 +516,12 @@ int covgram_sparse_mvm(covgram_sparse* S, const void* a, int64_t lda, void* y, i
     covgram_ctx* ctx = S->ctx;
     const size_t ts = dtype_size(S->dtype);
     CG_DEVICE(ctx);
-    const void* a_dev = a;
-    void* y_dev = y;
-    int64_t lda_d = lda, ldy_d = ldy;
-    int rc;
-    if (loc == COVGRAM_HOST) {                   // a is staged before anything is written back: any overlap of a and y is harmless
-        void *sa, *sy;
-        rc = ws_reserve(ctx, 2, (size_t)std::max<int64_t>(m, 1) * nrhs * ts, &sa); if (rc) return rc;
-        rc = ws_reserve(ctx, 3, (size_t)n * nrhs * ts, &sy); if (rc) return rc;
-        if (m > 0) CG_CHECK_HIP(hipMemcpy2DAsync(sa, (size_t)m * ts, a, (size_t)lda * ts, (size_t)m * ts, nrhs, hipMemcpyHostToDevice, ctx->stream));
-        if (beta != 0.0) CG_CHECK_HIP(hipMemcpy2DAsync(sy, (size_t)n * ts, y, (size_t)ldy * ts, (size_t)n * ts, nrhs, hipMemcpyHostToDevice, ctx->stream));
-        a_dev = sa; y_dev = sy; lda_d = std::max<int64_t>(m, 1); ldy_d = n;
-    } else {
-        rc = unalias_input(ctx, &a_dev, &lda_d, m, nrhs, y, ldy, n, ts);
-        if (rc) return rc;
-    }
-    auto* tm = timer_next(ctx);
-    if (tm) (void)hipEventRecord(tm->first, ctx->stream);
-    if (S->dtype == COVGRAM_F32) launch_sparse_mvm_t<float>(S, a_dev, lda_d, y_dev, ldy_d, nrhs, alpha, beta, ctx->stream);
-    else launch_sparse_mvm_t<double>(S, a_dev, lda_d, y_dev, ldy_d, nrhs, alpha, beta, ctx->stream);
-    if (tm) (void)hipEventRecord(tm->second, ctx->stream);
+    Staged st;
+    int rc = st.begin(ctx, loc, ts, a, lda, m, y, ldy, n, nrhs, beta);
+    if (rc) return rc;
+    { TimerScope tm(ctx); by_dtype(S->dtype, [&](auto t) { launch_sparse_mvm_t<decltype(t)>(S, st.a, st.lda, st.y, st.ldy, nrhs, alpha, beta, ctx->stream); }); }
     CG_CHECK_HIP(hipGetLastError());
-    if (loc == COVGRAM_HOST) {
-        CG_CHECK_HIP(hipMemcpy2DAsync(y, (size_t)ldy * ts, y_dev, (size_t)n * ts, (size_t)n * ts, nrhs, hipMemcpyDeviceToHost, ctx->stream));
-        CG_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return COVGRAM_OK;
+    return st.finish();
 }
 
 int covgram_sparse_destroy(covgram_sparse* S) {

@@ -1,4 +1,4 @@
-"""Row-wise parity of the gradient and value-gradient block MVMs (covgram_grad_mvm / covgram_valgrad_mvm, csrc/api.hip:
+"""Row-wise parity of the gradient and value-gradient block MVMs (covgram_grad_mvm / covgram_valgrad_mvm, csrc/block_mvm.hip:
 grad_mvm_impl) on every kernel route, each pinned by the info keys last_grad_path / last_grad_jsplit / last_grad_expand /
 last_grad_bcast before its numbers are checked.
 
@@ -276,7 +276,7 @@ def test_panel_path_forced_at_small_d(cg, oracle):
 
 
 def test_composite_with_a_matern_factor_takes_the_panel_path(cg, oracle):
-    """Matern(nu) * EQ: the lane-per-row interpreter is built without the Matern factor (api.hip: heavy_factor)."""
+    """Matern(nu) * EQ: the lane-per-row interpreter is built without the Matern factor (block_mvm.hip: heavy_factor)."""
     o = oracle
     rng = np.random.default_rng(1200)
     X, far = add_far(cloud(rng, 300, 3, F64), rng, 3)

@@ -293,3 +293,151 @@ def test_cg_step_shifted_adds_the_diagonal_term_and_leaves_the_norm(cg, ctx, dt)
                 for got, want in ((xd, x64), (rd, r64), (pd, p64)):
                     assert relerr(got.cpu().numpy(), want) <= tol * 200, (n, step, relerr(got.cpu().numpy(), want))
     f.check(lib.covgram_cg_step_shifted(ctx, 0, f.F64, None, None, None, None, None, None))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# The entry points whose a / y (or output tile) go through the shared staging helpers of csrc/driver.hpp (StagedVectors, StagedTile):
+# HOST pointers must give the bits DEVICE pointers give, and the timer bracket (TimerScope) must count what it always counted.
+# ------------------------------------------------------------------------------------------------------------------------------------
+_SN, _SM, _SD, _SNRHS = 130, 67, 3, 3
+_BLOCK_KINDS = ("gradient", "value_gradient", "hessian", "value_gradient_hessian")
+
+
+def _staged_entry_points(cg, ctx, dt):
+    """{name: (square_ok, run)}; run(loc, inplace) -> (result, prefill, rows): the whole column-major buffer after the call (leading dimension
+    included), what it held before, and the rows the call may write.  Seeded inputs: every run of one name sees the same numbers.
+    A single-profile kernel (EQ, l = 0.9, scale 1.7; sparse: l = 0.3), nrhs = 3, lda = rows + 5, ldy = rows + 3, alpha = -0.7, beta = 1.3 on a
+    prefilled y; inplace (square products only, X on both sides): y is a."""
+    lib, f = cg._ffi.lib(), cg._ffi
+    code = f.F64 if dt == np.float64 else f.F32
+    rng = np.random.default_rng(20)
+    X = rng.standard_normal((_SN, _SD)).astype(dt); Y = rng.standard_normal((_SM, _SD)).astype(dt)
+    hx, hy = make_points(cg, ctx, X), make_points(cg, ctx, Y)
+    spec = cg.device_spec(cg.Lengthscale(cg.EQ(), 0.9) * 1.7)
+    kp = f.kref(spec)
+    keep = [X, Y, spec]                                           # what the handles and pointers below refer to
+
+    def buffers(loc, arrays):
+        """the arrays as the call's pointers: numpy memory (HOST) or device copies (DEVICE), and a function that reads them back"""
+        if loc == f.HOST:
+            return [P(a) for a in arrays], lambda i: arrays[i]
+        dev = [torch.from_numpy(a).cuda() for a in arrays]
+        torch.cuda.synchronize()
+        def back(i):
+            f.check(lib.covgram_sync(ctx))
+            return dev[i].cpu().numpy()
+        return [f._P(t.data_ptr()) for t in dev], back
+
+    def mvm_like(call, bd_of, seed):
+        def run(loc, inplace):
+            r = np.random.default_rng(seed)
+            hcol = hx if inplace else hy
+            rows_a, rows_y = (_SN if inplace else _SM) * bd_of, _SN * bd_of
+            lda, ldy = (rows_y + 3, rows_y + 3) if inplace else (rows_a + 5, rows_y + 3)
+            A = r.standard_normal((_SNRHS, lda)).astype(dt); Yv = r.standard_normal((_SNRHS, ldy)).astype(dt)
+            Y0 = Yv.copy()
+            if inplace:
+                (p,), back = buffers(loc, [Yv])
+                f.check(call(hcol, p, lda, p, ldy, loc))
+                return back(0), Y0, rows_y
+            (pa, py), back = buffers(loc, [A, Yv])
+            f.check(call(hcol, pa, lda, py, ldy, loc))
+            return back(1), Y0, rows_y
+        return run
+
+    def tile_like(call, rows, cols, seed):
+        def run(loc, inplace):
+            ldo = rows + 3
+            O = np.random.default_rng(seed).standard_normal((cols, ldo)).astype(dt)
+            O0 = O.copy()
+            (po,), back = buffers(loc, [O])
+            f.check(call(po, ldo, loc))
+            return back(0), O0, rows
+        return run
+
+    d = _SD
+    eps = {}
+    for name, fn, bd in (("covgram_mvm", lib.covgram_mvm, 1), ("covgram_grad_mvm", lib.covgram_grad_mvm, d), ("covgram_valgrad_mvm", lib.covgram_valgrad_mvm, d + 1),
+                         ("covgram_hess_mvm", lib.covgram_hess_mvm, d * d), ("covgram_valgradhess_mvm", lib.covgram_valgradhess_mvm, 1 + d + d * d)):
+        eps[name] = (True, mvm_like(lambda hc, pa, lda, py, ldy, loc, fn=fn: fn(ctx, kp, hx, hc, pa, lda, py, ldy, _SNRHS, -0.7, 1.3, loc), bd, 31))
+    as_d = lambda v: np.ascontiguousarray(v, dtype=np.float64).ctypes.data_as(C.POINTER(C.c_double))
+    w, mu, il = np.array([0.7, 1.1]), rng.standard_normal((2, d)) * 0.3, 1.0 / (0.6 + rng.random((2, d)))
+    hsm = f._P()
+    f.check(lib.covgram_sm_create(ctx, C.byref(hsm), 2, d, as_d(w), as_d(mu), as_d(il), code))
+    eps["covgram_sm_mvm"] = (True, mvm_like(lambda hc, pa, lda, py, ldy, loc: lib.covgram_sm_mvm(hsm, hx, hc, pa, lda, py, ldy, _SNRHS, -0.7, 1.3, loc), 1, 32))
+    sparse_spec = cg.device_spec(cg.Lengthscale(cg.EQ(), 0.3))
+    keep.append(sparse_spec)
+    hsp = {}
+    for square, hc in ((False, hy), (True, hx)):
+        hsp[square] = f._P()
+        f.check(lib.covgram_sparse_create(ctx, C.byref(hsp[square]), f.kref(sparse_spec), hx, hc, 1e-6))
+    eps["covgram_sparse_mvm"] = (True, mvm_like(lambda hc, pa, lda, py, ldy, loc: lib.covgram_sparse_mvm(hsp[hc is hx], pa, lda, py, ldy, _SNRHS, -0.7, 1.3, loc), 1, 33))
+    eps["covgram_matrix"] = (False, tile_like(lambda po, ldo, loc: lib.covgram_matrix(ctx, kp, hx, hy, po, ldo, loc), _SN, _SM, 34))
+    for kind, B in zip(range(4), (d, d + 1, d * d, 1 + d + d * d)):
+        eps["covgram_block_matrix:" + _BLOCK_KINDS[kind]] = (False, tile_like(
+            lambda po, ldo, loc, kind=kind: lib.covgram_block_matrix(ctx, kind, kp, hx, hy, po, ldo, loc), _SN * B, _SM * B, 35))
+    eps["covgram_sm_matrix"] = (False, tile_like(lambda po, ldo, loc: lib.covgram_sm_matrix(hsm, hx, hy, po, ldo, loc), _SN, _SM, 36))
+
+    def close():
+        assert lib.covgram_sm_destroy(hsm) == 0
+        for h in hsp.values():
+            assert lib.covgram_sparse_destroy(h) == 0
+        for h in (hx, hy):
+            assert lib.covgram_points_destroy(h) == 0
+        keep.clear()
+    return eps, close
+
+
+@pytest.mark.parametrize("dt", [np.float32, np.float64])
+def test_host_pointers_give_the_bits_of_device_pointers(cg, ctx, dt):
+    """covgram_mvm, _grad_mvm, _valgrad_mvm, _hess_mvm, _valgradhess_mvm, _sm_mvm, _sparse_mvm (y <- alpha G a + beta y, and in place: y is a)
+    and covgram_matrix, _block_matrix (four kinds), _sm_matrix at n = 130, m = 67, d = 3: the HOST call returns the bits of the DEVICE call, and
+    neither writes the padding rows between the extent and the leading dimension."""
+    f = cg._ffi
+    eps, close = _staged_entry_points(cg, ctx, dt)
+    try:
+        for name, (square_ok, run) in eps.items():
+            for inplace in ((False, True) if square_ok else (False,)):
+                host, h0, rows = run(f.HOST, inplace)
+                dev, d0, _ = run(f.DEVICE, inplace)
+                assert host.shape == dev.shape and np.all(np.isfinite(host[:, :rows])), (name, inplace)
+                assert host.tobytes() == dev.tobytes(), (name, inplace, float(np.abs(host.astype(np.float64) - dev).max()))
+                if not inplace:
+                    assert np.array_equal(host[:, rows:], h0[:, rows:]) and np.array_equal(dev[:, rows:], d0[:, rows:]), (name, "padding rows")
+                    assert not np.array_equal(host[:, :rows], h0[:, :rows]), (name, "nothing written")
+    finally:
+        close()
+
+
+# launches covgram_ctx_kernel_time reports after ONE call of each entry point above with "time_kernels" = 1, fp32 and fp64 alike: the literals
+# were recorded from the library as it was before the brackets became TimerScope (profiles/driver_refactor_ab.txt: the same calls, HOST and
+# DEVICE).  covgram_matrix has no bracket; the gradient MVMs run the three right-hand sides as a pass of two and a pass of one, the Hessian
+# MVMs one pass per right-hand side.
+_TIMED_LAUNCHES = {
+    "covgram_mvm": 1, "covgram_grad_mvm": 2, "covgram_valgrad_mvm": 2, "covgram_hess_mvm": 3, "covgram_valgradhess_mvm": 3, "covgram_sm_mvm": 1,
+    "covgram_sparse_mvm": 1, "covgram_matrix": 0, "covgram_block_matrix:gradient": 1, "covgram_block_matrix:value_gradient": 1,
+    "covgram_block_matrix:hessian": 1, "covgram_block_matrix:value_gradient_hessian": 1, "covgram_sm_matrix": 1,
+}
+
+
+@pytest.mark.parametrize("dt", [np.float32, np.float64])
+def test_timer_bracket_counts_one_pair_per_bracketed_launch(cg, dt):
+    """With "time_kernels" = 1 every call leaves only complete event pairs (covgram_ctx_kernel_time returns OK: hipEventElapsedTime
+    refuses a pair whose second event was never recorded) and as many of them as the library always counted."""
+    lib, f = cg._ffi.lib(), cg._ffi
+    h = f._P()
+    f.check(lib.covgram_ctx_create(C.byref(h), 0, None))
+    eps, close = _staged_entry_points(cg, h, dt)
+    try:
+        f.check(lib.covgram_ctx_set_option(h, b"time_kernels", 1))
+        ms, cnt = C.c_double(), C.c_int64()
+        for name, (square_ok, run) in eps.items():
+            for loc in (f.HOST, f.DEVICE):
+                f.check(lib.covgram_ctx_kernel_time(h, C.byref(ms), C.byref(cnt), 1))
+                run(loc, False)
+                f.check(lib.covgram_ctx_kernel_time(h, C.byref(ms), C.byref(cnt), 1))
+                assert cnt.value == _TIMED_LAUNCHES[name] and ms.value >= 0.0, (name, loc, cnt.value)
+        f.check(lib.covgram_ctx_set_option(h, b"time_kernels", 0))
+    finally:
+        close()
+        assert lib.covgram_ctx_destroy(h) == 0

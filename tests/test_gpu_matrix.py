@@ -1,4 +1,4 @@
-"""Matrix(G) entry by entry on every kernel route of covgram_matrix (csrc/api.hip), each route pinned by the info key
+"""Matrix(G) entry by entry on every kernel route of covgram_matrix (csrc/matrix.hip), each route pinned by the info key
 last_matrix_path (route + 10 DM + 1000 VR, include/covgram.h) BEFORE any number is looked at.
 
 Reference: covgram_oracle.matrix on the data as rounded to the dtype (fp64 arithmetic, direct differences).  Error measure: ENTRYWISE,
@@ -218,7 +218,7 @@ def family_cases(cg):
 @pytest.mark.parametrize("dt", [F32, F64])
 @pytest.mark.parametrize("d", [3, 20])
 def test_register_kernel_bit_identical_to_generic(cg, dev, dt, d):
-    """csrc/api.hip says of the register kernel: "same arithmetic in the same order (entries are bit-identical)" to the generic one."""
+    """csrc/matrix.hip says of the register kernel: "same arithmetic in the same order (entries are bit-identical)" to the generic one."""
     n, m = 516, 130
     tally = Tally()
     try:
