@@ -1,0 +1,90 @@
+"""The lazy Gramian product as a differentiable PyTorch operation.
+
+    out = cg.gram_product(k, x, a, y=None, theta=None)      # = gramian(k′, x, y) @ a
+
+is a torch.autograd.Function: the forward pass is the library's own product, and the backward pass of an incoming ḡ (same shape as
+out) is three of its fused passes, each run only when the corresponding input requires a gradient:
+
+    ∂a     = Gᵀ ḡ                                      one product with G.T (G itself when y is None)
+    ∂theta = bilinear_gradient(G, ḡ, a)[1]              hyper-parameter gradients of Σ_t ḡ_tᵀ G a_t (csrc/bilin_grad.hip)
+    ∂x, ∂y = bilinear_input_gradient(G, ḡ, a)           its gradients in the points (csrc/input_grad.hip), cast to their dtype
+
+The backward pass is once differentiable (no second derivatives)."""
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _ffi
+from . import kernels as K
+from .gramian import Gramian, LazyOperator, bilinear_gradient, bilinear_input_gradient, gramian, _bilinear_plan
+
+
+def _refuse(what):
+    return _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"gram_product: gradients with respect to x, y or theta through {what} are not supported "
+                                                     "(the Gramian of gramian(k, x[, y]) on point tensors only; gradients with respect to a work for every operator)")
+
+
+class _GramProduct(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, k, x, a, y, theta):
+        need_x, need_y, need_theta = ctx.needs_input_grad[1], ctx.needs_input_grad[3], ctx.needs_input_grad[4]
+        structural = need_x or need_y or need_theta
+        operator = isinstance(k, LazyOperator) or hasattr(type(k), "mul_")
+        if operator:                                            # an operator built by the caller: differentiable in `a` only
+            if structural or x is not None or y is not None or theta is not None:
+                raise _refuse(type(k).__name__)
+            if not hasattr(type(k), "T") or not hasattr(type(k), "__matmul__"):
+                raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"gram_product: {type(k).__name__} has no transpose (.T) to carry the gradient of a")
+            G = k
+        else:
+            if theta is not None:
+                k = K.with_hyperparameters(k, theta.detach().cpu().numpy())
+            if structural:                                      # what can be refused before anything is built
+                inner = k.k if isinstance(k, K.ScaledInputKernel) and k.diagonal else k
+                _bilinear_plan(inner, "gram_product")
+                for p in (x, y):
+                    if p is not None and not isinstance(p, torch.Tensor):
+                        raise _refuse(f"points of type {type(p).__name__}")
+            same = y is None or y is x
+            xd = x.detach() if isinstance(x, torch.Tensor) else x
+            G = gramian(k, xd, None if same else (y.detach() if isinstance(y, torch.Tensor) else y))
+            if structural and type(G) is not Gramian:
+                raise _refuse(type(G).__name__)
+        ctx.G, ctx.symmetric = G, (not operator) and (y is None or y is x)
+        ctx.shapes = (None if not isinstance(x, torch.Tensor) else (x.shape, x.dtype), None if not isinstance(y, torch.Tensor) else (y.shape, y.dtype),
+                      None if theta is None else (theta.dtype, theta.device))
+        ctx.save_for_backward(a)
+        return G @ a.detach()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gbar):
+        G = ctx.G
+        a, = ctx.saved_tensors
+        gbar = gbar.contiguous()
+        _, need_x, need_a, need_y, need_theta = ctx.needs_input_grad
+        gx = ga = gy = gtheta = None
+        if need_a:
+            ga = ((G if ctx.symmetric else G.T) @ gbar).to(a.dtype).reshape(a.shape)
+        if need_theta:
+            dt, dev = ctx.shapes[2]
+            gtheta = bilinear_gradient(G, gbar, a)[1].to(device=dev, dtype=dt)
+        if need_x or need_y:
+            dX, dY = bilinear_input_gradient(G, gbar, a)
+            if need_x:
+                gx = dX.to(ctx.shapes[0][1]).reshape(ctx.shapes[0][0])
+            if need_y and dY is not None:                       # (y is x: the whole gradient is x's)
+                gy = dY.to(ctx.shapes[1][1]).reshape(ctx.shapes[1][0])
+        return None, gx, ga, gy, gtheta
+
+
+def gram_product(k, x, a, y=None, theta=None):
+    """gramian(k′, x, y) @ a as a differentiable operation: k′ = with_hyperparameters(k, theta) when `theta` (a float64 tensor in
+    hyperparameters(k) order) is given, otherwise k; `a` is (m,) or (m, p).  Gradients flow to whichever of x, y, a and theta require
+    them (module docstring); the points are detached for the forward pass, so the Gramian itself holds no graph.
+
+    When x, y or theta require a gradient the operator has to be the plain Gramian of a kernel bilinear_gradient supports (a simple
+    isotropic kernel or a Sum of them, optionally under ARD / a diagonal ScaledInputKernel) on point tensors: everything else —
+    Toeplitz, Kronecker, block, spectral-mixture and sharded operators among them — raises UnsupportedKernel by name, the kernel and the
+    point types before anything is built.  When only `a` requires a gradient every operator with `.T` works; `k` may then also be an
+    operator that was built already (x, y and theta None)."""
+    return _GramProduct.apply(k, x, a, y, theta)

@@ -389,17 +389,17 @@ class Gramian(LazyOperator):
 
 
 # ----------------------------------------------------------------------------------------------
-# hyper-parameter gradients of bilinear forms (include/covgram.h: covgram_bilinear_grad)
+# hyper-parameter and input gradients of bilinear forms (include/covgram.h: covgram_bilinear_grad, covgram_bilinear_input_grad)
 # ----------------------------------------------------------------------------------------------
 BILINEAR_MAX_NVEC, BILINEAR_MAX_D = _ffi.BILINEAR_MAX_NVEC, _ffi.BILINEAR_MAX_D
 
 
-def _bilinear_term(k):
+def _bilinear_term(k, fn="bilinear_gradient"):
     """(spec, rules) of one simple isotropic term: the covgram_kernel the device runs and, per leaf of hyperparameters(k) in its
     order, the chain rule ("scale", power, c) | ("l", l) | ("param",).  Raises UnsupportedKernel naming what is not supported."""
     rules = []
     def unsupported(what):
-        return _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"bilinear_gradient: {what} is not supported (simple isotropic kernels and Sums of them only)")
+        return _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"{fn}: {what} is not supported (simple isotropic kernels and Sums of them only)")
     def walk(node, power):
         if isinstance(node, K.Product):
             rest = [a for a in node.args if not isinstance(a, K.Constant)]
@@ -434,13 +434,39 @@ def _bilinear_term(k):
     return spec, rules
 
 
-def _bilinear_plan(k):
+def _bilinear_plan(k, fn="bilinear_gradient"):
     """Terms of `k` (a simple kernel, or a Sum of simple kernels and Constants, nested Sums flattened in walk order)."""
     if isinstance(k, K.Sum):
-        return [t for a in k.args for t in _bilinear_plan(a)]
+        return [t for a in k.args for t in _bilinear_plan(a, fn)]
     if isinstance(k, K.Constant):
         return [(None, [("const", k.c)])]
-    return [_bilinear_term(k)]
+    return [_bilinear_term(k, fn)]
+
+
+def _bilinear_setup(fn, G, U, A):
+    """What bilinear_gradient and bilinear_input_gradient (`fn`: the name in the messages) share: the refusals, before any device call,
+    and the weights as the device wants them.  Returns (scaled, plan, U, A, Ut, At): the diagonal ScaledInputKernel in front of the
+    kernel or None, the terms, U (n, nvec) and A (m, nvec) in the Gramian's dtype on its device and their transposes (nvec, n) / (nvec, m)
+    row-major == column-major n × nvec / m × nvec."""
+    if type(G) is not Gramian:
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"{fn}: {type(G).__name__} is not supported (the Gramian of gramian(k, x[, y]) only)")
+    scaled = getattr(G, "scaled_input", None)
+    if scaled is not None and not scaled.diagonal:
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"{fn}: ScaledInputKernel with a full matrix U is not supported")
+    plan = _bilinear_plan(G.k, fn)
+    if scaled is not None and (len(plan) != 1 or plan[0][0] is None):
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"{fn}: ARD over a Sum is not supported")
+    n, m = G.shape
+    d = G.x.shape[1]
+    if d > BILINEAR_MAX_D:
+        raise _ffi.DimensionMismatch(_ffi.EINVAL, f"{fn}: d = {d} exceeds {BILINEAR_MAX_D}")
+    U = _vec_arg(U, n, G.dtype, G.device, "U")
+    A = _vec_arg(A, m, G.dtype, G.device, "A")
+    U = U[:, None] if U.dim() == 1 else U
+    A = A[:, None] if A.dim() == 1 else A
+    if U.dim() != 2 or A.dim() != 2 or U.shape[1] != A.shape[1] or U.shape[1] < 1:
+        raise _ffi.DimensionMismatch(_ffi.EINVAL, f"DimensionMismatch: U has shape {tuple(U.shape)}, A {tuple(A.shape)}: equal column counts expected")
+    return scaled, plan, U, A, U.t().contiguous(), A.t().contiguous()
 
 
 def bilinear_chain_rules(rules, out, scaled=None):
@@ -484,28 +510,12 @@ def bilinear_gradient(G, U, A):
     run in chunks of 32 summed in fp64.  Everything else — a Product of two non-constant kernels, dot-product kernels, Matérn with real
     ν, spectral mixtures, block Gramians, Toeplitz / Kronecker / sparse / Barnes–Hut operators, ShardedGramian — raises
     UnsupportedKernel by name before any device call."""
-    if type(G) is not Gramian:
-        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"bilinear_gradient: {type(G).__name__} is not supported (the Gramian of gramian(k, x[, y]) only)")
-    scaled = getattr(G, "scaled_input", None)
-    if scaled is not None and not scaled.diagonal:
-        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, "bilinear_gradient: ScaledInputKernel with a full matrix U is not supported")
-    plan = _bilinear_plan(G.k)
-    if scaled is not None and (len(plan) != 1 or plan[0][0] is None):
-        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, "bilinear_gradient: ARD over a Sum is not supported")
+    scaled, plan, U, A, Ut, At = _bilinear_setup("bilinear_gradient", G, U, A)
     n, m = G.shape
     d = G.x.shape[1]
-    if d > BILINEAR_MAX_D:
-        raise _ffi.DimensionMismatch(_ffi.EINVAL, f"bilinear_gradient: d = {d} exceeds {BILINEAR_MAX_D}")
-    U = _vec_arg(U, n, G.dtype, G.device, "U")
-    A = _vec_arg(A, m, G.dtype, G.device, "A")
-    U = U[:, None] if U.dim() == 1 else U
-    A = A[:, None] if A.dim() == 1 else A
-    if U.dim() != 2 or A.dim() != 2 or U.shape[1] != A.shape[1] or U.shape[1] < 1:
-        raise _ffi.DimensionMismatch(_ffi.EINVAL, f"DimensionMismatch: U has shape {tuple(U.shape)}, A {tuple(A.shape)}: equal column counts expected")
     nvec = U.shape[1]
     per_dim = 1 if scaled is not None else 0
     nout = 2 + (d if per_dim else 1)
-    Ut, At = U.t().contiguous(), A.t().contiguous()            # (nvec, n) row-major == n × nvec column-major
     lib = _ffi.lib()
     ctx = G._px.ctx.bind_stream()
     py = None if G._py is G._px else G._py.handle
@@ -528,6 +538,68 @@ def bilinear_gradient(G, U, A):
             value += out[0]
         grad += bilinear_chain_rules(rules, out, scaled)
     return torch.tensor(value, dtype=torch.float64), torch.tensor(grad, dtype=torch.float64)
+
+
+def _input_grad_device(spec, px, py, Ut, At, rows, cols, d, device):
+    """Σ_j W_ij 2 (∂k/∂s)_ij (x_i − y_j) for the row points `px` against the column points `py` (None: the row points themselves) as a
+    float64 (rows, d) tensor on `device`: covgram_bilinear_input_grad on chunks of at most 32 of the columns of Ut (nvec, rows) and
+    At (nvec, cols), summed in fp64 on the device."""
+    lib = _ffi.lib()
+    ctx = px.ctx.bind_stream()
+    total = None
+    for c0 in range(0, Ut.shape[0], BILINEAR_MAX_NVEC):
+        nv = min(BILINEAR_MAX_NVEC, Ut.shape[0] - c0)
+        o = torch.empty((rows, d), dtype=torch.float64, device=device)
+        _ffi.check(lib.covgram_bilinear_input_grad(ctx, _ffi.kref(spec), px.handle, None if py is None else py.handle, _ffi._P(Ut[c0:].data_ptr()),
+                                                   max(rows, 1), _ffi._P(At[c0:].data_ptr()), max(cols, 1), nv,
+                                                   C.cast(o.data_ptr(), C.POINTER(C.c_double)), _ffi.DEVICE))
+        total = o if total is None else total.add_(o)
+    return total
+
+
+def _same_tensor(U, A) -> bool:
+    return (isinstance(U, torch.Tensor) and isinstance(A, torch.Tensor) and U.dtype == A.dtype and U.device == A.device
+            and U.data_ptr() == A.data_ptr() and U.shape == A.shape and U.stride() == A.stride())
+
+
+def bilinear_input_gradient(G, U, A):
+    """(dX, dY): the gradients of the bilinear form F = Σ_t U[:, t]ᵀ G A[:, t] = Σ_ij W_ij k(x_i, y_j), W = U Aᵀ, with respect to the
+    points of G, as float64 tensors (n, d) and (m, d) on G's device, in ONE fused pass over the pairs per term and side
+    (csrc/input_grad.hip): with s_ij = |x_i − y_j|²
+        dX[i, c] =  Σ_j W_ij · 2 (∂k/∂s)_ij (x_ic − y_jc)        dY[j, c] = −Σ_i W_ij · 2 (∂k/∂s)_ij (x_ic − y_jc)
+    dY is the same device call with the roles swapped, (Y, X, A, U): an isotropic k is symmetric in its arguments.  When G was built
+    from one point set (G.y is G.x) ONE array is returned and dY is None: dX = call(X, U, A) + call(X, A, U); when U and A are the same
+    tensor (same storage, shape and strides) that is one call, doubled (exact: both routes agree bit for bit).  A pair at distance 0
+    adds exactly 0, also for kernels whose derivative is unbounded there (Exponential, γ-exponential, MaternP(0)).
+
+    `G`, U and A are those of bilinear_gradient: the Gramian of a simple isotropic kernel or of a Sum of them (one launch per term and
+    side, summed in fp64 on the device; a Constant term adds 0); more than 32 columns run in chunks of 32 summed in fp64; everything
+    bilinear_gradient refuses is refused here by name before any device call.  Under a diagonal ScaledInputKernel / ARD the Gramian holds
+    x′ = x ∘ u (u_c = 1 / l_c or U_c), and the result is multiplied by u_c: the gradients are with respect to the points the caller passed.
+    For any other Gramian whose points were transformed when it was built (Warped, Periodic) the gradients are with respect to the
+    points the Gramian HOLDS, G.x and G.y."""
+    same_weights = _same_tensor(U, A)
+    scaled, plan, U, A, Ut, At = _bilinear_setup("bilinear_input_gradient", G, U, A)
+    n, m = G.shape
+    d = G.x.shape[1]
+    symmetric = G._py is G._px
+    dX = torch.zeros((n, d), dtype=torch.float64, device=G.device)
+    dY = None if symmetric else torch.zeros((m, d), dtype=torch.float64, device=G.device)
+    for spec, _ in plan:
+        if spec is None:                                       # a Constant term does not depend on the points
+            continue
+        if symmetric:
+            t = _input_grad_device(spec, G._px, None, Ut, At, n, n, d, G.device)
+            dX += 2.0 * t if same_weights else t + _input_grad_device(spec, G._px, None, At, Ut, n, n, d, G.device)
+        else:
+            dX += _input_grad_device(spec, G._px, G._py, Ut, At, n, m, d, G.device)
+            dY += _input_grad_device(spec, G._py, G._px, At, Ut, m, n, d, G.device)
+    if scaled is not None:                                     # x′ = x ∘ u: ∂/∂x_c = u_c ∂/∂x′_c
+        u = torch.as_tensor(scaled.U, dtype=torch.float64, device=G.device)
+        dX *= u
+        if dY is not None:
+            dY *= u
+    return dX, dY
 
 
 class SpectralMixtureGramian(LazyOperator):
@@ -849,15 +921,27 @@ class SymmetricToeplitz(_ToeplitzBase):
     def __init__(self, vc):
         super().__init__(vc, None, False)
 
+    @property
+    def T(self):
+        return self
+
 
 class Toeplitz(_ToeplitzBase):
     def __init__(self, vc, vr):
         super().__init__(vc, vr, False)
 
+    @property
+    def T(self):
+        return Toeplitz(self.vr, self.vc)                       # first column and first row change places
+
 
 class Circulant(_ToeplitzBase):
     def __init__(self, vc):
         super().__init__(vc, None, True)
+
+    @property
+    def T(self):
+        return Circulant(torch.roll(self.vc.flip(0), 1))        # C[i, j] = vc[(i - j) mod n]: the transpose's first column is vc[-i mod n]
 
 
 class SparseGramian(LazyOperator):

@@ -17,22 +17,10 @@
 //     precision and the wave's sum joins an fp64 total that lane (k mod 64) keeps for output k.  At the end the four waves' totals are
 //     added in fp64 in wave order and written to a slab; bg_reduce_kernel adds the slab in a fixed order.  No atomics.
 //   * a pair with s = 0 adds exactly 0 to out[2 ..]: dk/ds is replaced by 0 there (never 0 * inf), and to out[1] its finite limit.
-#include <algorithm>
-#include <cmath>
-
-#include "driver.hpp"
-#include "profiles.hpp"
+#include "bilin_common.hpp"
 
 namespace covgram {
 
-constexpr int BG_TI = 64;       // rows per workgroup = lanes per wave
-constexpr int BG_WAVES = 4;
-constexpr int BG_L = 128;       // pairs a lane adds in the working precision before the hand-off to fp64 (tests/bilin_grad_ref.py: HANDOFF)
-// columns per lane and tile: 16 in fp32 (64-column tiles, a hand-off every 8 tiles), 8 in fp64 (32-column tiles, every 16): the three
-// per-pair arrays (W, s, W dk/ds) are 3 JPL registers, twice that in fp64
-template <typename T> constexpr int bg_jpl = sizeof(T) == 4 ? 16 : 8;
-constexpr int BG_DS = 16;       // dimensions per LDS slab
-constexpr int BG_MAX_D = 64, BG_MAX_NVEC = 32;
 constexpr int BG_MAX_OUT = 2 + BG_MAX_D;
 
 template <typename T>
@@ -48,48 +36,6 @@ struct BgArgs {
     double* slab;                    // [gridDim.y][gridDim.x][nout]
     int64_t jchunk;                  // columns per blockIdx.y (a multiple of the tile width)
 };
-
-__device__ __forceinline__ float bg_log1p(float x) { return log1pf(x); }
-__device__ __forceinline__ double bg_log1p(double x) { return log1p(x); }
-
-// k, dk/ds (s raw; 0 where the scaled s is 0) and dk/dparam of one pair
-template <typename T>
-__device__ __forceinline__ void bg_jet(int family, T sr, const KParams<T>& kp, T cpar, T& v, T& ds, T& dp) {
-    const T s = sr * kp.gamma2;
-    T f, f1, f2, fp = (T)0;
-    switch (family) {
-        case COVGRAM_EQ: DPhi<COVGRAM_EQ, T>::eval(s, kp, f, f1, f2); break;
-        case COVGRAM_EXP: DPhi<COVGRAM_EXP, T>::eval(s, kp, f, f1, f2); break;
-        case COVGRAM_RQ: {
-            DPhi<COVGRAM_RQ, T>::eval(s, kp, f, f1, f2);
-            const T x = s * kp.c0;                                  // s / (2 alpha)
-            fp = f * (x * cg_rcp((T)1 + x) - bg_log1p(x));          // phi (s / (2 alpha + s) - log1p(s / (2 alpha)))
-            break;
-        }
-        case COVGRAM_GAMMAEXP: {
-            DPhi<COVGRAM_GAMMAEXP, T>::eval(s, kp, f, f1, f2);
-            const T sg = (kp.param == (T)0) ? (T)1 : pow_pos(s, kp.param);
-            fp = s == (T)0 ? (T)0 : (T)-0.25 * f * sg * cg_log(s);  // -1/4 phi s^(gamma/2) log s; 0 at s = 0
-            break;
-        }
-        case COVGRAM_CAUCHY: DPhi<COVGRAM_CAUCHY, T>::eval(s, kp, f, f1, f2); break;
-        case COVGRAM_IMQ: {
-            DPhi<COVGRAM_IMQ, T>::eval(s, kp, f, f1, f2);
-            fp = -cpar * f * cg_rcp(s + kp.param);                  // -c (s + c^2)^(-3/2)
-            break;
-        }
-        default: DPhi<COVGRAM_MATERNP, T>::eval(s, kp, f, f1, f2); break;
-    }
-    v = f;
-    if (kp.power != 1) {                                            // (phi^q)' = q phi^(q-1) phi', in s and in the parameter alike
-        const T fq1 = ipow(f, kp.power - 1);
-        const T mult = (T)kp.power * fq1;
-        v = fq1 * f; f1 *= mult; fp *= mult;
-    }
-    v *= kp.scale;
-    dp = fp * kp.scale;
-    ds = s == (T)0 ? (T)0 : f1 * kp.gamma2 * kp.scale;             // s = 0: the pair's differences are all 0 (NaN still propagates)
-}
 
 template <typename T>
 __device__ __forceinline__ T bg_wave_sum(T x) {
@@ -268,15 +214,9 @@ static int bg_run(covgram_ctx* ctx, const HostKernel& hk, const covgram_points* 
     g.nvec = nvec; g.family = hk.k.family; g.per_dim = per_dim; g.nout = nout;
     g.cpar = (T)hk.k.param;
     g.kp = cast_params<T>(hk.kp);
-    // column split: enough workgroups for every CU, chunks of at least one hand-off interval
-    constexpr int BG_TJ = bg_jpl<T> * BG_WAVES, BG_KT = BG_L / bg_jpl<T>;
+    constexpr int BG_TJ = bg_jpl<T> * BG_WAVES;
     const int64_t rowtiles = (n + BG_TI - 1) / BG_TI;
-    const int64_t ntiles = (m + BG_TJ - 1) / BG_TJ;
-    int64_t jsplit = std::min<int64_t>(((int64_t)ctx->num_cus * 8 + rowtiles - 1) / rowtiles, std::max<int64_t>(1, ntiles / BG_KT));
-    jsplit = std::max<int64_t>(1, std::min<int64_t>(jsplit, 65535));
-    const int64_t tiles_per = (ntiles + jsplit - 1) / jsplit;
-    jsplit = (ntiles + tiles_per - 1) / tiles_per;
-    g.jchunk = tiles_per * BG_TJ;
+    const int64_t jsplit = bg_column_split<T>(ctx, rowtiles, m, &g.jchunk);
     CG_REQUIRE(rowtiles <= 0x7fffffff, COVGRAM_EUNSUPPORTED, "bilinear_grad: n = %lld exceeds the grid", (long long)n);
     const int64_t nblk = rowtiles * jsplit;
     void* slab;
@@ -298,26 +238,11 @@ using namespace covgram;
 
 extern "C" int covgram_bilinear_grad(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, const void* U, int64_t ldu,
                                      const void* A, int64_t lda, int32_t nvec, int32_t per_dim, double* out, int32_t loc) {
-    CG_REQUIRE(ctx && k && X, COVGRAM_EINVAL, "NULL argument");
-    if (!Y) Y = X;
-    CG_REQUIRE(X->ctx == ctx && Y->ctx == ctx, COVGRAM_EINVAL, "points belong to a different ctx");
-    CG_REQUIRE(X->dtype == Y->dtype, COVGRAM_EINVAL, "X and Y have different dtypes");
-    CG_REQUIRE(X->d == Y->d, COVGRAM_EINVAL, "DimensionMismatch: inputs have to have the same length (%d and %d)", X->d, Y->d);
-    CG_REQUIRE(loc == COVGRAM_HOST || loc == COVGRAM_DEVICE, COVGRAM_EINVAL, "unknown loc %d", loc);
-    CG_REQUIRE(k->family != COVGRAM_COMPOSITE, COVGRAM_EUNSUPPORTED, "bilinear_grad: composite kernels are handled term by term on the host");
-    CG_REQUIRE(k->family >= 0 && k->family < COVGRAM_NFAMILY, COVGRAM_EUNSUPPORTED, "unknown kernel family %d", k->family);
-    CG_REQUIRE(k->family != COVGRAM_DOT && k->family != COVGRAM_EXPDOT && k->family != COVGRAM_ASINDOT, COVGRAM_EUNSUPPORTED,
-               "bilinear_grad: dot-product kernels have no hyper-parameter gradient path");
-    CG_REQUIRE(k->family != COVGRAM_MATERN, COVGRAM_EUNSUPPORTED, "bilinear_grad: Matern with real nu is not supported (half-integer nu: MaternP)");
-    CG_REQUIRE(nvec >= 1 && nvec <= BG_MAX_NVEC, COVGRAM_EINVAL, "bilinear_grad: nvec = %d is outside 1 .. %d", nvec, BG_MAX_NVEC);
-    CG_REQUIRE(X->d >= 1 && X->d <= BG_MAX_D, COVGRAM_EINVAL, "bilinear_grad: d = %d is outside 1 .. %d", X->d, BG_MAX_D);
-    CG_REQUIRE(out != nullptr, COVGRAM_EINVAL, "out is NULL");
+    int rc = bg_check_args("bilinear_grad", ctx, k, X, &Y, U, ldu, A, lda, nvec, out, loc);
+    if (rc) return rc;
     const int64_t n = X->n, m = Y->n;
-    CG_REQUIRE(ldu >= n && lda >= m, COVGRAM_EINVAL, "DimensionMismatch: ldu=%lld < n=%lld or lda=%lld < m=%lld", (long long)ldu, (long long)n,
-               (long long)lda, (long long)m);
-    CG_REQUIRE((U != nullptr || n == 0) && (A != nullptr || m == 0), COVGRAM_EINVAL, "U or A is NULL");
     HostKernel hk;
-    int rc = make_host_kernel(k, X->dtype, true, &hk);
+    rc = make_host_kernel(k, X->dtype, true, &hk);
     if (rc) return rc;
     const int nout = 2 + (per_dim ? X->d : 1);
     const size_t ts = dtype_size(X->dtype);
@@ -331,14 +256,10 @@ extern "C" int covgram_bilinear_grad(covgram_ctx* ctx, const covgram_kernel* k, 
     double* o_dev = out;
     int64_t ldu_d = ldu, lda_d = lda;
     if (loc == COVGRAM_HOST) {
-        void *su, *so;
-        const size_t ub = (((size_t)n * nvec * ts) + 255) & ~(size_t)255;
-        rc = ws_reserve(ctx, 2, ub + (size_t)m * nvec * ts, &su); if (rc) return rc;
+        void* so;
+        rc = bg_stage_weights(ctx, n, m, nvec, ts, &u_dev, &ldu_d, &a_dev, &lda_d); if (rc) return rc;
         rc = ws_reserve(ctx, 3, (size_t)nout * sizeof(double), &so); if (rc) return rc;
-        void* sa = (char*)su + ub;
-        CG_CHECK_HIP(hipMemcpy2DAsync(su, (size_t)n * ts, U, (size_t)ldu * ts, (size_t)n * ts, nvec, hipMemcpyHostToDevice, ctx->stream));
-        CG_CHECK_HIP(hipMemcpy2DAsync(sa, (size_t)m * ts, A, (size_t)lda * ts, (size_t)m * ts, nvec, hipMemcpyHostToDevice, ctx->stream));
-        u_dev = su; a_dev = sa; o_dev = (double*)so; ldu_d = n; lda_d = m;
+        o_dev = (double*)so;
     }
     rc = X->dtype == COVGRAM_F32 ? bg_run<float>(ctx, hk, X, Y, u_dev, ldu_d, a_dev, lda_d, nvec, per_dim ? 1 : 0, nout, o_dev)
                                  : bg_run<double>(ctx, hk, X, Y, u_dev, ldu_d, a_dev, lda_d, nvec, per_dim ? 1 : 0, nout, o_dev);

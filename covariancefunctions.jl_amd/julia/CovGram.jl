@@ -806,4 +806,18 @@ function bilinear_grad(G::Gramian{T}, U::StridedVecOrMat{T}, A::StridedVecOrMat{
     return out
 end
 
+# --- the gradient of the same bilinear form with respect to the ROW points in one pass (covgram_bilinear_input_grad): a d × n Float64 matrix
+#     whose column i is Σ_j W_ij 2 (∂k/∂s)_ij (x_i − y_j), the column side held fixed (also for G.x === G.y: add the call with U and A swapped)
+function bilinear_input_grad(G::Gramian{T}, U::StridedVecOrMat{T}, A::StridedVecOrMat{T}) where {T <: DevFloat}
+    spec = device_kernel_for(G.k)
+    spec isa CKernel || throw(ArgumentError("bilinear_input_grad: simple isotropic kernels only"))
+    n, m = size(G)
+    size(U, 1) == n && size(A, 1) == m && size(U, 2) == size(A, 2) || throw(DimensionMismatch("bilinear_input_grad: U is n × nvec, A is m × nvec"))
+    X = points(G.x, T); Y = G.x === G.y ? X : points(G.y, T)
+    dX = Matrix{Float64}(undef, length(first(G.x)), n)
+    check(ccall((:covgram_bilinear_input_grad, libcovgram), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int32, Ptr{Float64}, Int32),
+                ctx(), kref(spec), X.handle, Y.handle, U, max(stride(U, 2), n), A, max(stride(A, 2), m), size(U, 2), dX, HOST))
+    return dX
+end
+
 end # module

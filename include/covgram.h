@@ -72,7 +72,8 @@ extern "C" {
                                covgram_bcg_init, covgram_bcg_step, covgram_bcg_update, covgram_bcg_direction and the
                                COVGRAM_BCG_* layout of their state (batched CG on a block of right-hand sides);
                                the covgram_sm_* handle (SpectralMixture Gramians: one fused product and Matrix(G));
-                               covgram_bilinear_grad (hyper-parameter gradients of bilinear forms in one pass).
+                               covgram_bilinear_grad (hyper-parameter gradients of bilinear forms in one pass);
+                               covgram_bilinear_input_grad (their gradients with respect to the row points in one pass).
                                A binding checks covgram_version() against the header it mirrors at load time */
 
 typedef enum covgram_status {
@@ -637,6 +638,22 @@ int covgram_sm_destroy(covgram_sm* S);
  *   and never synchronises.  Option "time_kernels" brackets the pair kernel and its reduction. */
 int covgram_bilinear_grad(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, const void* U, int64_t ldu,
                           const void* A, int64_t lda, int32_t nvec, int32_t per_dim, double* out, int32_t loc);
+
+/* ---- Gradients of the bilinear forms sum_t u_t' G a_t with respect to the ROW points in ONE pass over the pairs (csrc/input_grad.hip),
+ * W = U A' as in covgram_bilinear_grad:
+ *     dX[i d + c] = sum_j W_ij 2 (dk/ds)_ij (x_ic - y_jc)        i < n, c < d
+ * the partial derivative of F(X, Y) = sum_ij W_ij k(x_i, y_j) in x_ic with the column side held FIXED, also when Y == NULL (Y = X): an
+ *   isotropic k is symmetric in its arguments, so the derivative in the column points is the call with (X, U) and (Y, A) swapped, and the
+ *   full derivative of the symmetric case is call(X, NULL, U, A) + call(X, NULL, A, U).
+ * `dX` holds n d DOUBLES, point-major like the points, whatever the points' dtype (host or device memory, `loc`, which also applies to U
+ *   and A); nothing outside them is written.  s is the RAW squared distance by direct differences: dk/ds includes scale, power and lengthscale.
+ * U, A, k, nvec and d: exactly as covgram_bilinear_grad, with the same status codes.
+ * A pair at distance 0 (with Y == NULL the whole diagonal) adds exactly 0 for every family, also those whose dk/ds is unbounded at 0.
+ * A lane owns a row: it adds at most 128 pairs in the points' precision before the sum continues in fp64, and partial sums are added in a
+ *   fixed order, no atomics: two calls with the same arguments agree bit for bit.  m == 0 gives zeros, n == 0 returns at once.  With
+ *   loc == DEVICE the call is stream-ordered and never synchronises.  Option "time_kernels" brackets the pair kernel and its reduction. */
+int covgram_bilinear_input_grad(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, const void* U, int64_t ldu,
+                                const void* A, int64_t lda, int32_t nvec, double* dX, int32_t loc);
 
 /* Test hook: the double-precision parameter block handed to the device kernels for `k`
  * (out45[0..8] = gamma, gamma^2, scale, param, c0, 2p+1, Taylor bound, d1, d2; then the MaternP tables
