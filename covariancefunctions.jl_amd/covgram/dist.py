@@ -330,7 +330,8 @@ class ShardedGramian:
         if alpha == 1.0 and beta == 0.0:
             return self.matmul(a, out=y)
         t = self.matmul(a)
-        return y.copy_(alpha * t) if beta == 0 else y.mul_(beta).add_(t, alpha=alpha)
+        from .gramian import _axpby_
+        return _axpby_(y, t, alpha, beta)
 
     @property
     def dtype(self):

@@ -21,7 +21,7 @@ import torch
 
 from . import _ffi
 from . import kernels as K
-from .gramian import Gramian, LazyOperator, SpectralMixtureGramian, _dtype_code
+from .gramian import Gramian, LazyOperator, SpectralMixtureGramian, _axpby_, _dtype_code
 
 DEFAULT_MAX_CHOLESKY_SIZE = 2 ** 14     # src/gramian.jl:201
 DEFAULT_TOL = 1e-6                      # src/gramian.jl:202
@@ -220,8 +220,7 @@ class PivotedCholeskyPreconditioner(LazyOperator):
         return y if vec else y.t()
 
     def mul_(self, y, a, alpha=1.0, beta=0.0):
-        t = self(a)
-        return y.mul_(beta).add_(t, alpha=alpha) if beta != 0 else y.copy_(alpha * t)
+        return _axpby_(y, self(a), alpha, beta)
 
     def logdet(self) -> torch.Tensor:
         """log det(L L' + D) (a 0-dim device tensor)."""

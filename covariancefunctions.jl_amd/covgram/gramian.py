@@ -172,7 +172,27 @@ def _as_points(x, device=None, dtype=None) -> torch.Tensor:
     return t.contiguous()
 
 
-class _Points:
+class _OwnsHandle:
+    """Owner of ONE library handle, a plain ctypes.c_void_p in the attribute named `_slot`, which the C entry named `_destroy` frees:
+    at most once, and silently while the interpreter shuts down."""
+
+    _destroy = None
+    _slot = "handle"
+
+    def _release(self):
+        h = getattr(self, self._slot, None)
+        setattr(self, self._slot, None)
+        if h:
+            getattr(_ffi.lib(), self._destroy)(h)
+
+    def __del__(self):
+        try:
+            self._release()
+        except Exception:
+            pass
+
+
+class _Points(_OwnsHandle):
     """Device-resident point set + its covgram_points handle (borrowing the tensor's memory).
 
     The C ABI's contract for borrowed memory is "unchanged while the handle lives" (the library caches the point set's max norm
@@ -180,14 +200,16 @@ class _Points:
     its points, so this wrapper watches torch's in-place version counter and re-creates the handle when the tensor was written
     to since the handle was made."""
 
+    _destroy, _slot = "covgram_points_destroy", "_h"
+
     def __init__(self, t: torch.Tensor):
         self.t = t
         self.ctx = get_ctx(t.device)
-        self._h = _ffi._P()
         self._create()
 
     def _create(self):
         t = self.t
+        self._h = _ffi._P()
         _ffi.check(_ffi.lib().covgram_points_create(self.ctx.handle, C.byref(self._h), _ffi._P(t.data_ptr()), t.shape[0],
                                                     t.shape[1], _dtype_code(t.dtype), _ffi.DEVICE))
         self._ver = t._version
@@ -195,18 +217,9 @@ class _Points:
     @property
     def handle(self):
         if self.t._version != self._ver:                      # points were modified in place: norms / fragments are stale
-            _ffi.lib().covgram_points_destroy(self._h)
-            self._h = _ffi._P()
+            self._release()
             self._create()
         return self._h
-
-    def __del__(self):
-        try:
-            if self._h:
-                _ffi.lib().covgram_points_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
 
 
 def _vec_arg(a: torch.Tensor, n: int, dtype, device, what: str) -> torch.Tensor:
@@ -215,6 +228,43 @@ def _vec_arg(a: torch.Tensor, n: int, dtype, device, what: str) -> torch.Tensor:
     if a.shape[0] != n:
         raise _ffi.DimensionMismatch(_ffi.EINVAL, f"DimensionMismatch: {what} has length {a.shape[0]}, expected {n}")
     return a.to(device=device, dtype=dtype)
+
+
+def _rhs(op, y: torch.Tensor, a, what: str = "a") -> torch.Tensor:
+    """The right-hand side of op.mul_(y, a): `a` in op's dtype on op's device, after the one shape check of every product."""
+    a = _vec_arg(a, op.shape[1], op.dtype, op.device, what)
+    if y.shape[0] != op.shape[0] or y.dtype != op.dtype or tuple(y.shape[1:]) != tuple(a.shape[1:]):
+        raise _ffi.DimensionMismatch(_ffi.EINVAL, f"DimensionMismatch: y has shape {tuple(y.shape)}, expected ({op.shape[0]}, ...) of {op.dtype}")
+    return a
+
+
+def _staged(y: torch.Tensor, a: torch.Tensor, beta, call) -> torch.Tensor:
+    """The one place where a and y of a product y ← α A a + β y meet a C entry, as column-major memory: runs
+    call(a_ptr, lda, y_ptr, ldy, nrhs) once and returns y.  A vector is passed contiguous; a matrix (m, p) as its transpose's storage,
+    (p, m) row-major == m × p column-major.  The library writes into y itself when y's memory already has that layout; otherwise into a
+    staging tensor that is copied back, and that holds y's values only when β ≠ 0 (nothing reads them otherwise).  a is always staged
+    before y is written and every C entry accepts any overlap of a and y, so y may alias a.  No columns: y is returned untouched, call
+    does not run (the ABI requires nrhs >= 1).  Touches tensor layouts and pointers only: no context, no library, no device API."""
+    vec = a.dim() == 1
+    if not vec and a.shape[1] == 0:
+        return y
+    at, yt = (a, y) if vec else (a.t(), y.t())
+    a_c = at.contiguous()
+    if yt.is_contiguous():
+        y_c = yt
+    elif beta == 0 and not vec:
+        y_c = torch.empty(yt.shape, dtype=y.dtype, device=y.device)
+    else:
+        y_c = yt.contiguous()
+    call(a_c.data_ptr(), max(a.shape[0], 1), y_c.data_ptr(), max(y.shape[0], 1), 1 if vec else a.shape[1])
+    if y_c is not yt:
+        yt.copy_(y_c)
+    return y
+
+
+def _axpby_(y: torch.Tensor, t: torch.Tensor, alpha, beta) -> torch.Tensor:
+    """y ← α t + β y for a product t that was computed in full before y is written (y may alias the product's input)."""
+    return y.copy_(alpha * t) if beta == 0 else y.mul_(beta).add_(t, alpha=alpha)
 
 
 def _overlaps(y: torch.Tensor, a: torch.Tensor) -> bool:
@@ -269,16 +319,15 @@ def mul_(y, A: LazyOperator, a, alpha=1.0, beta=0.0):
     return A.mul_(y, a, alpha, beta)
 
 
-class Gramian(LazyOperator):
-    """Lazy kernel matrix holding (k, x, y) (src/gramian.jl:10-21); O(1) construction, O(n m d) `mul!`."""
+class _PointPairGramian(LazyOperator):
+    """What the lazy Gramians of ONE kernel on two point sets share: the points and their handles, symmetry, the transpose, Matrix(G)
+    and indexing.  A subclass says how to build its kind of operator on other points (_on) and makes the one library call of Matrix(G)
+    (_matrix)."""
 
     def __init__(self, k, x, y=None):
         self.k = k
         self.x = _as_points(x)
-        if y is None or y is x:
-            self.y = self.x
-        else:
-            self.y = _as_points(y, device=self.x.device, dtype=self.x.dtype)
+        self.y = self.x if (y is None or y is x) else _as_points(y, device=self.x.device, dtype=self.x.dtype)
         if self.x.shape[1] != self.y.shape[1]:
             raise _ffi.DimensionMismatch(_ffi.EINVAL, f"inputs have to have the same length: {self.x.shape[1]}, {self.y.shape[1]}")
         self.dtype = self.x.dtype                              # gramian_eltype: T follows the data (src/gramian.jl:30-33)
@@ -287,15 +336,53 @@ class Gramian(LazyOperator):
         self._px = _Points(self.x)
         self._py = self._px if self.y is self.x else _Points(self.y)
 
+    def _on(self, xi, yj):
+        """The same kind of operator, of the same kernel, on the points xi and yj."""
+        raise NotImplementedError
+
+    def _matrix(self, out, ldo):
+        """The library call that writes the column-major n × m matrix (leading dimension ldo) to the device pointer `out`."""
+        raise NotImplementedError
+
     # -- structure ------------------------------------------------------------------------------
     @property
     def T(self):
-        return Gramian(self.k, self.y, self.x)                 # src/gramian.jl:116-117
+        return self._on(self.y, self.x)                        # src/gramian.jl:116-117
 
     adjoint = T
 
     def issymmetric(self):
         return self.x is self.y or (self.x.shape == self.y.shape and bool(torch.equal(self.x, self.y)))   # :132
+
+    def to_dense(self):
+        """Matrix(G) (src/gramian.jl:102-114) on the device, with the per-pair arithmetic of the product."""
+        n, m = self.shape
+        buf = torch.empty((m, n), dtype=self.dtype, device=self.device)   # column-major n×m
+        if n * m:
+            self._px.ctx.bind_stream()
+            self._matrix(_ffi._P(buf.data_ptr()), n)
+        return buf.t()
+
+    def __getitem__(self, ij):
+        """G[i, j] = k(x[i], y[j]) and sub-block indexing (src/gramian.jl:37-52), evaluated on the device from the sliced point sets."""
+        i, j = ij
+        xi = self.x[i] if not isinstance(i, int) else self.x[i:i + 1]
+        yj = self.y[j] if not isinstance(j, int) else self.y[j:j + 1]
+        sub = self._on(xi.reshape(-1, self.x.shape[1]), yj.reshape(-1, self.y.shape[1])).to_dense()
+        if isinstance(i, int) and isinstance(j, int):
+            return sub[0, 0]
+        if isinstance(i, int):
+            return sub[0]
+        if isinstance(j, int):
+            return sub[:, 0]
+        return sub
+
+
+class Gramian(_PointPairGramian):
+    """Lazy kernel matrix holding (k, x, y) (src/gramian.jl:10-21); O(1) construction, O(n m d) `mul!`."""
+
+    def _on(self, xi, yj):
+        return Gramian(self.k, xi, yj)
 
     def isposdef(self):
         return isinstance(self.k, (K.MercerKernel, K.MultiKernel)) and self.issymmetric()               # :135-137
@@ -310,30 +397,11 @@ class Gramian(LazyOperator):
     # -- products ---------------------------------------------------------------------------------
     def mul_(self, y, a, alpha=1.0, beta=0.0):
         """src/gramian.jl:78-99.  β == 0 ⇒ y's previous contents (NaN included) are ignored."""
-        n, m = self.shape
-        a = _vec_arg(a, m, self.dtype, self.device, "a")
-        if y.shape[0] != n or y.dtype != self.dtype or tuple(y.shape[1:]) != tuple(a.shape[1:]):
-            raise _ffi.DimensionMismatch(_ffi.EINVAL, f"DimensionMismatch: y has shape {tuple(y.shape)}, expected ({n}, ...) of {self.dtype}")
+        a = _rhs(self, y, a)
         spec = self._spec()
         ctx = self._px.ctx.bind_stream()
-        lib = _ffi.lib()
-        if a.dim() == 1:
-            a_c = a.contiguous()
-            y_c = y if y.is_contiguous() else y.contiguous()
-            _ffi.check(lib.covgram_mvm(ctx, _ffi.kref(spec), self._px.handle, self._py.handle, _ffi._P(a_c.data_ptr()), max(m, 1),
-                                       _ffi._P(y_c.data_ptr()), max(n, 1), 1, float(alpha), float(beta), _ffi.DEVICE))
-            if y_c is not y:
-                y.copy_(y_c)
-            return y
-        p = a.shape[1]
-        a_cm = a.t().contiguous()                              # (p, m) row-major == m×p column-major
-        direct = y.t().is_contiguous()
-        y_cm = y.t() if direct else y.t().contiguous()
-        _ffi.check(lib.covgram_mvm(ctx, _ffi.kref(spec), self._px.handle, self._py.handle, _ffi._P(a_cm.data_ptr()), max(m, 1),
-                                   _ffi._P(y_cm.data_ptr()), max(n, 1), p, float(alpha), float(beta), _ffi.DEVICE))
-        if not direct:
-            y.copy_(y_cm.t())
-        return y
+        return _staged(y, a, beta, lambda ap, lda, yp, ldy, nrhs: _ffi.check(_ffi.lib().covgram_mvm(
+            ctx, _ffi.kref(spec), self._px.handle, self._py.handle, _ffi._P(ap), lda, _ffi._P(yp), ldy, nrhs, float(alpha), float(beta), _ffi.DEVICE)))
 
     # -- multi-GPU symmetric form (include/covgram.h: covgram_mvm_sym_partial) ---------------------
     def sym_partial_supported(self, world: int = 1) -> bool:
@@ -363,29 +431,8 @@ class Gramian(LazyOperator):
                                                       _ffi._P(a_c.data_ptr()), _ffi._P(y.data_ptr()), int(rank), int(world)))
         return y
 
-    def to_dense(self):
-        """Matrix(G) (src/gramian.jl:102-114) on the device."""
-        n, m = self.shape
-        buf = torch.empty((m, n), dtype=self.dtype, device=self.device)   # column-major n×m
-        if n * m:
-            spec = self._spec()
-            ctx = self._px.ctx.bind_stream()
-            _ffi.check(_ffi.lib().covgram_matrix(ctx, _ffi.kref(spec), self._px.handle, self._py.handle, _ffi._P(buf.data_ptr()), n, _ffi.DEVICE))
-        return buf.t()
-
-    def __getitem__(self, ij):
-        """G[i, j] = k(x[i], y[j]) and sub-block indexing (src/gramian.jl:37-52), evaluated on the device."""
-        i, j = ij
-        xi = self.x[i] if not isinstance(i, int) else self.x[i:i + 1]
-        yj = self.y[j] if not isinstance(j, int) else self.y[j:j + 1]
-        sub = Gramian(self.k, xi.reshape(-1, self.x.shape[1]), yj.reshape(-1, self.y.shape[1])).to_dense()
-        if isinstance(i, int) and isinstance(j, int):
-            return sub[0, 0]
-        if isinstance(i, int):
-            return sub[0]
-        if isinstance(j, int):
-            return sub[:, 0]
-        return sub
+    def _matrix(self, out, ldo):
+        _ffi.check(_ffi.lib().covgram_matrix(self._px.ctx.handle, _ffi.kref(self._spec()), self._px.handle, self._py.handle, out, ldo, _ffi.DEVICE))
 
 
 # ----------------------------------------------------------------------------------------------
@@ -602,45 +649,24 @@ def bilinear_input_gradient(G, U, A):
     return dX, dY
 
 
-class SpectralMixtureGramian(LazyOperator):
+class SpectralMixtureGramian(_OwnsHandle, _PointPairGramian):
     """Lazy Gramian of a spectral mixture Σ_q w_q Cosine(μ_q) ARD(EQ(), l_q) (src/stationary.jl:213-217), a GenericInput kernel in the
     reference's terms: holds (k, x, y), the point handles and the covgram_sm handle with the mixture's parameters; `mul!` and
     Matrix(G) are ONE fused pass each (covgram_sm_mvm / covgram_sm_matrix).  `gramian` builds it for exactly the kernels that
     kernels.spectral_mixture_spec recognises and kernels.device_spec does not."""
 
+    _destroy = "covgram_sm_destroy"
+
     def __init__(self, k, x, y=None, spec=None):
-        self.k = k
-        self.x = _as_points(x)
-        self.y = self.x if (y is None or y is x) else _as_points(y, device=self.x.device, dtype=self.x.dtype)
-        if self.x.shape[1] != self.y.shape[1]:
-            raise _ffi.DimensionMismatch(_ffi.EINVAL, f"inputs have to have the same length: {self.x.shape[1]}, {self.y.shape[1]}")
-        d = self.x.shape[1]
-        self.w, self.mu, self.inv_l = spec if spec is not None else K.require_sm_spec(k, d)   # refusals come before any device call
-        self.dtype, self.device = self.x.dtype, self.x.device
-        self.shape = (self.x.shape[0], self.y.shape[0])
-        self._px = _Points(self.x)
-        self._py = self._px if self.y is self.x else _Points(self.y)
+        self.w, self.mu, self.inv_l = spec if spec is not None else K.require_sm_spec(k, _point_dim(x))   # refusals come before any device call
+        super().__init__(k, x, y)
         self.handle = _ffi._P()
         as_d = lambda v: np.ascontiguousarray(v, dtype=np.float64).ctypes.data_as(C.POINTER(C.c_double))
-        _ffi.check(_ffi.lib().covgram_sm_create(self._px.ctx.bind_stream(), C.byref(self.handle), int(self.w.shape[0]), int(d), as_d(self.w),
+        _ffi.check(_ffi.lib().covgram_sm_create(self._px.ctx.bind_stream(), C.byref(self.handle), int(self.w.shape[0]), int(self.x.shape[1]), as_d(self.w),
                                                 as_d(self.mu), as_d(self.inv_l), _dtype_code(self.dtype)))
 
-    def __del__(self):
-        try:
-            if self.handle:
-                _ffi.lib().covgram_sm_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
-
-    @property
-    def T(self):
-        return SpectralMixtureGramian(self.k, self.y, self.x, (self.w, self.mu, self.inv_l))   # cos is even: k(y, x) = k(x, y)
-
-    adjoint = T
-
-    def issymmetric(self):
-        return self.x is self.y or (self.x.shape == self.y.shape and bool(torch.equal(self.x, self.y)))
+    def _on(self, xi, yj):
+        return SpectralMixtureGramian(self.k, xi, yj, (self.w, self.mu, self.inv_l))   # the transpose too: cos is even, k(y, x) = k(x, y)
 
     def isposdef(self):
         return self.issymmetric() and bool(np.all(self.w >= 0))
@@ -653,54 +679,13 @@ class SpectralMixtureGramian(LazyOperator):
 
     def mul_(self, y, a, alpha=1.0, beta=0.0):
         """y ← α G a + β y for a vector or a matrix a; β == 0 ⇒ y's previous contents (NaN included) are ignored."""
-        n, m = self.shape
-        a = _vec_arg(a, m, self.dtype, self.device, "a")
-        if y.shape[0] != n or y.dtype != self.dtype or tuple(y.shape[1:]) != tuple(a.shape[1:]):
-            raise _ffi.DimensionMismatch(_ffi.EINVAL, f"DimensionMismatch: y has shape {tuple(y.shape)}, expected ({n}, ...) of {self.dtype}")
+        a = _rhs(self, y, a)
         self._px.ctx.bind_stream()
-        fn = _ffi.lib().covgram_sm_mvm
-        if a.dim() == 1:
-            a_c = a.contiguous()
-            y_c = y if y.is_contiguous() else y.contiguous()
-            _ffi.check(fn(self.handle, self._px.handle, self._py.handle, _ffi._P(a_c.data_ptr()), max(m, 1), _ffi._P(y_c.data_ptr()), max(n, 1), 1,
-                          float(alpha), float(beta), _ffi.DEVICE))
-            if y_c is not y:
-                y.copy_(y_c)
-            return y
-        p = a.shape[1]
-        if p == 0:                                             # no columns: nothing to do (the ABI requires nrhs >= 1)
-            return y
-        a_cm = a.t().contiguous()                              # (p, m) row-major == m×p column-major
-        direct = y.t().is_contiguous()
-        y_cm = y.t() if direct else y.t().contiguous()
-        _ffi.check(fn(self.handle, self._px.handle, self._py.handle, _ffi._P(a_cm.data_ptr()), max(m, 1), _ffi._P(y_cm.data_ptr()), max(n, 1), p,
-                      float(alpha), float(beta), _ffi.DEVICE))
-        if not direct:
-            y.copy_(y_cm.t())
-        return y
+        return _staged(y, a, beta, lambda ap, lda, yp, ldy, nrhs: _ffi.check(_ffi.lib().covgram_sm_mvm(
+            self.handle, self._px.handle, self._py.handle, _ffi._P(ap), lda, _ffi._P(yp), ldy, nrhs, float(alpha), float(beta), _ffi.DEVICE)))
 
-    def to_dense(self):
-        """Matrix(G) on the device, with the per-pair arithmetic of the product."""
-        n, m = self.shape
-        buf = torch.empty((m, n), dtype=self.dtype, device=self.device)   # column-major n×m
-        if n * m:
-            self._px.ctx.bind_stream()
-            _ffi.check(_ffi.lib().covgram_sm_matrix(self.handle, self._px.handle, self._py.handle, _ffi._P(buf.data_ptr()), n, _ffi.DEVICE))
-        return buf.t()
-
-    def __getitem__(self, ij):
-        """G[i, j] = k(x[i], y[j]) and sub-block indexing, evaluated on the device from the sliced point sets."""
-        i, j = ij
-        xi = self.x[i] if not isinstance(i, int) else self.x[i:i + 1]
-        yj = self.y[j] if not isinstance(j, int) else self.y[j:j + 1]
-        sub = SpectralMixtureGramian(self.k, xi.reshape(-1, self.x.shape[1]), yj.reshape(-1, self.y.shape[1]), (self.w, self.mu, self.inv_l)).to_dense()
-        if isinstance(i, int) and isinstance(j, int):
-            return sub[0, 0]
-        if isinstance(i, int):
-            return sub[0]
-        if isinstance(j, int):
-            return sub[:, 0]
-        return sub
+    def _matrix(self, out, ldo):
+        _ffi.check(_ffi.lib().covgram_sm_matrix(self.handle, self._px.handle, self._py.handle, out, ldo, _ffi.DEVICE))
 
 
 BLOCK_MATRIX_MAX_D = 64     # covgram_block_matrix, gradient kinds: rows in registers (include/covgram.h)
@@ -735,14 +720,16 @@ class BlockGramian(LazyOperator):
         self.value = isinstance(g, K.ValueGradientKernel)      # blocks of d+1: src/gradient.jl:400-474
         self.inner = Gramian(g.k, x, y)
         n, m = self.inner.shape
-        d = self.inner.x.shape[1]
-        self.d = d
-        self.block_size = d + 1 if self.value else d
+        self.d = self.inner.x.shape[1]
+        self.block_size = self._block_size(self.d)
         self.shape = (n * self.block_size, m * self.block_size)
         self.dtype, self.device = self.inner.dtype, self.inner.device
 
     def issymmetric(self):
         return self.inner.issymmetric()
+
+    def _block_size(self, d):
+        return d + 1 if self.value else d
 
     def _lower(self):
         return K.require_device_spec(self.g.k)   # GenericInput gradient kernels have no device path
@@ -792,44 +779,22 @@ class BlockGramian(LazyOperator):
         return sub[ri][..., rj]
 
     def mul_(self, y, a, alpha=1.0, beta=0.0):
+        """Matrix right-hand sides (block solvers; src/gramian.jl:241-257 takes vectors of matrices) go down in ONE library call: the
+        library shares the pair evaluations between two columns at a time where its kernel holds two accumulators."""
         spec = self._lower()
-        a = _vec_arg(a, self.shape[1], self.dtype, self.device, "a")
-        if y.shape[0] != self.shape[0] or y.dtype != self.dtype or y.dim() != a.dim() or (a.dim() == 2 and y.shape[1] != a.shape[1]):
-            raise _ffi.DimensionMismatch(_ffi.EINVAL, f"DimensionMismatch: y has shape {tuple(y.shape)}")
-        # matrix right-hand sides (block solvers; src/gramian.jl:241-257 takes vectors of matrices): ONE library call, the columns
-        # as column-major storage (a torch matrix is row-major: its transpose's storage); the library shares the pair evaluations
-        # between two columns at a time where its kernel holds two accumulators
-        nrhs = 1 if a.dim() == 1 else a.shape[1]
-        if a.dim() == 1:
-            a_c = a.contiguous()
-            y_c = y if y.is_contiguous() else y.contiguous()
-        else:
-            a_c = a.t().contiguous()
-            y_c = y.t().contiguous() if beta != 0.0 else torch.empty((nrhs, self.shape[0]), dtype=self.dtype, device=self.device)
+        a = _rhs(self, y, a)
         ctx = self.inner._px.ctx.bind_stream()
-        fn = self._entry()
-        _ffi.check(fn(ctx, _ffi.kref(spec), self.inner._px.handle, self.inner._py.handle, _ffi._P(a_c.data_ptr()), self.shape[1],
-                      _ffi._P(y_c.data_ptr()), self.shape[0], nrhs, float(alpha), float(beta), _ffi.DEVICE))
-        if a.dim() == 2:
-            y.copy_(y_c.t())
-        elif y_c is not y:
-            y.copy_(y_c)
-        return y
+        return _staged(y, a, beta, lambda ap, lda, yp, ldy, nrhs: _ffi.check(self._entry()(
+            ctx, _ffi.kref(spec), self.inner._px.handle, self.inner._py.handle, _ffi._P(ap), lda, _ffi._P(yp), ldy, nrhs, float(alpha), float(beta),
+            _ffi.DEVICE)))
 
 
 class HessianGramian(BlockGramian):
     """Gramian of a HessianKernel: the lazy (n d²)×(m d²) BlockFactorization whose blocks are ∂⁴k / ∂x∂x∂y∂y (src/hessian.jl:33-41),
     applied in O(d²) per pair by covgram_hess_mvm.  Block vectors are point-major, entry i d² + a + b d."""
 
-    def __init__(self, g, x, y=None):
-        self.g = g
-        self.value = False
-        self.inner = Gramian(g.k, x, y)
-        n, m = self.inner.shape
-        self.d = d = self.inner.x.shape[1]
-        self.block_size = d * d
-        self.shape = (n * self.block_size, m * self.block_size)
-        self.dtype, self.device = self.inner.dtype, self.inner.device
+    def _block_size(self, d):
+        return d * d
 
     def _lower(self):
         return K.require_hessian_spec(self.g.k, self.d)
@@ -846,15 +811,8 @@ class ValueGradientHessianGramian(BlockGramian):
     [f, ∂f, vec ∂²f] (src/hessian.jl:301-325), applied in O(d²) per pair by covgram_valgradhess_mvm.  Block vectors are point-major:
     entry i(1+d+d²) the value, then the d gradient components, then Hessian component (a, b) at 1 + d + a + b d."""
 
-    def __init__(self, g, x, y=None):
-        self.g = g
-        self.value = False
-        self.inner = Gramian(g.k, x, y)
-        n, m = self.inner.shape
-        self.d = d = self.inner.x.shape[1]
-        self.block_size = 1 + d + d * d
-        self.shape = (n * self.block_size, m * self.block_size)
-        self.dtype, self.device = self.inner.dtype, self.inner.device
+    def _block_size(self, d):
+        return 1 + d + d * d
 
     def _lower(self):
         return K.require_vgh_spec(self.g.k, self.d)
@@ -866,7 +824,9 @@ class ValueGradientHessianGramian(BlockGramian):
         return _ffi.BLOCK_VALUE_GRADIENT_HESSIAN
 
 
-class _ToeplitzBase(LazyOperator):
+class _ToeplitzBase(_OwnsHandle, LazyOperator):
+    _destroy = "covgram_toeplitz_destroy"
+
     def __init__(self, vc: torch.Tensor, vr: Optional[torch.Tensor], circulant: bool):
         self.vc = vc.contiguous()
         self.vr = None if vr is None else vr.contiguous()
@@ -881,31 +841,13 @@ class _ToeplitzBase(LazyOperator):
                                                       _ffi._P(self.vr.data_ptr()) if self.vr is not None else None, n, m,
                                                       _dtype_code(self.dtype), _ffi.DEVICE, 1 if circulant else 0))
 
-    def __del__(self):
-        try:
-            if self.handle:
-                _ffi.lib().covgram_toeplitz_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
-
     def mul_(self, y, a, alpha=1.0, beta=0.0):
-        a = _vec_arg(a, self.shape[1], self.dtype, self.device, "a")
-        if a.dim() != 1:
-            for c in range(a.shape[1]):
-                yc = y[:, c].contiguous()
-                self.mul_(yc, a[:, c].contiguous(), alpha, beta)
-                y[:, c] = yc
-            return y
-        if y.shape[0] != self.shape[0] or y.dtype != self.dtype:
-            raise _ffi.DimensionMismatch(_ffi.EINVAL, f"DimensionMismatch: y has shape {tuple(y.shape)}")
-        a_c = a.contiguous()
-        y_c = y if y.is_contiguous() else y.contiguous()
+        a = _rhs(self, y, a)
+        if a.dim() != 1:                                       # covgram_toeplitz_mvm takes vectors
+            return _by_columns(self, y, a, alpha, beta)
         self._ctx.bind_stream()
-        _ffi.check(_ffi.lib().covgram_toeplitz_mvm(self.handle, _ffi._P(a_c.data_ptr()), _ffi._P(y_c.data_ptr()), float(alpha), float(beta), _ffi.DEVICE))
-        if y_c is not y:
-            y.copy_(y_c)
-        return y
+        return _staged(y, a, beta, lambda ap, lda, yp, ldy, nrhs: _ffi.check(_ffi.lib().covgram_toeplitz_mvm(
+            self.handle, _ffi._P(ap), _ffi._P(yp), float(alpha), float(beta), _ffi.DEVICE)))
 
     def to_dense(self):
         n, m = self.shape
@@ -944,10 +886,12 @@ class Circulant(_ToeplitzBase):
         return Circulant(torch.roll(self.vc.flip(0), 1))        # C[i, j] = vc[(i - j) mod n]: the transpose's first column is vc[-i mod n]
 
 
-class SparseGramian(LazyOperator):
+class SparseGramian(_OwnsHandle, LazyOperator):
     """sparse(G, δ) (src/sparse.jl:5-22): the entries of gramian(k, x, y) within the kernel's decay radius, as a CSR matrix that lives
     on the device (covgram_sparse_create); `mul!` is the library's CSR product (covgram_sparse_mvm).  The handle owns its arrays and
     keeps no reference to the Gramian's points."""
+
+    _destroy = "covgram_sparse_destroy"
 
     def __init__(self, G: "Gramian", delta: float = 1e-6):
         self.delta = float(delta)
@@ -960,14 +904,6 @@ class SparseGramian(LazyOperator):
         _ffi.check(_ffi.lib().covgram_sparse_info(self.handle, C.byref(n), C.byref(m), C.byref(nnz), C.byref(dt), C.byref(r)))
         self.nnz, self.radius = int(nnz.value), float(r.value)
 
-    def __del__(self):
-        try:
-            if self.handle:
-                _ffi.lib().covgram_sparse_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
-
     def csr(self):
         """(rowptr, colind, vals): int64 n + 1, int32 nnz (0-based, ascending within a row), nnz scalars — copies, as device tensors."""
         rowptr = torch.empty(self.shape[0] + 1, dtype=torch.int64, device=self.device)
@@ -979,31 +915,10 @@ class SparseGramian(LazyOperator):
         return rowptr, colind, vals
 
     def mul_(self, y, a, alpha=1.0, beta=0.0):
-        n, m = self.shape
-        a = _vec_arg(a, m, self.dtype, self.device, "a")
-        if y.shape[0] != n or y.dtype != self.dtype or tuple(y.shape[1:]) != tuple(a.shape[1:]):
-            raise _ffi.DimensionMismatch(_ffi.EINVAL, f"DimensionMismatch: y has shape {tuple(y.shape)}, expected ({n}, ...) of {self.dtype}")
+        a = _rhs(self, y, a)
         self._ctx.bind_stream()
-        lib = _ffi.lib()
-        if a.dim() == 1:
-            a_c = a.contiguous()
-            y_c = y if y.is_contiguous() else y.contiguous()
-            _ffi.check(lib.covgram_sparse_mvm(self.handle, _ffi._P(a_c.data_ptr()), max(m, 1), _ffi._P(y_c.data_ptr()), max(n, 1), 1,
-                                              float(alpha), float(beta), _ffi.DEVICE))
-            if y_c is not y:
-                y.copy_(y_c)
-            return y
-        p = a.shape[1]
-        if p == 0:                                             # no columns: nothing to do (the ABI requires nrhs >= 1)
-            return y
-        a_cm = a.t().contiguous()                              # (p, m) row-major == m×p column-major
-        direct = y.t().is_contiguous()
-        y_cm = y.t() if direct else y.t().contiguous()
-        _ffi.check(lib.covgram_sparse_mvm(self.handle, _ffi._P(a_cm.data_ptr()), max(m, 1), _ffi._P(y_cm.data_ptr()), max(n, 1), p,
-                                          float(alpha), float(beta), _ffi.DEVICE))
-        if not direct:
-            y.copy_(y_cm.t())
-        return y
+        return _staged(y, a, beta, lambda ap, lda, yp, ldy, nrhs: _ffi.check(_ffi.lib().covgram_sparse_mvm(
+            self.handle, _ffi._P(ap), lda, _ffi._P(yp), ldy, nrhs, float(alpha), float(beta), _ffi.DEVICE)))
 
     def to_dense(self):
         n, m = self.shape
@@ -1072,7 +987,7 @@ def require_barneshut_spec(k, d: Optional[int] = None, theta: float = BARNES_HUT
     return spec
 
 
-class BarnesHutFactorization(LazyOperator):
+class BarnesHutFactorization(_OwnsHandle, LazyOperator):
     """BarnesHutFactorization(k, x, y = x, D = nothing; θ = 1/4, leafsize = 16) (src/barneshut.jl:8-39): a ball tree over y, built once on
     the device (covgram_bh_create), and the tree-based approximate product F w + D w (covgram_bh_mvm).  `BarnesHutFactorization(G)` takes
     k, x, y from a Gramian.  D is None, a number, or n values (n == m).
@@ -1088,6 +1003,8 @@ class BarnesHutFactorization(LazyOperator):
         variant a Krylov solver wants.  The operator is not exactly symmetric either way (targets and sources are treated differently).
     taylor_ / taylor / taylor_moments are available whatever `product` is.  `solve.cg(F, b)` and `solve.minres(F, b)` run on mul_;
     `F.solve(b)` is the reference's `\\` (minres!, src/barneshut.jl:64-72).  The expansion stops at first order, like the reference's."""
+
+    _destroy = "covgram_bh_destroy"
 
     def __init__(self, k, x=None, y=None, D=None, theta: float = BARNES_HUT_THETA, leafsize: int = BARNES_HUT_LEAFSIZE,
                  product: str = "split", use_com: bool = True):
@@ -1127,14 +1044,6 @@ class BarnesHutFactorization(LazyOperator):
         _ffi.check(_ffi.lib().covgram_bh_info(self.handle, None, None, None, None, C.byref(nn), None, None))
         self.nnodes = int(nn.value)
 
-    def __del__(self):
-        try:
-            if self.handle:
-                _ffi.lib().covgram_bh_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
-
     def __getitem__(self, ij):
         return self._G[ij]                                     # src/barneshut.jl:42: F[i, j] = k(x[i], y[j])
 
@@ -1173,33 +1082,23 @@ class BarnesHutFactorization(LazyOperator):
                                                         _ffi._P(cen.data_ptr()), _ffi._P(m1.data_ptr()), _ffi.DEVICE))
         return sums, cen, m1
 
-    def _mvm(self, taylor, y, a, alpha, beta, theta, flag):
-        n, m = self.shape
-        a = _vec_arg(a, m, self.dtype, self.device, "a")
-        if y.shape[0] != n or y.dtype != self.dtype or tuple(y.shape[1:]) != tuple(a.shape[1:]):
-            raise _ffi.DimensionMismatch(_ffi.EINVAL, f"DimensionMismatch: y has shape {tuple(y.shape)}, expected ({n}, ...) of {self.dtype}")
+    def _mvm(self, y, a, alpha, beta, taylor, theta, flag):
+        a = _rhs(self, y, a)
         if theta is not None and not float(theta) >= 0:
             raise _ffi.DimensionMismatch(_ffi.EINVAL, f"BarnesHutFactorization: theta = {theta} is negative (0 = the exact product)")
-        if a.dim() == 2:
-            return _by_columns(self, y, a, alpha, beta, method="_mvm_column", taylor=taylor, theta=theta, flag=flag)
-        a_c = a.contiguous()
-        y_c = y if y.is_contiguous() else y.contiguous()
+        if a.dim() == 2:                                       # covgram_bh_mvm / covgram_bh_taylor_mvm take vectors
+            return _by_columns(self, y, a, alpha, beta, method="_mvm", taylor=taylor, theta=theta, flag=flag)
         self._ctx.bind_stream()
         dptr, dlen = (None, 0) if self.D is None else (_ffi._P(self.D.data_ptr()), self.D.shape[0])
         fn = _ffi.lib().covgram_bh_taylor_mvm if taylor else _ffi.lib().covgram_bh_mvm
-        _ffi.check(fn(self.handle, _ffi._P(a_c.data_ptr()), _ffi._P(y_c.data_ptr()), float(alpha), float(beta),
-                      -1.0 if theta is None else float(theta), 1 if flag else 0, dptr, dlen, _ffi.DEVICE))
-        if y_c is not y:
-            y.copy_(y_c)
-        return y
-
-    def _mvm_column(self, y, a, alpha, beta, taylor, theta, flag):
-        return self._mvm(taylor, y, a, alpha, beta, theta, flag)
+        return _staged(y, a, beta, lambda ap, lda, yp, ldy, nrhs: _ffi.check(fn(
+            self.handle, _ffi._P(ap), _ffi._P(yp), float(alpha), float(beta), -1.0 if theta is None else float(theta), 1 if flag else 0, dptr, dlen,
+            _ffi.DEVICE)))
 
     def taylor_(self, y, w, alpha=1.0, beta=0.0, theta: Optional[float] = None, use_com: bool = True):
         """b ← α (T w) + β b + α D w with T the first-order Taylor product taylor!(b, F, w, α, β, θ; use_com) (src/taylor.jl:7-57).
         theta=None: the handle's θ; θ = 0 is the exact product.  A matrix right-hand side goes column by column."""
-        return self._mvm(True, y, w, alpha, beta, theta, use_com)
+        return self._mvm(y, w, alpha, beta, True, theta, use_com)
 
     def taylor(self, w, **kw):
         """T w + D w as a new tensor (kw: theta, use_com)."""
@@ -1216,8 +1115,8 @@ class BarnesHutFactorization(LazyOperator):
         """b ← α (F w) + β b + α D w.  theta=None: the handle's θ; θ = 0 is the exact product.  split=False: the single pass of
         barneshut!(…; split = false).  With product="taylor" this is taylor_ with the constructor's use_com, and `split` is not consulted."""
         if self.product == "taylor":
-            return self._mvm(True, y, a, alpha, beta, theta, self.use_com)
-        return self._mvm(False, y, a, alpha, beta, theta, split)
+            return self._mvm(y, a, alpha, beta, True, theta, self.use_com)
+        return self._mvm(y, a, alpha, beta, False, theta, split)
 
     def to_dense(self):
         """The matrix the factorization approximates, Matrix(G) + D."""
@@ -1252,30 +1151,16 @@ class KroneckerProduct(LazyOperator):
         return self._dense
 
     def mul_(self, y, a, alpha=1.0, beta=0.0):
-        a = _vec_arg(a, self.shape[1], self.dtype, self.device, "a")
-        if y.shape[0] != self.shape[0] or y.dtype != self.dtype or y.dim() != a.dim() or (a.dim() == 2 and y.shape[1] != a.shape[1]):
-            raise _ffi.DimensionMismatch(_ffi.EINVAL, f"DimensionMismatch: y has shape {tuple(y.shape)}")
+        a = _rhs(self, y, a)
         fs = self._dense_factors()
         q = len(fs)
         ptrs = (_ffi._P * q)(*[_ffi._P(f.data_ptr()) for f in fs])
         rows = (C.c_int64 * q)(*[f.shape[1] for f in fs])
         cols = (C.c_int64 * q)(*[f.shape[0] for f in fs])
         lds = (C.c_int64 * q)(*[f.shape[1] for f in fs])
-        # right-hand sides: column-major n x p (a torch matrix is row-major: its transpose's storage)
-        nrhs = 1 if a.dim() == 1 else a.shape[1]
-        a_c = a.contiguous() if a.dim() == 1 else a.t().contiguous()
-        if a.dim() == 1:
-            y_c = y if y.is_contiguous() else y.contiguous()
-        else:
-            y_c = y.t().contiguous() if beta != 0.0 else torch.empty((nrhs, self.shape[0]), dtype=self.dtype, device=self.device)
         ctx = get_ctx(self.device).bind_stream()
-        _ffi.check(_ffi.lib().covgram_kron_mvm(ctx, ptrs, rows, cols, lds, q, _dtype_code(self.dtype), _ffi._P(a_c.data_ptr()), self.shape[1],
-                                               _ffi._P(y_c.data_ptr()), self.shape[0], nrhs, float(alpha), float(beta), _ffi.DEVICE))
-        if a.dim() == 2:
-            y.copy_(y_c.t())
-        elif y_c is not y:
-            y.copy_(y_c)
-        return y
+        return _staged(y, a, beta, lambda ap, lda, yp, ldy, nrhs: _ffi.check(_ffi.lib().covgram_kron_mvm(
+            ctx, ptrs, rows, cols, lds, q, _dtype_code(self.dtype), _ffi._P(ap), lda, _ffi._P(yp), ldy, nrhs, float(alpha), float(beta), _ffi.DEVICE)))
 
     def to_dense(self):
         out = None
@@ -1329,28 +1214,14 @@ class LazyMatrixProduct(LazyOperator):
         self._Vcm = self._Ucm if V is U else V.t().contiguous()
 
     def mul_(self, y, a, alpha=1.0, beta=0.0):
-        a = _vec_arg(a, self.shape[1], self.dtype, self.device, "a")
+        """A matrix right-hand side goes down in ONE call: from 8 columns on both products run on the matrix cores (csrc/lowrank.hip)."""
+        a = _rhs(self, y, a)
         n, m = self.shape
         r = self.U.shape[1]
-        nrhs = 1 if a.dim() == 1 else a.shape[1]
-        if y.shape[0] != n or y.dtype != self.dtype or (a.dim() == 2 and tuple(y.shape) != (n, nrhs)):
-            raise _ffi.DimensionMismatch(_ffi.EINVAL, f"DimensionMismatch: y has shape {tuple(y.shape)}")
-        # matrix right-hand sides go down in ONE call (column-major m x p / n x p): from 8 columns on both products run on the
-        # matrix cores (csrc/lowrank.hip)
-        a_c = a.contiguous() if a.dim() == 1 else a.t().contiguous()
-        if a.dim() == 1:
-            y_c = y if y.is_contiguous() else y.contiguous()
-        else:
-            y_c = y.t().contiguous() if beta != 0 else torch.empty((nrhs, n), dtype=self.dtype, device=self.device)
         ctx = get_ctx(self.device).bind_stream()
-        _ffi.check(_ffi.lib().covgram_lowrank_mvm(ctx, _ffi._P(self._Ucm.data_ptr()), n, _ffi._P(self._Vcm.data_ptr()), m, n, m, r,
-                                                  _dtype_code(self.dtype), _ffi._P(a_c.data_ptr()), m, _ffi._P(y_c.data_ptr()), n, nrhs,
-                                                  float(alpha), float(beta), _ffi.DEVICE))
-        if a.dim() == 2:
-            y.copy_(y_c.t())
-        elif y_c is not y:
-            y.copy_(y_c)
-        return y
+        return _staged(y, a, beta, lambda ap, lda, yp, ldy, nrhs: _ffi.check(_ffi.lib().covgram_lowrank_mvm(
+            ctx, _ffi._P(self._Ucm.data_ptr()), n, _ffi._P(self._Vcm.data_ptr()), m, n, m, r, _dtype_code(self.dtype), _ffi._P(ap), lda, _ffi._P(yp), ldy,
+            nrhs, float(alpha), float(beta), _ffi.DEVICE)))
 
     def to_dense(self):
         return self.U @ self.V.t()
@@ -1361,9 +1232,7 @@ def _by_columns(op, y, a, alpha, beta, method="mul_", **kw):
     method: another product of op with mul_'s leading arguments)."""
     product = getattr(op, method)
     for c in range(a.shape[1]):
-        yc = y[:, c].contiguous()
-        product(yc, a[:, c].contiguous(), alpha, beta, **kw)
-        y[:, c] = yc
+        product(y[:, c], a[:, c], alpha, beta, **kw)           # views: the product stages what is not contiguous
     return y
 
 
@@ -1380,7 +1249,7 @@ class ScaledOperator(LazyOperator):
         sa = self.dy * a if a.dim() == 1 else self.dy[:, None] * a
         t = self.K @ sa
         t = self.dx * t if t.dim() == 1 else self.dx[:, None] * t
-        return y.copy_(alpha * t) if beta == 0 else y.mul_(beta).add_(t, alpha=alpha)
+        return _axpby_(y, t, alpha, beta)
 
     def to_dense(self):
         return self.dx[:, None] * self.K.to_dense() * self.dy[None, :]
@@ -1404,7 +1273,7 @@ class LinearMapBlockGramian(LazyOperator):
         UA = (A * self.U if self.U.dim() == 1 else A @ self.U.t()).contiguous()
         t = (self.inner @ UA.reshape(-1)).reshape(n, -1)
         b = (t * self.U if self.U.dim() == 1 else t @ self.U).reshape(-1)
-        return y.copy_(alpha * b) if beta == 0 else y.mul_(beta).add_(b, alpha=alpha)
+        return _axpby_(y, b, alpha, beta)
 
 
 class CosineBlockGramian(LazyOperator):
@@ -1425,7 +1294,7 @@ class CosineBlockGramian(LazyOperator):
         A = _vec_arg(a, self.shape[1], self.dtype, self.device, "a").reshape(m, self.d)
         t = self.scalar @ (A @ self.c).contiguous()
         b = ((4 * math.pi ** 2) * t[:, None] * self.c[None, :]).reshape(-1)
-        return y.copy_(alpha * b) if beta == 0 else y.mul_(beta).add_(b, alpha=alpha)
+        return _axpby_(y, b, alpha, beta)
 
 
 class PointJacobianBlockGramian(LazyOperator):
@@ -1451,7 +1320,7 @@ class PointJacobianBlockGramian(LazyOperator):
         V = (self.inner @ JA.reshape(-1).contiguous()).reshape(n, d + 1)
         xv = (self.xh * V).sum(dim=1)
         b = (V[:, :d] / self.rx[:, None] - self.x * (xv / self.rx ** 2)[:, None]).reshape(-1)
-        return yv.copy_(alpha * b) if beta == 0 else yv.mul_(beta).add_(b, alpha=alpha)
+        return _axpby_(yv, b, alpha, beta)
 
 
 class LazyMatrixSum(LazyOperator):
@@ -1483,10 +1352,7 @@ class LazyMatrixSum(LazyOperator):
                     first = False
                     continue
                 t = (A * a if a.dim() == 1 else A[:, None] * a) if A.dim() == 1 else A @ a
-                if b == 0:
-                    y.copy_(alpha * t)
-                else:
-                    y.mul_(b).add_(t, alpha=alpha)
+                _axpby_(y, t, alpha, b)
             first = False
         return y
 
@@ -1560,6 +1426,12 @@ def _cosine_lowrank(k, px: torch.Tensor, py: torch.Tensor, same: bool):
     return LazyMatrixProduct(U, torch.stack([torch.cos(v), torch.sin(v)], dim=1))
 
 
+def _point_pair(x, y, same: bool):
+    """(px, py): the two point sets as device tensors, py on px's device in px's dtype — and px itself when `same`."""
+    px = _as_points(x)
+    return px, (px if same else _as_points(y, device=px.device, dtype=px.dtype))
+
+
 def gramian(k, x=None, y=None, trait: Optional[K.InputTrait] = None):
     """gramian(k, x[, y][, trait]) — picks the representation exactly as the reference does."""
     if x is None:
@@ -1572,13 +1444,11 @@ def gramian(k, x=None, y=None, trait: Optional[K.InputTrait] = None):
     same = y is None or y is x
 
     if isinstance(k, K.Constant):                               # src/stationary.jl:34
-        px = _as_points(x)
-        py = px if same else _as_points(y, device=px.device, dtype=px.dtype)
+        px, py = _point_pair(x, y, same)
         return Fill(k.c, px.shape[0], py.shape[0], px.dtype, px.device)
 
     if isinstance(k, K.FiniteBasis):                            # src/mercer.jl:61-70
-        px = _as_points(x)
-        py = px if same else _as_points(y, device=px.device, dtype=px.dtype)
+        px, py = _point_pair(x, y, same)
         r = len(k.basis)
         if px.shape[0] > r and py.shape[0] > r:
             def basis(p):
@@ -1591,14 +1461,12 @@ def gramian(k, x=None, y=None, trait: Optional[K.InputTrait] = None):
 
     # ---- input / output transformations: the points are transformed ONCE, the hot path runs on the result -------------------
     if isinstance(k, K.VerticalRescaling):                     # src/transformation.jl:165-171
-        px = _as_points(x)
-        py = px if same else _as_points(y, device=px.device, dtype=px.dtype)
+        px, py = _point_pair(x, y, same)
         fx = torch.as_tensor(k.f(px), dtype=px.dtype, device=px.device).reshape(-1)
         fy = fx if same else torch.as_tensor(k.f(py), dtype=px.dtype, device=px.device).reshape(-1)
         return ScaledOperator(fx, gramian(k.k, px, None if same else py), fy)
     if isinstance(k, (K.ScaledInputKernel, K.Warped, K.Periodic)):   # src/transformation.jl:82-90, 114-118, 54-65
-        px = _as_points(x)
-        py = px if same else _as_points(y, device=px.device, dtype=px.dtype)
+        px, py = _point_pair(x, y, same)
         tx = _transform_points(k, px)
         g = gramian(k.k, tx, None if same else _transform_points(k, py))
         if isinstance(k, K.ScaledInputKernel) and type(g) is Gramian:
@@ -1606,8 +1474,7 @@ def gramian(k, x=None, y=None, trait: Optional[K.InputTrait] = None):
         return g
     if isinstance(k, K.NeuralNetwork) or (isinstance(k, K.GradientKernel) and isinstance(k.k, K.NeuralNetwork)):
         nn = k if isinstance(k, K.NeuralNetwork) else k.k          # src/mercer.jl:82-85 on normalised augmented inputs
-        px = _as_points(x)
-        py = px if same else _as_points(y, device=px.device, dtype=px.dtype)
+        px, py = _point_pair(x, y, same)
         def warp(p):
             rho = torch.sqrt(1 + (p * p).sum(dim=1) + nn.sigma)
             z = torch.cat([p, torch.full((p.shape[0], 1), math.sqrt(nn.sigma), dtype=p.dtype, device=p.device)], dim=1)
@@ -1618,19 +1485,16 @@ def gramian(k, x=None, y=None, trait: Optional[K.InputTrait] = None):
             return Gramian(K.AsinDot(), xh, None if same else yh)
         return PointJacobianBlockGramian(px, py, xh, yh, rx, ry, BlockGramian(K.GradientKernel(K.AsinDot()), xh, None if same else yh))
     if isinstance(k, K.CosineKernel):                           # rank 2: cos(u_i − v_j) = cos u_i cos v_j + sin u_i sin v_j
-        px = _as_points(x)
-        py = px if same else _as_points(y, device=px.device, dtype=px.dtype)
+        px, py = _point_pair(x, y, same)
         return _cosine_lowrank(k, px, py, same)
     if isinstance(k, K.GradientKernel) and isinstance(k.k, K.ScaledInputKernel):
-        px = _as_points(x)
-        py = px if same else _as_points(y, device=px.device, dtype=px.dtype)
+        px, py = _point_pair(x, y, same)
         U = torch.as_tensor(k.k.U, dtype=px.dtype, device=px.device)
         tx = _transform_points(k.k, px)
         inner = BlockGramian(K.GradientKernel(k.k.k), tx, None if same else _transform_points(k.k, py))
         return LinearMapBlockGramian(U, inner, px.shape[1])
     if isinstance(k, K.GradientKernel) and isinstance(k.k, K.CosineKernel):
-        px = _as_points(x)
-        py = px if same else _as_points(y, device=px.device, dtype=px.dtype)
+        px, py = _point_pair(x, y, same)
         return CosineBlockGramian(torch.as_tensor(k.k.c, dtype=px.dtype, device=px.device), _cosine_lowrank(k.k, px, py, same))
 
     if isinstance(k, (K.GradientKernel, K.ValueGradientKernel)):   # src/gramian.jl:120-123
