@@ -130,8 +130,10 @@ template <int FAM, typename T> struct ParamsOf { using type = KParams<T>; };
 template <typename T> struct ParamsOf<FAM_EXPR_ISO, T> { using type = ExprParams<T>; };
 template <typename T> struct ParamsOf<FAM_EXPR_DOT, T> { using type = ExprParams<T>; };
 template <typename T> struct ParamsOf<FAM_SUM_ISO, T> { using type = SumParams<T>; };
-template <int FAM> constexpr bool fam_is_expr = (FAM == FAM_EXPR_ISO || FAM == FAM_EXPR_DOT);
-template <int FAM> constexpr bool fam_is_iso = (FAM != COVGRAM_DOT && FAM != COVGRAM_EXPDOT && FAM != COVGRAM_ASINDOT && FAM != FAM_EXPR_DOT);
+constexpr bool fam_expr(int fam) { return fam == FAM_EXPR_ISO || fam == FAM_EXPR_DOT; }
+constexpr bool fam_iso(int fam) { return fam != COVGRAM_DOT && fam != COVGRAM_EXPDOT && fam != COVGRAM_ASINDOT && fam != FAM_EXPR_DOT; }
+template <int FAM> constexpr bool fam_is_expr = fam_expr(FAM);
+template <int FAM> constexpr bool fam_is_iso = fam_iso(FAM);
 
 struct HostKernel {
     covgram_kernel k;     // simple kernel, or the head of a composite

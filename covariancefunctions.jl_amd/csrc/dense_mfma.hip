@@ -41,408 +41,23 @@
 // and otherwise the exact direct-difference kernel runs.
 // Option "dense_variant": 0 = this rule, 1 = always direct differences, 2 = MFMA whenever the shape allows (tests).
 //
-// Kernels in this file and in dense_mfma.hpp (one path each, chosen on the host in covgram_mvm):
-//   dense_mfma_eq_kernel<K2, RT, WPB, LDS>   EQ, any X / Y.  LDS = 0: one wave per workgroup with its own fragment loads;
-//                                            LDS = 1 (d <= 8) / 2 (d > 8): four waves share the column tiles through LDS
-//                                            (global_load_lds DMA, double buffered) when the column chunks are long.
-//   dense_mfma_gen_kernel<FAM, ...>          RQ, Cauchy, IMQ, MaternP, Dot^p, ExponentialDot, EQ^p, several right-hand sides:
-//                                            the MFMA yields the profile argument s (dense_mfma.hpp).
-//   dense_mfma_sym_kernel / _sym_wide_kernel gramian(k, x), one point set: the upper triangle once, row AND column sums
-//                                            ("Symmetric Gramian" below); also rank r of P's share for the multi-GPU form.
+//
+// This file is the HOST side of the matrix-core paths; the kernels live in headers (one path each, chosen on the host in covgram_mvm):
+//   dense_mfma_eq.hpp  dense_mfma_eq_kernel<K2, RT, WPB, LDS>: EQ, any X / Y.  LDS = 0: one wave per workgroup with its own fragment loads; LDS = 1 (d <= 8) /
+//                      2 (d > 8): four waves share the column tiles through LDS (global_load_lds DMA, double buffered) when the column chunks are long; the pack kernels
+//   dense_mfma.hpp     dense_mfma_gen_kernel<FAM, ...>: RQ, Cauchy, IMQ, MaternP, Dot^p, ExponentialDot, EQ^p, several right-hand sides (the MFMA yields the profile
+//                      argument s); dense_mfma_sym_kernel / _sym_wide_kernel / _sym2_kernel (dense_mfma_sym2.hpp): gramian(k, x), the upper triangle once, row AND
+//                      column sums ("Symmetric Gramian" below), also rank r of P's share for the multi-GPU form; the launchers, one argument list per kernel family
+//   mfma_plan.hpp      the column split and the symmetric work list as plain arithmetic (no HIP; tests/mfma_plan_check.cpp)
+// Sections: the points handle's radii (device code: their reduction kernel) | the rules, each written once | shared steps | the three drivers.
 #include "driver.hpp"
-#include "dense_mfma.hpp"
-#include "dense_mfma_sym2.hpp"
+#include "mfma_plan.hpp"
+#include "dense_mfma_eq.hpp"
 
 namespace covgram {
 
-// B fragments of every column tile in MFMA lane order + the fraction factors of the column norms (both depend on the points
-// and g only: cached in the points handle).  Lane (r, h) of MFMA mm of tile T holds, for coordinate c = 2 mm + h of column
-// j = 32 T + r, the eight K-slots  [y1, y2, y1, y3, y2, y1, y3, y2]  (16 bytes) of y~_c, which meet the row side's
-// [x1, x1, x2, x1, x2, x3, x2, x3]; the integer part k_j of -|y~_j|^2/2 sits in the idle coordinate c = d as [1, k_j, 0, ...]
-// (d odd) or replaces the last two slots of coordinate 0, [.., 1, k_j] (d even) — dense_mfma.hpp: norm_split.
-//   PB[(T * K2 + mm) * 64 + l] = that fragment (zero outside the point set / dimension)
-//   EF[32 T + r]               = exp2(f_j) in (1/2, 1]                          (0 for padding columns)
-__global__ __launch_bounds__(256) void mfma_pack_kernel(const float* __restrict__ Y, int64_t m, int32_t d, uint4* __restrict__ PB,
-                                                        float* __restrict__ EF, int32_t K2, float g, const float* __restrict__ Cn, int32_t fmt) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;      // (tile, mm, lane)
-    const int64_t ntile = (m + 31) / 32;
-    if (e >= ntile * K2 * 64) return;
-    const int l = (int)(e & 63);
-    const int64_t q = e >> 6;
-    const int mm = (int)(q % K2);
-    const int64_t T = q / K2;
-    const int64_t j = 32 * T + (l & 31);
-    if (fmt == 1) {
-        // fp16 two-way split: lane (r, h) of MFMA mm holds coordinates c0 = 4 mm + 2 h and c0 + 1 of column j as
-        // [y1, y2, y1 | y1, y2, y1 | 1, k_j] — the last two slots in lane half 0 of MFMA 0 only (dense_mfma.hpp: eq_row_fragments_h)
-        const int c0 = 4 * mm + 2 * (l >> 5);
-        const bool nl = mm == 0 && (l >> 5) == 0;
-        uint4 frag = make_uint4(0, 0, 0, 0);
-        if (j < m) {
-            const float ya = c0 < d ? g * (Y[j * (int64_t)d + c0] - Cn[c0]) : 0.0f;
-            const float yb = c0 + 1 < d ? g * (Y[j * (int64_t)d + c0 + 1] - Cn[c0 + 1]) : 0.0f;
-            unsigned a1, a2, b1, b2;
-            split2h(ya, a1, a2);
-            split2h(yb, b1, b2);
-            frag = make_uint4(a1 | (a2 << 16), a1 | (b1 << 16), b2 | (b1 << 16), 0u);
-            if (nl) {
-                double ny = 0.0;
-                for (int cc = 0; cc < d; ++cc) { const double yc = (double)(g * (Y[j * (int64_t)d + cc] - Cn[cc])); ny = __builtin_fma(yc, yc, ny); }
-                const double hn = -0.5 * ny, k = __builtin_ceil(hn);
-                frag.w = F16_ONE | (f16_bits((float)k) << 16);
-                EF[j] = __builtin_amdgcn_exp2f((float)(hn - k));
-            }
-        } else if (nl) {
-            EF[j] = 0.0f;
-        }
-        PB[e] = frag;
-        return;
-    }
-    const int c = 2 * mm + (l >> 5);
-    uint4 frag = make_uint4(0, 0, 0, 0);
-    const bool norm_lane = (d & 1) ? (c == d) : (c == 0);          // the lane that carries k_j (one per column)
-    if (j < m) {
-        if (c < d) {
-            const float yt = g * (Y[j * (int64_t)d + c] - Cn[c]);
-            unsigned y1, y2, y3;
-            split3(yt, y1, y2, y3);
-            frag = make_uint4(y1 | (y2 << 16), y1 | (y3 << 16), y2 | (y1 << 16), y3 | (y2 << 16));
-        }
-        if (norm_lane) {
-            double ny = 0.0;
-            for (int cc = 0; cc < d; ++cc) { const double yc = (double)(g * (Y[j * (int64_t)d + cc] - Cn[cc])); ny = __builtin_fma(yc, yc, ny); }
-            const NormSplit sp = norm_split(ny);
-            if (d & 1) frag = make_uint4(BF16_ONE | (sp.kbits << 16), 0, 0, 0);
-            else frag.w = BF16_ONE | (sp.kbits << 16);
-            EF[j] = sp.ef;
-        }
-    } else if (norm_lane) {
-        EF[j] = 0.0f;
-    }
-    PB[e] = frag;
-}
-
-// the per-MVM part of the pack: W[j] = a_j * exp2(f_j) (the cached fraction factor, in (1/2, 1]), 0 for padding columns
-__global__ __launch_bounds__(256) void mfma_pack_w_kernel(const float* __restrict__ A, const float* __restrict__ EF, float* __restrict__ W,
-                                                          int64_t m, int64_t mpad) {
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < mpad) W[j] = j < m ? A[j] * EF[j] : 0.0f;
-}
-
-// LDS: 0 = every wave loads its own column tiles; 1 = stages of WPB tiles shared through LDS (K2 <= 4, RT = 2);
-//      2 = ONE tile per stage, its K2 fragment slices fetched by the WPB waves in turn (K2 > 4, RT = 1)
-// STAMP = 1: the diagnostic build of the SAME loop that reads the shader clock (s_memtime) and the constant 100 MHz counter
-// (s_memrealtime) around the column loop of every workgroup — clock = d(memtime) / d(memrealtime) x 100 MHz (MI355X_MICROARCH.md,
-// DVFS give-back item 6).  The stamps go to a buffer of their own; no product launch ever runs this instantiation.
-template <int K2, int RT, int WPB = 1, int LDS = 0, int STAMP = 0, int FMT = 0>
-__global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(LDS == 1 ? (RT == 4 ? 2 : K2 <= 2 ? 4 : 3) : 1, LDS == 1 ? (RT == 4 ? 2 : K2 <= 2 ? 4 : 3) : 8))) void dense_mfma_eq_kernel(const float* __restrict__ X, int64_t n, int32_t d,
-                                                           const uint4* __restrict__ PB, const float* __restrict__ W, int64_t ntile,
-                                                           float* __restrict__ out, int64_t npad, int64_t tchunk, float g,
-                                                           float alpha, float beta, int32_t final_store, const float* __restrict__ Cn,
-                                                           unsigned long long* __restrict__ stamps, unsigned* __restrict__ tickets,
-                                                           float* __restrict__ yfinal, const float* __restrict__ EF, int64_t mcols) {
-    // WPB waves per workgroup take consecutive row tiles and walk the SAME column tiles at the same pace (no barrier,
-    // nothing shared explicitly): their fragment loads coalesce in the CU's vector L1 instead of each going to L2
-    const int l = threadIdx.x & 63, t = l & 31, h = l >> 5;
-    const int64_t i0 = ((int64_t)blockIdx.x * WPB + (threadIdx.x >> 6)) * (32 * RT);
-    // A fragments: lane (t, h) holds the split of x~[row][c = 2 mm + h] (+ the integer part of the row's half-norm)
-    Frag a[RT][K2];
-    float er[RT];                                                // exp2 of the fraction of the row's half-norm, in (1/2, 1]
-#pragma unroll
-    for (int r = 0; r < RT; ++r) {
-        int64_t row = i0 + 32 * r + t;
-        if (row >= n) row = n - 1;                               // clamp: computed, never stored
-        er[r] = eq_row_fragments_fmt<K2, FMT>(X + row * (int64_t)d, Cn, d, g, h, a[r]);
-    }
-
-    unsigned long long st_c0 = 0, st_r0 = 0;
-    if constexpr (STAMP) { st_c0 = __builtin_amdgcn_s_memtime(); st_r0 = __builtin_amdgcn_s_memrealtime(); }
-    const int64_t T0 = (int64_t)blockIdx.y * tchunk;
-    const int64_t T1 = (T0 + tchunk < ntile) ? (T0 + tchunk) : ntile;
-    // the accumulators live as register PAIRS: with one or two MFMAs per tile the weighted sums are v_pk_fma_f32 (two fmas per instruction — nearly twice
-    // the rate while no MFMA executes, slower than two v_fma_f32 beside one: tools/pkfma_probe.hip; C2-shaped 1.44 -> 1.33 ms, four MFMAs per tile +2-3 %)
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    f32x2 acc2[RT][8];
-#pragma unroll
-    for (int r = 0; r < RT; ++r)
-#pragma unroll
-        for (int v = 0; v < 8; ++v) acc2[r][v] = (f32x2){0.0f, 0.0f};
-
-    // Column tiles in pairs with two operand buffers (no register copies); the prefetch of a tile past the chunk is clamped
-    // to the last tile (a harmless re-read) instead of branching.  Uniform base + 32-bit lane offset -> saddr loads.
-    const uint4* __restrict__ pbase = PB + (T0 * K2) * 64;
-    // column weights w_j = a_j exp2(f_j) (0 for padding columns).  EF != nullptr (round 4): W is the caller's a itself and the product with the cached
-    // fraction factors is formed here, where a tile's weights are fetched: no weight-pack launch in front of the MVM (mvm_eq_mfma)
-    const float* __restrict__ wbase = W + T0 * 32;
-    const int nt = (int)(T1 - T0);
-    auto weight = [&](int tc) {
-        if (EF == nullptr) return wbase[tc * 32 + t];
-        const int64_t j = (T0 + tc) * 32 + t;
-        return j < mcols ? W[j] * EF[j] : 0.0f;
-    };
-    auto load_tile = [&](int ti, Frag (&f)[K2], float& w) {
-        const int tc = ti < nt ? ti : nt - 1;
-#pragma unroll
-        for (int mm = 0; mm < K2; ++mm) f[mm].u = pbase[(tc * K2 + mm) * 64 + l];
-        w = weight(tc);
-    };
-    auto process = [&](const Frag (&f)[K2], float w) {
-        f32x16 D[RT];
-#pragma unroll
-        for (int r = 0; r < RT; ++r) {
-            D[r] = (f32x16){0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-            for (int mm = 0; mm < K2; ++mm) D[r] = eq_mma<FMT>(a[r][mm], f[mm], D[r]);
-        }
-        // all exponentials of the tile first, then the weighted accumulation: no exp -> fma wait states in between
-#pragma unroll
-        for (int r = 0; r < RT; ++r)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) D[r][v] = __builtin_amdgcn_exp2f(D[r][v]);
-#pragma unroll
-        for (int r = 0; r < RT; ++r)
-#pragma unroll
-            for (int v = 0; v < 8; ++v) {
-                if constexpr (K2 <= 2) acc2[r][v] = __builtin_elementwise_fma((f32x2){w, w}, (f32x2){D[r][2 * v], D[r][2 * v + 1]}, acc2[r][v]);
-                else { acc2[r][v][0] = __builtin_fmaf(w, D[r][2 * v], acc2[r][v][0]); acc2[r][v][1] = __builtin_fmaf(w, D[r][2 * v + 1], acc2[r][v][1]); }
-            }
-    };
-    if constexpr (LDS == 2) {
-        // Long fragments (K2 KB per tile): the workgroup stages ONE tile at a time, wave w fetching the fragment slices
-        // mm = w, w + WPB, ... of the NEXT tile (global_load_lds_dwordx4) while all waves stream the CURRENT tile's slices
-        // from the other buffer into their MFMA chain; one barrier per tile (a tile is >= 32 K2 matrix-pipe cycles).
-        static_assert(RT == 1, "split-tile staging is built for one row tile per wave");
-        __shared__ uint4 tfA[K2][64], tfB[K2][64];
-        __shared__ float twA[32], twB[32];
-        typedef __attribute__((address_space(1))) const void* gptr_t;
-        typedef __attribute__((address_space(3))) void* lptr_t;
-        const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-        // (gw, ge): loaded with the tile's LDS-DMA, multiplied only where the weight is stored after the tile's arithmetic (as in the LDS == 1 form
-        // below; round 5: here the product sat right behind the loads — one exposed memory round trip per TILE for wave 0, and the barrier passes it on)
-        float gw = 0.0f, ge = 1.0f;
-#define CG_DMA2(tile, TF)                                                                       \
-        {                                                                                       \
-            const int ti_ = (tile);                                                             \
-            const int tc_ = ti_ < nt ? ti_ : nt - 1;                                            \
-            _Pragma("unroll") for (int q = 0; q < (K2 + WPB - 1) / WPB; ++q) {                  \
-                const int mm = wv + q * WPB;                                                    \
-                if (mm < K2) __builtin_amdgcn_global_load_lds((gptr_t)(pbase + (tc_ * K2 + mm) * 64 + l), (lptr_t)&TF[mm][0], 16, 0, 0); \
-            }                                                                                   \
-            if (wv == 0) {                                                                      \
-                if (EF == nullptr) gw = ti_ < nt ? wbase[tc_ * 32 + t] : 0.0f;                  \
-                else {                                                                          \
-                    const int64_t j_ = (T0 + tc_) * 32 + t;                                     \
-                    const bool in_ = ti_ < nt && j_ < mcols;                                    \
-                    gw = in_ ? W[j_] : 0.0f; ge = in_ ? EF[j_] : 0.0f;                          \
-                }                                                                               \
-            }                                                                                   \
-        }
-#define CG_TILE2(TF, TW)                                                                        \
-        {                                                                                       \
-            f32x16 D = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};                        \
-            Frag f_[K2];                                                                        \
-            _Pragma("unroll") for (int mm = 0; mm < K2; ++mm) f_[mm].u = TF[mm][l];             \
-            const float w = TW[t];                                                              \
-            _Pragma("unroll") for (int mm = 0; mm < K2; ++mm) D = eq_mma<FMT>(a[0][mm], f_[mm], D); \
-            _Pragma("unroll") for (int v = 0; v < 16; ++v) D[v] = __builtin_amdgcn_exp2f(D[v]); \
-            _Pragma("unroll") for (int v = 0; v < 8; ++v) { acc2[0][v][0] = __builtin_fmaf(w, D[2 * v], acc2[0][v][0]); acc2[0][v][1] = __builtin_fmaf(w, D[2 * v + 1], acc2[0][v][1]); } \
-        }
-        CG_DMA2(0, tfA)
-        if (wv == 0 && h == 0) twA[t] = gw * ge;
-        __syncthreads();
-        for (int ti = 0; ti < nt; ti += 2) {
-            CG_DMA2(ti + 1, tfB)                                    // past the chunk: a re-fetch nobody reads
-            CG_TILE2(tfA, twA)
-            if (wv == 0 && h == 0) twB[t] = gw * ge;
-            __syncthreads();
-            if (ti + 1 >= nt) break;
-            CG_DMA2(ti + 2, tfA)
-            CG_TILE2(tfB, twB)
-            if (wv == 0 && h == 0) twA[t] = gw * ge;
-            __syncthreads();
-        }
-#undef CG_DMA2
-#undef CG_TILE2
-    } else if constexpr (LDS == 1) {
-        // The WPB waves of the workgroup walk the same column tiles: each stage of WPB tiles is fetched ONCE — wave w moves
-        // tile w of the NEXT stage straight from global memory into LDS (global_load_lds_dwordx4: no staging registers; lane
-        // order in LDS = lane order of the packed fragments) while the current stage is read by all waves from the other
-        // buffer — which cuts the L2 -> L1 fragment traffic by WPB.  Two buffers as two distinct arrays (the compiler's
-        // LDS-DMA wait tracking tells them apart), the stage loop unrolled by two, one barrier per stage.
-        __shared__ uint4 sfA[WPB][K2][64], sfB[WPB][K2][64];
-        __shared__ float swA[WPB][32], swB[WPB][32];
-        typedef __attribute__((address_space(1))) const void* gptr_t;
-        typedef __attribute__((address_space(3))) void* lptr_t;
-        const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-        const int nstage = (nt + WPB - 1) / WPB;
-        // (gw, ge): the weight's two factors a_j and exp2(f_j) when the kernel forms the product itself (EF != nullptr) — loaded here, multiplied
-        // only where the weight goes to LDS at the end of the stage: a product right behind the loads would hold this wave until the LDS-DMA
-        // it has just issued lands (the same counter); ge = 1 when W holds packed weights
-        float gw, ge = 1.0f;
-#define CG_DMA(stage, SF)                                                                       \
-        {                                                                                       \
-            const int ti_ = (stage) * WPB + wv;                                                 \
-            const int tc_ = ti_ < nt ? ti_ : nt - 1;                                            \
-            _Pragma("unroll") for (int mm = 0; mm < K2; ++mm)                                   \
-                __builtin_amdgcn_global_load_lds((gptr_t)(pbase + (tc_ * K2 + mm) * 64 + l), (lptr_t)&SF[wv][mm][0], 16, 0, 0); \
-            if (EF == nullptr) gw = ti_ < nt ? wbase[tc_ * 32 + t] : 0.0f;   /* tiles past the chunk: weight 0 */ \
-            else {                                                                              \
-                const int64_t j_ = (T0 + tc_) * 32 + t;                                         \
-                const bool in_ = ti_ < nt && j_ < mcols;                                        \
-                gw = in_ ? W[j_] : 0.0f; ge = in_ ? EF[j_] : 0.0f;                              \
-            }                                                                                   \
-        }
-#define CG_STAGE(SF, SW)                                                                        \
-        _Pragma("unroll 1") for (int k = 0; k < WPB; k += 2) {                                  \
-            Frag f0[K2], f1[K2];                                                                \
-            _Pragma("unroll") for (int mm = 0; mm < K2; ++mm) f0[mm].u = SF[k][mm][l];          \
-            const float w0 = SW[k][t];                                                          \
-            _Pragma("unroll") for (int mm = 0; mm < K2; ++mm) f1[mm].u = SF[k + 1][mm][l];      \
-            const float w1 = SW[k + 1][t];                                                      \
-            process(f0, w0);                                                                    \
-            process(f1, w1);                                                                    \
-        }
-        CG_DMA(0, sfA)
-        if (h == 0) swA[wv][t] = gw * ge;
-        __syncthreads();
-        for (int st = 0; st < nstage; st += 2) {
-            CG_DMA(st + 1 < nstage ? st + 1 : st, sfB)              // past the last stage: a re-fetch nobody reads
-            CG_STAGE(sfA, swA)
-            if (h == 0) swB[wv][t] = gw * ge;
-            __syncthreads();
-            if (st + 1 >= nstage) break;
-            CG_DMA(st + 2 < nstage ? st + 2 : st + 1, sfA)
-            CG_STAGE(sfB, swB)
-            if (h == 0) swA[wv][t] = gw * ge;
-            __syncthreads();
-        }
-#undef CG_DMA
-#undef CG_STAGE
-    } else {
-    Frag f0[K2], f1[K2];
-    float w0, w1;
-    load_tile(0, f0, w0);
-    for (int ti = 0; ti < nt; ti += 2) {
-        load_tile(ti + 1, f1, w1);
-        process(f0, w0);
-        load_tile(ti + 2, f0, w0);
-        if (ti + 1 < nt) process(f1, w1);
-    }
-    }
-
-    if constexpr (STAMP) {
-        const unsigned long long c1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-        if (threadIdx.x == 0) {
-            unsigned long long* o = stamps + 4 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x);
-            o[0] = st_c0; o[1] = st_r0; o[2] = c1; o[3] = r1;
-        }
-    }
-    // lane (t, h) owns output row t of each row tile iff bit 2 of t equals h; its register is v = (t & 3) + 4 (t >> 3)
-    const int vsel = (t & 3) + 4 * (t >> 3);
-#pragma unroll
-    for (int r = 0; r < RT; ++r) {
-        // sum over the 32 column lanes of each half: afterwards every lane of half h holds the totals of rows i(v, h)
-        float tot = 0.0f;
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            float s = acc2[r][v >> 1][v & 1];
-            s += __shfl_xor(s, 1); s += __shfl_xor(s, 2); s += __shfl_xor(s, 4); s += __shfl_xor(s, 8); s += __shfl_xor(s, 16);
-            tot = (vsel == v) ? s : tot;
-        }
-        const int64_t i = i0 + 32 * r + t;
-        if (((t >> 2) & 1) != h || i >= n) continue;
-        const float res = er[r] * tot;
-        if (final_store) {
-            float v = alpha * res;
-            if (beta != 0.0f) v = __builtin_fmaf(beta, out[i], v);
-            out[i] = v;
-        } else {
-            slab_store(out + (int64_t)blockIdx.y * npad + i, res, tickets != nullptr);
-        }
-    }
-    // column split with tickets: the LAST workgroup of this row block to arrive adds the block's partials in dense_reduce_kernel's
-    // order and applies alpha / beta (pack.hpp: last_arrival) — no reduce launch, no dependent-launch gap behind the kernel
-    if (!final_store && tickets != nullptr) {
-        if (!last_arrival(tickets + blockIdx.x, gridDim.y)) return;
-        const int64_t r0 = (int64_t)blockIdx.x * (WPB * 32 * RT);
-        for (int idx = threadIdx.x; idx < WPB * 32 * RT; idx += 64 * WPB) {
-            const int64_t i = r0 + idx;
-            if (i >= n) continue;
-            float v = alpha * ordered_split_sum<float>(out + i, npad, (int)gridDim.y);
-            if (beta != 0.0f) v = __builtin_fmaf(beta, yfinal[i], v);
-            yfinal[i] = v;
-        }
-    }
-}
-
-// Column tiles for the generic kernel.  Lane (r, h) of MFMA mm of tile T holds coordinate c = 2 mm + h of column
-// j = 32 T + r:  c < d: the split of (iso ? -2 g y_c : g y_c) as [y1, y2, y1, y3, y2, y1, y3, y2];  c == d (iso): the norm
-// slots [1, 1, 1, n1, n2, n3, 0, 0] with n = |g y|^2;  beyond: zeros.   W[(T * NR + c) * 32 + r] = A[j + c lda].
-__global__ __launch_bounds__(256) void mfma_pack_gen_kernel(const float* __restrict__ Y, int64_t m, int32_t d, const float* __restrict__ A,
-                                                            int64_t lda, int32_t nrhs, int32_t c0, uint4* __restrict__ PB,
-                                                            float* __restrict__ W, int32_t K2, int32_t NR, float g, int32_t iso,
-                                                            const float* __restrict__ Cn, int32_t fmt) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;      // (tile, mm, lane)
-    const int64_t ntile = (m + 31) / 32;
-    if (e >= ntile * K2 * 64) return;
-    const int l = (int)(e & 63);
-    const int64_t q = e >> 6;
-    const int mm = (int)(q % K2);
-    const int64_t T = q / K2;
-    const int64_t j = 32 * T + (l & 31);
-    const int c = 2 * mm + (l >> 5);
-    uint4 frag = make_uint4(0, 0, 0, 0);
-    if (fmt == 1) {
-        // fp16 two-way split (dense_mfma.hpp: gen_row_fragments, GFMT = 1): positions q0 = 4 mm + 2 h and q0 + 1, three slots each — a coordinate
-        // [y1, y2, y1] of -2 g (y - c), the row norm's position d as [1, 1, 1], the column norm at d + 1 as [k, f1, f2]
-        if (j < m) {
-            float ny = 0.0f;
-            for (int cc = 0; cc < d; ++cc) { const float yc = g * (Y[j * (int64_t)d + cc] - Cn[cc]); ny = __builtin_fmaf(yc, yc, ny); }
-            unsigned sl[6] = {0, 0, 0, 0, 0, 0};
-            for (int w = 0; w < 2; ++w) {
-                const int qq = 4 * mm + 2 * (l >> 5) + w;
-                if (qq < d) { unsigned y1, y2; split2h(-2.0f * (g * (Y[j * (int64_t)d + qq] - Cn[qq])), y1, y2); sl[3 * w] = y1; sl[3 * w + 1] = y2; sl[3 * w + 2] = y1; }
-                else if (qq == d) { sl[3 * w] = sl[3 * w + 1] = sl[3 * w + 2] = F16_ONE; }
-                else if (qq == d + 1) { const Norm16 nn = norm16(ny); sl[3 * w] = nn.k; sl[3 * w + 1] = nn.f1; sl[3 * w + 2] = nn.f2; }
-            }
-            frag = make_uint4(sl[0] | (sl[1] << 16), sl[2] | (sl[3] << 16), sl[4] | (sl[5] << 16), 0u);
-        }
-    } else
-    if (j < m) {
-        if (c < d) {
-            const float yt = iso ? -2.0f * (g * (Y[j * (int64_t)d + c] - Cn[c])) : g * Y[j * (int64_t)d + c];
-            unsigned y1, y2, y3;
-            split3(yt, y1, y2, y3);
-            frag = make_uint4(y1 | (y2 << 16), y1 | (y3 << 16), y2 | (y1 << 16), y3 | (y2 << 16));
-        } else if (iso && c == d) {
-            float ny = 0.0f;
-            for (int cc = 0; cc < d; ++cc) { const float yc = g * (Y[j * (int64_t)d + cc] - Cn[cc]); ny = __builtin_fmaf(yc, yc, ny); }
-            unsigned n1, n2, n3;
-            split3(ny, n1, n2, n3);
-            frag = make_uint4(BF16_ONE | (BF16_ONE << 16), BF16_ONE | (n1 << 16), n2 | (n3 << 16), 0);
-        }
-    }
-    PB[e] = frag;
-    if (mm == 0 && l < 32)
-        for (int cr = 0; cr < NR; ++cr) W[(T * NR + cr) * 32 + l] = (j < m && c0 + cr < nrhs) ? A[j + (int64_t)(c0 + cr) * lda] : 0.0f;
-}
-
-// A operands of dense_mfma_mrhs_kernel: AP[((T * NB + b) * 64 + l) * 16 + v] = a[j][c0 + 32 b + (l & 31)] with
-// j = 32 T + 8 (v / 4) + 4 (l >> 5) + v % 4 (zero outside the matrix): lane l's sixteen values of one tile are contiguous
-__global__ __launch_bounds__(256) void mfma_pack_rhs_kernel(const float* __restrict__ A, int64_t lda, int32_t nrhs, int32_t c0, int64_t m,
-                                                            float* __restrict__ AP, int32_t NB) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;      // (tile, block, lane, v)
-    const int64_t ntile = (m + 31) / 32;
-    if (e >= ntile * NB * 64 * 16) return;
-    const int v = (int)(e & 15), l = (int)((e >> 4) & 63);
-    const int64_t q = e >> 10;
-    const int b = (int)(q % NB);
-    const int64_t T = q / NB;
-    const int64_t j = 32 * T + 8 * (v >> 2) + 4 * (l >> 5) + (v & 3);
-    const int c = c0 + 32 * b + (l & 31);
-    AP[e] = (j < m && c < nrhs) ? A[j + (int64_t)c * lda] : 0.0f;
-}
-
+// ---- The points handle's radii: max |x|^2 and max |x - c|^2 about a sampled centre, computed once at handle creation (covgram_points_create, --------------------
+// api.hip), and the gate quantity the rules below derive from them
 // max_i |x_i|^2 of a point set (fp32 or fp64 points), via atomicMax on the bit pattern of a non-negative float
 // DL > 1 (d == DL, a power of two 8 .. 64): DL lanes share a point, one coordinate each — consecutive lanes read consecutive memory (round 5: a thread per
 // point put every lane of a load on its own cache line once rows were long: 373 us for n = 2^20, d = 32 fp64 at handle creation)
@@ -560,9 +175,12 @@ double gate_radius2(const covgram_points* X, const covgram_points* Y) {
     return r * r;
 }
 
-static int eq_k2_for(int d) {   // MFMAs per tile of the EQ kernels (two coordinates each), from the compiled set
+// ---- Rules: which kernel serves a call.  Each is written once; covgram_mvm (api.hip) and the drivers below only ask. --------------------
+constexpr double LOG2E = 1.4426950408889634074;   // the pre-scaled coordinates: |x~|^2 = LOG2E |x|^2 / l^2
+
+static int mfma_k2_for(int dims) {   // MFMAs per tile for `dims` (pseudo-)coordinates (two each), from the compiled set (dense_mfma.hpp: mfma_for_k2)
     static const int ks[] = {1, 2, 3, 4, 6, 8, 12, 16};
-    const int need = (d + 1) / 2;
+    const int need = (dims + 1) / 2;
     for (int k : ks) if (k >= need) return k;
     return -1;
 }
@@ -572,10 +190,213 @@ bool mfma_eq_eligible(const covgram_ctx* ctx, const HostKernel& hk, const covgra
     if (hk.tu_family != COVGRAM_EQ || hk.k.power != 1 || X->dtype != COVGRAM_F32 || nrhs != 1) return false;
     if (X->d > 32 || Y->n == 0) return false;                   // beyond d = 32 the fragments leave one wave per SIMD
     if (ctx->dense_variant == 2) return true;
-    const double g2 = 1.4426950408889634074 / (hk.k.lengthscale * hk.k.lengthscale);   // |x~|^2 = g2 |x|^2
+    const double g2 = LOG2E / (hk.k.lengthscale * hk.k.lengthscale);   // |x~|^2 = g2 |x|^2
     return g2 * gate_radius2(X, Y) <= mfma_gate_of(ctx);                 // BOTH sides: a far X cluster must not ride on a compact Y
 }
 
+// Which split (round 4) of the EQ forms' coordinates, and with it the MFMAs per tile.  The bf16 three-way split is exact to 2^-24 |x~_c y~_c| per
+// coordinate and costs one MFMA per TWO coordinates.  The fp16 two-way split (x~ = h1 + h2, 11 + 11 bits; products h1 h1, h1 h2, h2 h1) drops terms
+// of ~2^-22 |x~_c y~_c| — the size of ONE fp32 rounding of the dot product itself, which the accumulator commits anyway — and covers FOUR coordinates
+// per MFMA: half the matrix-core work per pair.  The d = 5 ... 8 kernels are power-bound (2.0 GHz under C3's shard kernel,
+// profiles/r04_c3_power_bound.txt), so that is both fewer cycles and a higher clock.  Taken while BOTH clouds lie within g^2 R^2 <= MFMA_F16_GATE
+// (the added exponent error grows with the radius like the accumulator's own: common.hpp); beyond it, up to MFMA_GATE, the bf16 split serves as
+// before.  Option "mfma_f16": -1 / 1 = this rule, 0 = never, 2 = wherever the matrix-core gate admits the cloud (measurements: tools/f16_split_ab.py).
+// (gramian(k, x): every rank of a multi-GPU call sees the same cloud and lengthscale, hence the same split and the same panel size)
+struct EqSplit { int fmt, K2; };
+static EqSplit eq_split(const covgram_ctx* ctx, const HostKernel& hk, const covgram_points* X, const covgram_points* Y) {
+    const double g2r2 = LOG2E / (hk.k.lengthscale * hk.k.lengthscale) * gate_radius2(X, Y);
+    const int fmt = (ctx->mfma_f16 != 0 && g2r2 <= (ctx->mfma_f16 == 2 ? mfma_gate_of(ctx) : mfma_f16_gate_of(ctx))) ? 1 : 0;
+    return {fmt, fmt ? mfma_k2_for(2 * ((X->d + 3) / 4)) : mfma_k2_for(X->d)};      // fp16: one MFMA per four coordinates
+}
+
+#define CG_DECL(n) int launch_mfma_family_##n(const MfmaArgs&, bool query);   // one translation unit per launcher family (mfma_fam.hip)
+CG_DECL(0) CG_DECL(2) CG_DECL(4) CG_DECL(5) CG_DECL(6) CG_DECL(7) CG_DECL(8) CG_DECL(11) CG_DECL(12) CG_DECL(13)
+#undef CG_DECL
+
+mfma_launch_fn mfma_launcher(int family) {
+    switch (family) {
+        case COVGRAM_EQ: return launch_mfma_family_0;
+        case COVGRAM_RQ: return launch_mfma_family_2;
+        case COVGRAM_CAUCHY: return launch_mfma_family_4;
+        case COVGRAM_IMQ: return launch_mfma_family_5;
+        case COVGRAM_MATERNP: return launch_mfma_family_6;
+        case COVGRAM_DOT: return launch_mfma_family_7;
+        case COVGRAM_EXPDOT: return launch_mfma_family_8;
+        case FAM_EXPR_ISO: return launch_mfma_family_11;          // Sum / Product / Power composites of the profiles above
+        case FAM_EXPR_DOT: return launch_mfma_family_12;
+        case FAM_SUM_ISO: return launch_mfma_family_13;           // a Sum of 2-3 single-profile isotropic terms in one pass (common.hpp: SumParams)
+        default: return nullptr;
+    }
+}
+
+// relative sensitivity of a profile to an absolute error in s (natural units): |phi'/phi| at its maximum.  0: a dot-product factor (x.y itself:
+// no cancellation to gate); infinity: no matrix-core form (Exp = MaternP(0), gammaExp, Matern(nu), asin: not differentiable in s at 0 — direct
+// differences only)
+static double mfma_profile_sens(int fam, const KParams<double>& q) {
+    switch (fam) {
+        case COVGRAM_EQ: case COVGRAM_RQ: return 0.5;
+        case COVGRAM_CAUCHY: return 1.0;
+        case COVGRAM_IMQ: return 0.5 / q.param;                      // 1/sqrt(s + c^2) at s = 0 (param holds c^2)
+        case COVGRAM_MATERNP: return q.p < 1 ? INFINITY : (fabs(q.mp_d1) > 0.5 ? fabs(q.mp_d1) : 0.5);
+        case COVGRAM_DOT: case COVGRAM_EXPDOT: return 0.0;
+        default: return INFINITY;
+    }
+}
+// sensitivity x Power of a kernel.  A composite: every factor must be one of the smooth matrix-core profiles, and the relative errors of a product
+// add up: the largest sum over a term's factors of (sensitivity x power / l^2) takes the place of the single profile's (whose 1 / l^2 the caller applies)
+static double mfma_kernel_sens(const HostKernel& hk) {
+    if (hk.tu_family < COVGRAM_NFAMILY) return mfma_profile_sens(hk.tu_family, hk.kp) * hk.k.power;
+    double worst = 0.0;
+    int fi = 0;
+    for (int t = 0; t < hk.nterms; ++t) {
+        double sum = 0.0;
+        for (int f = 0; f < hk.nfac[t]; ++f, ++fi) {
+            const double s = mfma_profile_sens(hk.ffam[fi], hk.fkp[fi]);
+            if (!(s < INFINITY)) return INFINITY;
+            sum += s * hk.fkp[fi].power * hk.fkp[fi].gamma2;
+        }
+        worst = std::max(worst, sum);
+    }
+    return worst;
+}
+// (radius-gate quantity of an ISOTROPIC generic matrix-core MVM) / (what mfma_gen_eligible admits at mfma_gate_pct = 100): sensitivity x Power x
+// g^2 R^2 over 0.5 MFMA_GATE / log2(e) — the EQ gate in natural units —, single profiles and composites alike; infinity where a profile has no
+// matrix-core form
+static double mfma_gen_gate_frac(const HostKernel& hk, const covgram_points* X, const covgram_points* Y) {
+    const double limit = 0.5 * MFMA_GATE / LOG2E;
+    const double Pn = gate_radius2(X, Y);                                  // natural units: every factor of a composite has its own 1 / l^2
+    if (!(Pn < 1e30)) return INFINITY;
+    const double l2 = hk.tu_family < COVGRAM_NFAMILY ? hk.k.lengthscale * hk.k.lengthscale : 1.0;
+    return mfma_kernel_sens(hk) * Pn / l2 / limit;
+}
+
+bool mfma_gen_eligible(const covgram_ctx* ctx, const HostKernel& hk, const covgram_points* X, const covgram_points* Y, int nrhs) {
+    if (ctx->dense_variant == 1 || X->dtype != COVGRAM_F32 || Y->n == 0) return false;
+    if (mfma_launcher(hk.tu_family) == nullptr) return false;
+    // MaternP(p >= 1): up to round 4 the lane-per-row kernels (packed fp32 profile) beat the matrix-core ones (profile entry by entry) at d <= 4.
+    // Round 5: the profile arithmetic runs on register pairs (dense_mfma.hpp: mfma_profile_pairs) and the order is a compile-time constant of the
+    // instance: the general kernel is ahead at every d (16384 x 131072, d = 3: 428 against 543 us lane-per-row; d = 8: 631 against 862;
+    // profiles/r05_sum_fused_ab.txt), the symmetric one too (n = 131072, d = 3: 2.0 against 2.6 ms) — MaternP(p >= 1) no longer has an exception here.
+    if (!(mfma_kernel_sens(hk) < INFINITY)) return false;                      // some profile has no matrix-core form
+    const bool iso = hk.k.trait == COVGRAM_ISOTROPIC;
+    if (mfma_k2_for(X->d + (iso ? 1 : 0)) < 0) return false;
+    if (ctx->dense_variant == 2) return true;
+    if (!iso) {                                                                // x.y itself: no cancellation to gate, only the range
+        const double P = sqrt(X->max_norm2) * sqrt(Y->max_norm2);
+        return (hk.tu_family < COVGRAM_NFAMILY ? P / (hk.k.lengthscale * hk.k.lengthscale) : P) < 1e30;
+    }
+    return mfma_gen_gate_frac(hk, X, Y) <= 0.01 * (double)ctx->mfma_gate_pct;
+}
+
+// The generic kernels' split of the coordinates (round 5): the fp16 two-way split (dense_mfma.hpp: gen_row_fragments) for the isotropic single
+// profiles and one-pass Sums while (a) its instance exists — d + 2 positions in at most `maxk2` MFMAs of four —, and (b) the cloud lies inside
+// MFMA_F16_GATE / MFMA_GATE of the generic radius gate (mfma_gen_gate_frac: the quantity mfma_gen_eligible admits up to 1), the EQ kernel's rule
+// (option "mfma_f16": 0 never, 2 wherever the matrix-core gate admits the cloud).  Returns the format and sets the MFMAs per tile.
+static int mfma_gen_fmt(const covgram_ctx* ctx, const HostKernel& hk, int lfam, const covgram_points* X, const covgram_points* Y, int maxk2, int* K2) {
+    const bool iso = hk.k.trait == COVGRAM_ISOTROPIC;
+    const int d = X->d;
+    *K2 = mfma_k2_for(d + (iso ? 1 : 0));
+    if (ctx->mfma_f16 == 0 || !iso || lfam == FAM_EXPR_ISO || lfam == FAM_EXPR_DOT) return 0;
+    int k2h = (d + 2 + 3) / 4;                                   // d + 2 positions, four per MFMA; compiled: 1, 2, 3, 4, 6, 8 (d <= 30)
+    if (k2h == 5) k2h = 6; else if (k2h == 7) k2h = 8;
+    if (k2h > maxk2 || k2h > 8) return 0;
+    const double frac = mfma_gen_gate_frac(hk, X, Y);
+    if (!(frac <= 0.01 * (double)ctx->mfma_gate_pct * (ctx->mfma_f16 == 2 ? 1.0 : MFMA_F16_GATE / MFMA_GATE))) return 0;
+    *K2 = k2h;
+    return 1;
+}
+
+// The launcher family and coordinate pre-scale of a generic matrix-core MVM: a Sum of single-profile terms runs its one-pass form
+// (FAM_SUM_ISO: the pre-scale carries the first term's argument scale) unless option "sum_fused" = 0 keeps the composite interpreter.
+static int mfma_family_of(const covgram_ctx* ctx, const HostKernel& hk, float* gamma) {
+    if (ctx->sum_fused != 0 && sum_fusable(hk)) { *gamma = (float)make_sum_params(hk).gamma; return FAM_SUM_ISO; }
+    *gamma = (float)hk.kp.gamma;
+    return hk.tu_family;
+}
+
+// gramian(k, x) on a symmetric (upper-triangle) matrix-core form: the same point set on both sides and one right-hand side (option "mfma_sym" = 0:
+// never), the column-sum slab — one row of the padded n per panel of `tpp` row tiles; tpp = 0: not asked — within 16 GiB of the 288, and n from
+// `min_n` on, the size from which the form pays (option "mfma_sym" = 1: at any n)
+static bool mfma_sym_admits(const covgram_ctx* ctx, const covgram_points* X, const covgram_points* Y, int nrhs, int tpp, int64_t min_n) {
+    if (ctx->mfma_sym == 0 || nrhs != 1 || X->dptr != Y->dptr || X->n != Y->n) return false;
+    if (tpp > 0) {
+        const int64_t panels = sym_panels((X->n + 31) / 32, tpp);
+        if ((size_t)panels * (size_t)(panels * 32 * tpp) * sizeof(float) > ((size_t)16 << 30)) return false;
+    }
+    return ctx->mfma_sym == 1 || X->n >= min_n;
+}
+// ... of the generic profiles.  heavy: the profile costs several exponentials (at d > 4: the all-entries kernel's cost grows with the fragment length,
+// the symmetric kernel's floor does not — tools/sym_threshold_sweep.py, MaternP(2) d = 8: n = 10000 60.0 / 59.8 us, 12000 77.4 / 66.7)
+static int64_t mfma_gen_sym_min_n(const HostKernel& hk, int d) {
+    const bool heavy = hk.tu_family == COVGRAM_MATERNP || hk.tu_family == COVGRAM_RQ || hk.tu_family >= COVGRAM_NFAMILY;
+    return heavy ? (d > 4 ? 10000 : MFMA_SYM_MIN_N_HEAVY) : MFMA_SYM_MIN_N_EQ_WIDE;
+}
+
+bool mfma_eq_sym_eligible(const covgram_ctx* ctx, const HostKernel& hk, const covgram_points* X, const covgram_points* Y, int nrhs) {
+    if (!mfma_eq_eligible(ctx, hk, X, Y, nrhs)) return false;
+    const int tpp = mfma_k2_for(X->d) > MFMA_NARROW_MAXK2 ? 4 : 8;                  // row tiles per panel (dense_mfma_sym_wide_kernel: 4)
+    return mfma_sym_admits(ctx, X, Y, nrhs, tpp, X->d <= 4 ? MFMA_SYM_MIN_N_EQ : MFMA_SYM_MIN_N_EQ_WIDE);
+}
+
+// the generic profiles' symmetric form: same conditions on top of the generic matrix-core gate (hk: gamma = 1/l parameter block)
+bool mfma_gen_sym_eligible(const covgram_ctx* ctx, const HostKernel& hk, const covgram_points* X, const covgram_points* Y, int nrhs) {
+    if (!mfma_sym_admits(ctx, X, Y, nrhs, 0, 0) || !mfma_gen_eligible(ctx, hk, X, Y, nrhs)) return false;
+    const int k2 = mfma_k2_for(X->d + (hk.k.trait == COVGRAM_ISOTROPIC ? 1 : 0));
+    float gam_unused;
+    const int lfam = mfma_family_of(ctx, hk, &gam_unused);
+    if (lfam == FAM_SUM_ISO && k2 > 8) return false;                              // no one-pass symmetric instance: one (symmetric) MVM per term instead
+    // (tiles per panel of the one-row-tile form: an upper bound of the slab whichever form runs — fewer tiles per panel = more panels)
+    return mfma_sym_admits(ctx, X, Y, nrhs, mfma_sym_tiles_per_panel(lfam, k2), mfma_gen_sym_min_n(hk, X->d));
+}
+
+// covgram_mvm: does this composite take the one-pass Sum kernels (instead of one MVM per term)?
+bool sum_fused_applies(const covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, int nrhs) {
+    if (ctx->sum_fused == 0 || k == nullptr || k->family != COVGRAM_COMPOSITE || X->dtype != COVGRAM_F32 || Y->n == 0) return false;
+    HostKernel hk;
+    if (make_host_kernel(k, COVGRAM_F32, false, &hk) != COVGRAM_OK) return false;
+    if (!sum_fusable(hk) || !mfma_gen_eligible(ctx, hk, X, Y, nrhs)) return false;
+    // gramian(k, x) at d >= 16: the one-pass symmetric kernel has no instance (K2 > 8), and one symmetric MVM per term evaluates half the pairs
+    // of the one-pass general kernel
+    if (mfma_sym_admits(ctx, X, Y, nrhs, 0, mfma_gen_sym_min_n(hk, X->d)) && mfma_k2_for(X->d + 1) > 8) return false;
+    // Measured (d = 3, n = 131072; profiles/r05_sum_fused_ab.txt, r05_sum_general_ab.txt): what one pass shares is the matrix-core work, the weighted
+    // sums and the slabs — every term's transcendentals remain, and they are what the kernels are bound by.  Three terms: 4.07 against 4.83 ms for one
+    // symmetric MVM per term, 0.95 / 1.01 against 0.98 / 1.09 on a 16384-row shard.  Two terms: one MVM per term wins or ties on both forms (symmetric
+    // 3.05 against 3.32; shard, MaternP(2) + EQ: 0.62 against 0.71 — the EQ term costs 0.15 on its own kernel —, MaternP + MaternP 0.83 against 0.87,
+    // RQ + MaternP 0.79 against 0.78): the one-pass kernel's wave-uniform family switches and its one-tile loop cost more than the second pass saves.
+    // Option "sum_fused" = 1 takes the one-pass kernels wherever they exist (tests).
+    if (ctx->sum_fused == 1) return true;
+    return hk.nterms >= 3;
+}
+
+// ---- Steps the drivers share --------------------
+// where a launch of plan `pl` leaves its sums: y itself, or (js > 1) the split-J slab of workspace slot 1, `nrpad` columns per chunk
+static int split_out(covgram_ctx* ctx, const ColumnPlan& pl, int nrpad, float* y, float** out) {
+    *out = y;
+    return pl.js == 1 ? COVGRAM_OK : ws_reserve(ctx, 1, (size_t)pl.js * nrpad * pl.npad * sizeof(float), (void**)out);
+}
+// y[:, 0..nr) <- alpha (the js slab rows added in fixed order) + beta y
+static void reduce_split(covgram_ctx* ctx, const float* slab, const ColumnPlan& pl, int nrpad, float* y, int64_t n, int64_t ldy, int nr, double alpha,
+                         double beta) {
+    hipLaunchKernelGGL(dense_reduce_kernel<float>, dim3((unsigned)((n + 63) / 64), nr), dim3(256), 0, ctx->stream, slab, pl.npad, nrpad, (int)pl.js, y, n,
+                       ldy, nr, (float)alpha, (float)beta);
+}
+
+// the generic kernels' column fragments (norm pseudo-coordinate) and the weights of `nr` right-hand sides in NR slots per tile, packed per MVM into
+// workspace slot 0, with `extra` bytes behind them for the caller (*W + ntile NR 32)
+static int gen_fragments(covgram_ctx* ctx, const covgram_points* Y, const float* a, int64_t lda, int nr, int NR, int K2, float gam, bool iso, int fmt,
+                         size_t extra, const uint4** PB, float** W) {
+    const int64_t ntile = (Y->n + 31) / 32, pe = ntile * K2 * 64;
+    void* P;
+    int rc = ws_reserve(ctx, 0, (size_t)ntile * ((size_t)K2 * 64 * sizeof(uint4) + (size_t)NR * 32 * sizeof(float)) + extra, &P);
+    if (rc) return rc;
+    *PB = (const uint4*)P;
+    *W = (float*)((uint4*)P + pe);
+    hipLaunchKernelGGL(mfma_pack_gen_kernel, dim3((unsigned)((pe + 255) / 256)), dim3(256), 0, ctx->stream, (const float*)Y->dptr, Y->n, Y->d, a, lda, nr, 0,
+                       (uint4*)P, *W, K2, NR, gam, iso ? 1 : 0, (const float*)Y->center, fmt);
+    return COVGRAM_OK;
+}
+
+// ---- EQ, all n m entries: dense_mfma_eq_kernel --------------------
 // resident single-wave workgroups per CU of the kernel instance (register-limited), for the grid sizing below
 template <int K2, int RT>
 static int mfma_blocks_per_cu() {
@@ -587,36 +408,31 @@ static int mfma_blocks_per_cu() {
     }
     return cached;
 }
-template <int K2>
-static int mfma_blocks(int rt) {
-    if constexpr (K2 <= 8) { if (rt == 2) return mfma_blocks_per_cu<K2, 2>(); }
-    return mfma_blocks_per_cu<K2, 1>();
+// the one place that spells dense_mfma_eq_kernel's argument list; a.grid counts WAVES (x: row blocks of 32 RT rows)
+template <int K2, int RT, int WPB, int LDS, int STAMP, int FMT>
+static void eq_launch(covgram_ctx* ctx, const MfmaArgs& a, dim3* launched) {
+    ctx->last_mfma_instance = (int64_t)K2 * 100000 + RT * 10000 + WPB * 1000 + LDS * 100 + STAMP * 10 + FMT;
+    *launched = dim3((a.grid.x + WPB - 1) / WPB, a.grid.y);
+    hipLaunchKernelGGL((dense_mfma_eq_kernel<K2, RT, WPB, LDS, STAMP, FMT>), *launched, dim3(64 * WPB), 0, a.stream, a.X, a.n, a.d, a.PB, a.W, a.ntile, a.out,
+                       a.npad, a.tchunk, a.g, a.alpha, a.beta, a.final_store, a.Cn, STAMP ? a.stamps : nullptr, a.tickets, a.yfinal, a.EF, a.mcols);
 }
-
-template <int K2, int FMT = 0>
-static void launch_mfma(int rt, bool lds4, dim3 grid, hipStream_t st, const float* X, int64_t n, int32_t d, const uint4* PB, const float* W,
-                        int64_t ntile, float* out, int64_t npad, int64_t tchunk, float g, float alpha, float beta, int final_store, const float* Cn,
-                        unsigned long long* stamps, dim3* launched, unsigned* tickets, float* yfinal, const float* EF, int64_t mcols, int64_t* inst) {
+// the instance of (K2, split) for this plan: row tiles per wave a.RT, the LDS-shared form (a.lds), the diagnostic build (a.stamps)
+template <int K2, int FMT>
+static void eq_launch_instance(covgram_ctx* ctx, const MfmaArgs& a, dim3* launched) {
     constexpr bool NARROW = K2 <= MFMA_NARROW_MAXK2;
-    unsigned long long* const ns = nullptr;
-    auto enc = [](int k2, int rtt, int wpb, int lds, int stamp) { return (int64_t)k2 * 100000 + rtt * 10000 + wpb * 1000 + lds * 100 + stamp * 10 + FMT; };
-    if (lds4 && K2 <= 2 && grid.x >= 1024) {   // d <= 4 and many row tiles: eight waves share each column tile (C2: 1.569 -> 1.550 ms; not for a 16384-row shard)
-        *launched = dim3((grid.x + 7) / 8, grid.y);
-        if constexpr (K2 <= 2) { if (stamps) { *inst = enc(K2, 2, 8, 1, 1); hipLaunchKernelGGL((dense_mfma_eq_kernel<K2, 2, 8, 1, 1, FMT>), *launched, dim3(512), 0, st, X, n, d, PB, W, ntile, out, npad, tchunk, g, alpha, beta, final_store, Cn, stamps, tickets, yfinal, EF, mcols); return; } }
-        *inst = enc((K2 <= 2 ? K2 : 1), 2, 8, 1, 0); hipLaunchKernelGGL((dense_mfma_eq_kernel<(K2 <= 2 ? K2 : 1), 2, 8, 1, 0, FMT>), *launched, dim3(512), 0, st, X, n, d, PB, W, ntile, out, npad, tchunk, g, alpha, beta, final_store, Cn, ns, tickets, yfinal, EF, mcols);
-    } else if (lds4) {   // 256-thread workgroups: four waves on consecutive row tiles share the column tiles through LDS
-        *launched = dim3((grid.x + 3) / 4, grid.y);
-        if constexpr (K2 == 3 || K2 == 4) { if (rt == 4) { *inst = enc(K2, 4, 4, 1, 0); hipLaunchKernelGGL((dense_mfma_eq_kernel<K2, 4, 4, 1, 0, FMT>), *launched, dim3(256), 0, st, X, n, d, PB, W, ntile, out, npad, tchunk, g, alpha, beta, final_store, Cn, ns, tickets, yfinal, EF, mcols); return; } }
-        if constexpr (K2 == 1 || K2 == 2 || K2 == 4) { if (stamps) { *inst = enc(K2, 2, 4, 1, 1); hipLaunchKernelGGL((dense_mfma_eq_kernel<K2, 2, 4, 1, 1, FMT>), *launched, dim3(256), 0, st, X, n, d, PB, W, ntile, out, npad, tchunk, g, alpha, beta, final_store, Cn, stamps, tickets, yfinal, EF, mcols); return; } }
+    const bool stamp = a.stamps != nullptr;
+    if (a.lds) {
+        if constexpr (K2 <= 2) {   // d <= 4 and many row tiles: eight waves share each column tile (C2: 1.569 -> 1.550 ms; not for a 16384-row shard)
+            if (a.grid.x >= 1024) return stamp ? eq_launch<K2, 2, 8, 1, 1, FMT>(ctx, a, launched) : eq_launch<K2, 2, 8, 1, 0, FMT>(ctx, a, launched);
+        }
+        // 256-thread workgroups: four waves on consecutive row tiles share the column tiles through LDS
+        if constexpr (K2 == 3 || K2 == 4) { if (a.RT == 4) return eq_launch<K2, 4, 4, 1, 0, FMT>(ctx, a, launched); }
+        if constexpr (K2 == 1 || K2 == 2 || K2 == 4) { if (stamp) return eq_launch<K2, 2, 4, 1, 1, FMT>(ctx, a, launched); }
         constexpr int LDSF = (NARROW || K2 == 6) ? 1 : 2;   // six MFMAs per tile: stages of four tiles too (round 5; one tile per stage before, as the longer fragments still are)
-        *inst = enc(K2, (NARROW ? 2 : 1), 4, LDSF, 0); hipLaunchKernelGGL((dense_mfma_eq_kernel<K2, (NARROW ? 2 : 1), 4, LDSF, 0, FMT>), *launched, dim3(256), 0, st, X, n, d, PB, W, ntile, out, npad, tchunk, g, alpha, beta, final_store, Cn, ns, tickets, yfinal, EF, mcols);
-    } else if (rt == 2 && K2 <= 8) {
-        *launched = grid;
-        *inst = enc((K2 <= 8 ? K2 : 1), 2, 1, 0, 0); hipLaunchKernelGGL((dense_mfma_eq_kernel<(K2 <= 8 ? K2 : 1), 2, 1, 0, 0, FMT>), grid, dim3(64), 0, st, X, n, d, PB, W, ntile, out, npad, tchunk, g, alpha, beta, final_store, Cn, ns, tickets, yfinal, EF, mcols);
-    } else {
-        *launched = grid;
-        *inst = enc(K2, 1, 1, 0, 0); hipLaunchKernelGGL((dense_mfma_eq_kernel<K2, 1, 1, 0, 0, FMT>), grid, dim3(64), 0, st, X, n, d, PB, W, ntile, out, npad, tchunk, g, alpha, beta, final_store, Cn, ns, tickets, yfinal, EF, mcols);
+        return eq_launch<K2, (NARROW ? 2 : 1), 4, LDSF, 0, FMT>(ctx, a, launched);
     }
+    if constexpr (K2 <= 8) { if (a.RT == 2) return eq_launch<K2, 2, 1, 0, 0, FMT>(ctx, a, launched); }
+    eq_launch<K2, 1, 1, 0, 0, FMT>(ctx, a, launched);
 }
 
 // the column fragments and norm fraction factors of point set Y for (g, K2): packed once into the handle and reused by every
@@ -671,25 +487,18 @@ static int eq_fragments(covgram_ctx* ctx, const covgram_points* Y, int K2, float
 int mvm_eq_mfma(covgram_ctx* ctx, const HostKernel& hk, const covgram_points* X, const covgram_points* Y, const float* a, float* y,
                 double alpha, double beta) {
     const int64_t n = X->n, m = Y->n;
-    const int d = X->d;
-    // Which split (round 4).  The bf16 three-way split is exact to 2^-24 |x~_c y~_c| per coordinate and costs one MFMA per TWO coordinates.  The
-    // fp16 two-way split (x~ = h1 + h2, 11 + 11 bits; products h1 h1, h1 h2, h2 h1) drops terms of ~2^-22 |x~_c y~_c| — the size of ONE fp32 rounding
-    // of the dot product itself, which the accumulator commits anyway — and covers FOUR coordinates per MFMA: half the matrix-core work per pair.
-    // The d = 5 ... 8 kernels are power-bound (2.0 GHz under C3's shard kernel, profiles/r04_c3_power_bound.txt), so that is both fewer cycles and a
-    // higher clock.  Taken while BOTH clouds lie within g^2 R^2 <= MFMA_F16_GATE (the added exponent error grows with the radius like the
-    // accumulator's own: common.hpp); beyond it, up to MFMA_GATE, the bf16 split serves as before.  Option "mfma_f16": -1 / 1 = this rule,
-    // 0 = never, 2 = wherever the matrix-core gate admits the cloud (measurements: tools/f16_split_ab.py).
-    const double g2r2 = 1.4426950408889634074 / (hk.k.lengthscale * hk.k.lengthscale) * gate_radius2(X, Y);
-    const int fmt = (ctx->mfma_f16 != 0 && g2r2 <= (ctx->mfma_f16 == 2 ? mfma_gate_of(ctx) : mfma_f16_gate_of(ctx))) ? 1 : 0;
+    const EqSplit sp = eq_split(ctx, hk, X, Y);
+    const int fmt = sp.fmt, K2 = sp.K2;
     ctx->last_mfma_f16 = fmt;
-    const int K2 = fmt ? eq_k2_for(2 * ((d + 3) / 4)) : eq_k2_for(d);      // fp16: one MFMA per four coordinates
-    CG_REQUIRE(K2 > 0, COVGRAM_EUNSUPPORTED, "dense_mfma: d = %d has no matrix-core instance", d);
-    const int64_t ntile = (m + 31) / 32;
-    const float g = (float)(sqrt(1.4426950408889634074) / hk.k.lengthscale);
-    const float* Cn = (const float*)Y->center;                    // both sides are taken relative to the column side's centre
-    const uint4* PB;
+    CG_REQUIRE(K2 > 0, COVGRAM_EUNSUPPORTED, "dense_mfma: d = %d has no matrix-core instance", X->d);
+    MfmaArgs ma;
+    ma.X = (const float*)X->dptr; ma.n = n; ma.d = X->d; ma.ntile = (m + 31) / 32; ma.mcols = m; ma.K2 = K2; ma.fmt = fmt; ma.stream = ctx->stream;
+    ma.g = (float)(sqrt(LOG2E) / hk.k.lengthscale);
+    ma.Cn = (const float*)Y->center;                              // both sides are taken relative to the column side's centre
+    ma.alpha = (float)(alpha * hk.kp.scale); ma.beta = (float)beta; ma.yfinal = y;
+    const int64_t ntile = ma.ntile;
     const float* EF;
-    int rc = eq_fragments(ctx, Y, K2, g, Cn, &PB, &EF, fmt);
+    int rc = eq_fragments(ctx, Y, K2, ma.g, ma.Cn, &ma.PB, &EF, fmt);
     if (rc) return rc;
     // the weights a_j exp2(f_j) of THIS right-hand side: formed inside the kernel (round 4) — the wave that fetches a tile loads a_j and the cached
     // exp2(f_j) with it and multiplies where the weight goes to LDS at the end of the stage.  (Rounds 1-2 had measured the in-kernel product 3 %
@@ -700,48 +509,34 @@ int mvm_eq_mfma(covgram_ctx* ctx, const HostKernel& hk, const covgram_points* X,
     // a — the pack launch copies the weights first, as every dense path did before round 4 (include/covgram.h: aliasing)
     const bool overlap = (const char*)a < (const char*)(y + n) && (const char*)y < (const char*)(a + m);
     const bool fuse_w = ctx->mfma_fuse_w != 0 && !overlap;
-    const float* W = a;
+    ma.W = a; ma.EF = EF;
     if (!fuse_w) {
         void* Wp;
         rc = ws_reserve(ctx, 0, (size_t)ntile * 32 * sizeof(float), &Wp);
         if (rc) return rc;
         hipLaunchKernelGGL(mfma_pack_w_kernel, dim3((unsigned)((ntile * 32 + 255) / 256)), dim3(256), 0, ctx->stream, a, EF, (float*)Wp, m, ntile * 32);
-        W = (const float*)Wp;
+        ma.W = (const float*)Wp; ma.EF = nullptr;
     }
-    const float* EFk = fuse_w ? EF : nullptr;
     // split the column tiles so that the grid holds ~CUs * 128 waves (as the lane-per-row kernel, profiles/r01_quickbench_wg64.txt)
     // row tiles per wave: two share every B fragment while the state fits (d <= 8); option "rows_per_lane" = 1 / 2 forces it
     int rt = ctx->rows_per_lane == 1 ? 1 : (ctx->rows_per_lane == 2 ? 2 : (K2 <= MFMA_NARROW_MAXK2 ? 2 : 1));
     if (K2 > 8) rt = 1;
     // grid = a whole number (4) of rounds of resident waves: a fractional last round costs up to one round of idle SIMDs
     int nb = 16;
-#define CG_NB_CASE(K) case K: nb = mfma_blocks<K>(rt); break;
-    switch (K2) {
-        CG_NB_CASE(1) CG_NB_CASE(2) CG_NB_CASE(3) CG_NB_CASE(4) CG_NB_CASE(6) CG_NB_CASE(8) CG_NB_CASE(12) CG_NB_CASE(16)
-        default: break;
-    }
-#undef CG_NB_CASE
-    struct Plan { int rt; int64_t rowtiles, npad, js, tchunk; bool lds4; };
+    mfma_for_k2(K2, [&](auto k) {
+        constexpr int K = decltype(k)::value;
+        if constexpr (K <= 8) { if (rt == 2) { nb = mfma_blocks_per_cu<K, 2>(); return; } }
+        nb = mfma_blocks_per_cu<K, 1>();
+    });
+    struct Plan { ColumnPlan col; int rt; bool lds4; };
     auto plan_for = [&](int r) {
         Plan pl; pl.rt = r;
-        pl.rowtiles = (n + 32 * r - 1) / (32 * r);
-        pl.npad = pl.rowtiles * 32 * r;
         const int64_t target = ctx->target_wgs > 0 ? ctx->target_wgs : (int64_t)ctx->num_cus * nb * 4;
-        int64_t js = ctx->jsplit > 0 ? ctx->jsplit : std::max<int64_t>(1, (target + pl.rowtiles / 2) / pl.rowtiles);
-        // GP-sized problems (n = 8k ... 32k): a wave's prologue (row fragments), pipeline fill and epilogue (shuffles, slab row) are
-        // worth ~40 column tiles of work, so the split stops at 64 tiles per wave — as long as the grid still holds >= 2048 waves,
-        // half of the chip's wave slots (tools/eq_small_sweep.py: d = 3, n = 16384 45.9 -> 37.9 us, n = 32768 118.8 -> 113.1;
-        // d = 8, n = 16384 60.9 -> 47.4, n = 32768 175 -> 152; n = 8192 17.7 -> 16.9 / 25.3 -> 21.8 us)
-        // (few rows — prediction shapes —: the 2048-wave floor itself stops at 16 tiles per wave: 256 x 65536, d = 3: 26.8 -> 22.2 us)
-        if (ctx->jsplit <= 0) js = std::max<int64_t>(std::min<int64_t>((2048 + pl.rowtiles - 1) / pl.rowtiles, std::max<int64_t>(1, ntile / 16)),
-                                                     std::min<int64_t>(js, std::max<int64_t>(1, ntile / 64)));
-        js = std::max<int64_t>(1, std::min<int64_t>(js, std::max<int64_t>(1, ntile / 8)));     // >= 8 tiles (256 columns) per wave
-        pl.tchunk = (ntile + js - 1) / js;
-        pl.js = (ntile + pl.tchunk - 1) / pl.tchunk;
+        pl.col = plan_columns(n, ntile, 32 * r, target, ctx->jsplit, 8, 64, 2048, 16);     // (the 64-tile stop and its 2048-wave floor: mfma_plan.hpp)
         // long column chunks: four waves of a workgroup share every column tile through LDS; short chunks would only pay its
         // prologue and barriers (tools/mfma_lds_ab.py)
         pl.lds4 = ((r >= 2 && K2 <= MFMA_NARROW_MAXK2) || (r == 1 && K2 > MFMA_NARROW_MAXK2)) &&
-                  (ctx->mfma_lds == 1 || (ctx->mfma_lds < 0 && pl.tchunk >= MFMA_LDS_MIN_TILES && pl.rowtiles >= 64));
+                  (ctx->mfma_lds == 1 || (ctx->mfma_lds < 0 && pl.col.tchunk >= MFMA_LDS_MIN_TILES && pl.col.rowtiles >= 64));
         return pl;
     };
     Plan pl = plan_for(rt);
@@ -753,58 +548,50 @@ int mvm_eq_mfma(covgram_ctx* ctx, const HostKernel& hk, const covgram_points* X,
         const Plan p4 = plan_for(4);
         if (p4.lds4) pl = p4;
     }
-    rt = pl.rt;
-    const int64_t rowtiles = pl.rowtiles, npad = pl.npad, tchunk = pl.tchunk;
-    const int64_t js = pl.js;
-    const bool lds4 = pl.lds4;
-    const double alpha_eff = alpha * hk.kp.scale;
-    float* out = y;
-    if (js > 1) { void* slab; rc = ws_reserve(ctx, 1, (size_t)js * npad * sizeof(float), &slab); if (rc) return rc; out = (float*)slab; }
-    const dim3 grid((unsigned)rowtiles, (unsigned)js);
-    const int fs = js == 1 ? 1 : 0;
+    const ColumnPlan& col = pl.col;
+    ma.RT = pl.rt; ma.lds = pl.lds4 ? 1 : 0;
+    ma.npad = col.npad; ma.tchunk = col.tchunk; ma.final_store = col.js == 1 ? 1 : 0;
+    ma.grid = dim3((unsigned)col.rowtiles, (unsigned)col.js);
+    rc = split_out(ctx, col, 1, y, &ma.out);
+    if (rc) return rc;
     // option "mfma_stamp": the clock-stamping diagnostic build of the two LDS-shared instances (C2's and C3's kernels)
-    unsigned long long* stamps = nullptr;
     ctx->stamp_count = 0;
-    if (ctx->mfma_stamp && lds4 && (K2 == 1 || K2 == 2 || K2 == 4)) {
-        const size_t need = (size_t)rowtiles * js * 4 * sizeof(unsigned long long);
+    if (ctx->mfma_stamp && pl.lds4 && (K2 == 1 || K2 == 2 || K2 == 4)) {
+        const size_t need = (size_t)col.rowtiles * col.js * 4 * sizeof(unsigned long long);
         if (need > ctx->stamp_cap) {
             if (ctx->stamp_buf) { CG_CHECK_HIP(hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->stamp_buf); ctx->stamp_buf = nullptr; ctx->stamp_cap = 0; }
             CG_CHECK_HIP(hipMalloc(&ctx->stamp_buf, need));
             ctx->stamp_cap = need;
         }
         CG_CHECK_HIP(hipMemsetAsync(ctx->stamp_buf, 0, need, ctx->stream));
-        stamps = (unsigned long long*)ctx->stamp_buf;
+        ma.stamps = (unsigned long long*)ctx->stamp_buf;
     }
     // js > 1: the kernel can sum its own split-J slab (the last workgroup of each row block to arrive, fixed order; pack.hpp).  Measured
     // (profiles/r04_inkernel_reduce_ab.txt, separate launch -> in-kernel): n = 2048 16.2 -> 13.2 us, 4096 16.3 -> 14.9, 8192 17.2 -> 18.8,
     // 16384 37.9 -> 37.2, rank 0 of 8's shard of C2 214.4 -> 213.5, of 16 116.3 -> 115.0: it pays where the whole MVM is launch latency
     // and is noise elsewhere, so the automatic rule takes it up to n = 4096 (option "inkernel_reduce" = 1 / 0 forces it on / off)
-    unsigned* tickets = nullptr;
-    const bool ikr = inkernel_reduce_on(ctx, true, n, js);
+    const bool ikr = inkernel_reduce_on(ctx, true, n, col.js);
     ctx->last_inkernel_reduce = ikr ? 1 : 0;
-    if (ikr) { rc = tickets_reserve(ctx, (size_t)rowtiles, &tickets); if (rc) return rc; }
-    ctx->last_mfma_lds = lds4 ? 1 : 0;
+    if (ikr) { rc = tickets_reserve(ctx, (size_t)col.rowtiles, &ma.tickets); if (rc) return rc; }
+    ctx->last_mfma_lds = ma.lds;
     dim3 launched;
     {
-    TimerScope tm(ctx);
-#define CG_MFMA_CASE(K) case K: if (fmt) { if constexpr (K <= 8) launch_mfma<K, 1>(rt, lds4, grid, ctx->stream, (const float*)X->dptr, n, d, PB, W, ntile, out, npad, tchunk, g, (float)alpha_eff, (float)beta, fs, Cn, stamps, &launched, tickets, y, EFk, m, &ctx->last_mfma_instance); } else launch_mfma<K>(rt, lds4, grid, ctx->stream, (const float*)X->dptr, n, d, PB, W, ntile, out, npad, tchunk, g, (float)alpha_eff, (float)beta, fs, Cn, stamps, &launched, tickets, y, EFk, m, &ctx->last_mfma_instance); break;
-    switch (K2) {
-        CG_MFMA_CASE(1) CG_MFMA_CASE(2) CG_MFMA_CASE(3) CG_MFMA_CASE(4) CG_MFMA_CASE(6) CG_MFMA_CASE(8) CG_MFMA_CASE(12) CG_MFMA_CASE(16)
-        default: set_error("dense_mfma: K2 = %d not compiled", K2); return COVGRAM_EUNSUPPORTED;
+        TimerScope tm(ctx);
+        const bool compiled = mfma_for_k2(K2, [&](auto k) {
+            constexpr int K = decltype(k)::value;
+            if (!fmt) eq_launch_instance<K, 0>(ctx, ma, &launched);
+            else if constexpr (K <= 8) eq_launch_instance<K, 1>(ctx, ma, &launched);   // (the fp16 split: d <= 32 in at most eight MFMAs)
+        });
+        CG_REQUIRE(compiled, COVGRAM_EUNSUPPORTED, "dense_mfma: K2 = %d not compiled", K2);
     }
-#undef CG_MFMA_CASE
-    }
-    if (stamps) ctx->stamp_count = (size_t)launched.x * launched.y;
-    if (js > 1 && !ikr)
-        hipLaunchKernelGGL(dense_reduce_kernel<float>, dim3((unsigned)((n + 63) / 64), 1), dim3(256), 0, ctx->stream, (const float*)out, npad, 1,
-                           (int)js, y, n, n, 1, (float)alpha_eff, (float)beta);
+    if (ma.stamps) ctx->stamp_count = (size_t)launched.x * launched.y;
+    if (col.js > 1 && !ikr) reduce_split(ctx, ma.out, col, 1, y, n, n, 1, alpha * hk.kp.scale, beta);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("dense_mfma launch failed: %s", hipGetErrorString(e)); return COVGRAM_EHIP; }
     return COVGRAM_OK;
 }
 
-// ------------------------------------------------------------------------------------------------------------------------
-// Symmetric Gramian (gramian(k, x): y IS x): every tile on or above the diagonal is evaluated ONCE and used twice,
+// ---- Symmetric Gramian (gramian(k, x): y IS x) ----: every tile on or above the diagonal is evaluated ONCE and used twice,
 //     b_i += e_i sum_j (a_j e_j) E_ij          (row sums, as dense_mfma_eq_kernel)
 //     b_j += e_j sum_i (a_i e_i) E_ij          (column sums of the same exponentials, tiles strictly above the diagonal)
 // with E_ij = exp2(x~_i . x~_j + k_i + k_j) from the MFMA and e = exp2(f) in (1/2, 1] the fraction factors of the half-norms
@@ -819,7 +606,7 @@ int mvm_eq_mfma(covgram_ctx* ctx, const HostKernel& hk, const covgram_points* X,
 // per-chunk slab R[c][i]; the column sums of a tile are added over the 8 waves in LDS in fixed order and stored to
 // S[p][j] (each (p, tile) exactly once); dense_mfma_sym_reduce_kernel adds R over the panel's chunks and S over the panels
 // p <= panel(j) in fixed order: deterministic, no float atomics.
-// ------------------------------------------------------------------------------------------------------------------------
+//
 // b_i = alpha (sum_{chunks c the panel of i visited} R[c][i] + e_i sum_{p <= panel(i)} S[p][i]) + beta b_i, fixed order
 // (EF = the fraction factors e_i the EQ form's column sums still lack; nullptr: generic form).
 // 64 rows per workgroup, the panel index strided over the 4 waves (as dense_reduce_kernel).
@@ -862,43 +649,97 @@ __global__ __launch_bounds__(1024) void dense_mfma_sym_reduce_kernel(int64_t n, 
     }
 }
 
-bool mfma_eq_sym_eligible(const covgram_ctx* ctx, const HostKernel& hk, const covgram_points* X, const covgram_points* Y, int nrhs) {
-    if (ctx->mfma_sym == 0 || X->dptr != Y->dptr || X->n != Y->n) return false;       // gramian(k, x): the same point set on both sides
-    if (!mfma_eq_eligible(ctx, hk, X, Y, nrhs)) return false;
-    const int tpp = eq_k2_for(X->d) > MFMA_NARROW_MAXK2 ? 4 : 8;                    // row tiles per panel (dense_mfma_sym_wide_kernel: 4)
-    const int64_t ntile = (X->n + 31) / 32, panels = (ntile + tpp - 1) / tpp;
-    if ((size_t)panels * (size_t)(panels * 32 * tpp) * sizeof(float) > ((size_t)16 << 30)) return false;   // column-sum slab <= 16 GiB of the 288
-    return ctx->mfma_sym == 1 || X->n >= (X->d <= 4 ? MFMA_SYM_MIN_N_EQ : MFMA_SYM_MIN_N_EQ_WIDE);
+// the symmetric kernel of this call, resolved from the kernel, the cloud and the options: launcher family and its coordinate pre-scale (generic form), split of
+// the coordinates and MFMAs per tile, row tiles per wave (2: dense_mfma_sym2_kernel) and per panel, EQ form at K2 > 4: the staged 8-wave kernel
+struct SymForm { int lfam = COVGRAM_EQ; float gam = 0.0f; int fmt = 0, K2 = 0, rt = 1, tpp = 8; bool staged_wide = false; };
+static SymForm sym_form(covgram_ctx* ctx, const HostKernel& hk, const covgram_points* X, bool fast) {
+    SymForm f;
+    if (fast) {
+        const EqSplit sp = eq_split(ctx, hk, X, X);
+        f.fmt = sp.fmt; f.K2 = sp.K2;
+        // the EQ forms up to four MFMAs per tile: two row tiles per wave, 4-wave workgroups (dense_mfma_sym2.hpp) — option "mfma_sym_rt": 2 = that,
+        // -1 = that up to two MFMAs per tile, 1 = the 8-wave one-row-tile kernel
+        f.rt = (f.K2 <= (ctx->mfma_sym_rt == 2 ? MFMA_NARROW_MAXK2 : 2) && ctx->mfma_sym_rt != 1) ? 2 : 1;
+        // Six MFMAs per tile (d = 17 .. 24 with the fp16 split, 11 .. 12 with bf16): the STAGED 8-wave kernel (four column tiles per stage and barrier, one
+        // tile at a time in registers) instead of the one-tile-per-stage 4-wave kernel — round 5, tools/wide_staged_ab.py: n = 131072, d = 24 2.19 -> 1.89 ms,
+        // d = 20 2.16 -> 1.82.  Eight MFMAs per tile need 169 registers there (two waves per SIMD): 2.55 -> 2.60 ms, so they keep the 4-wave kernel
+        // (option "mfma_sym_st" = 16 forces the staged form for measurements).
+        f.staged_wide = f.K2 == 6 || (f.K2 == 8 && f.fmt == 1 && ctx->mfma_sym_st == 16);
+        // row tiles per panel: 8 waves x 1 tile (or 4 x 2), or 4 x 1 for long fragments (dense_mfma.hpp)
+        f.tpp = (f.K2 > MFMA_NARROW_MAXK2 && !f.staged_wide) ? 4 : 8;
+        return f;
+    }
+    const bool iso = hk.k.trait == COVGRAM_ISOTROPIC;
+    f.lfam = mfma_family_of(ctx, hk, &f.gam);
+    ctx->last_sum_fused = f.lfam == FAM_SUM_ISO ? 1 : 0;
+    // the fp16 split where the staged (narrow) symmetric kernel of the family has the instance (dense_mfma.hpp: mfma_sym_narrow_maxk2)
+    f.fmt = mfma_gen_fmt(ctx, hk, f.lfam, X, X, f.lfam == FAM_SUM_ISO ? 2 : 8, &f.K2);   // (the Sum: its staged kernel only)
+    // at one or two MFMAs per tile: two row tiles per wave as the EQ form (dense_mfma_sym2.hpp; option "mfma_sym_rt" = 1: the one-row-tile panels)
+    f.rt = (ctx->mfma_sym_rt != 1 && mfma_sym2_has(f.lfam, f.K2)) ? 2 : 1;
+    f.tpp = mfma_sym_tiles_per_panel(f.lfam, f.K2, f.rt);   // 8 waves x 1 tile, 4 for the heavy profiles' 3-waves-per-SIMD form and for long fragments
+    return f;
 }
 
-static int mfma_k2_for(int dims);
-static int mfma_gen_fmt(const covgram_ctx* ctx, const HostKernel& hk, int lfam, const covgram_points* X, const covgram_points* Y, int maxk2, int* K2);
-static int mfma_family_of(const covgram_ctx* ctx, const HostKernel& hk, float* gamma);
-bool mfma_gen_eligible(const covgram_ctx* ctx, const HostKernel& hk, const covgram_points* X, const covgram_points* Y, int nrhs);
-// the generic profiles' symmetric form: same conditions on top of the generic matrix-core gate (hk: gamma = 1/l parameter block)
-bool mfma_gen_sym_eligible(const covgram_ctx* ctx, const HostKernel& hk, const covgram_points* X, const covgram_points* Y, int nrhs) {
-    if (ctx->mfma_sym == 0 || nrhs != 1 || X->dptr != Y->dptr || X->n != Y->n) return false;
-    if (!mfma_gen_eligible(ctx, hk, X, Y, nrhs)) return false;
-    const int k2 = mfma_k2_for(X->d + (hk.k.trait == COVGRAM_ISOTROPIC ? 1 : 0));
-    if (k2 < 0) return false;
-    float gam_unused;
-    const int lfam = mfma_family_of(ctx, hk, &gam_unused);
-    if (lfam == FAM_SUM_ISO && k2 > 8) return false;                              // no one-pass symmetric instance: one (symmetric) MVM per term instead
-    const int tpp = mfma_sym_tiles_per_panel(lfam, k2);                           // (an upper bound of the slab whichever form runs: fewer tiles per panel = more panels)
-    const int64_t ntile = (X->n + 31) / 32, panels = (ntile + tpp - 1) / tpp;
-    if ((size_t)panels * (size_t)(panels * 32 * tpp) * sizeof(float) > ((size_t)16 << 30)) return false;
-    const bool heavy = hk.tu_family == COVGRAM_MATERNP || hk.tu_family == COVGRAM_RQ || hk.tu_family >= COVGRAM_NFAMILY;   // profile costs several exponentials
-    // (heavy profiles at d > 4: the all-entries kernel's cost grows with the fragment length, the symmetric kernel's floor does not — tools/sym_threshold_sweep.py,
-    //  MaternP(2) d = 8: n = 10000 60.0 / 59.8 us, 12000 77.4 / 66.7)
-    return ctx->mfma_sym == 1 || X->n >= (heavy ? (X->d > 4 ? 10000 : MFMA_SYM_MIN_N_HEAVY) : MFMA_SYM_MIN_N_EQ_WIDE);
+// column chunk of the symmetric kernels: a multiple of the 4-tile stage; ~8 rounds of the resident workgroups (2 per CU) over the triangle,
+// ~4 for one rank's share of a multi-GPU MVM (the work list puts the cut, shorter chunks last, so the last round balances); >= 64 tiles —
+// shorter chunks do not amortise a workgroup's prologue (rows, row weights, first stage) —, >= 128 for a rank's share (tools/sym_tchunk_sweep.py,
+// tools/sym_shard_probe.py: rank r of 8 at C2 size 170-185 us with 128-tile chunks, 183-201 with 64).
+// (4-wave workgroups: three per CU.  The two-row-tile kernels — heavier prologue: two sets of row fragments and weights per wave — take ~5 rounds:
+//  tools/sym_rounds_ab.py, interleaved, n = 131072: EQ d = 3 980 / 962 / 958 us at 8 / 5 / 4 rounds, d = 8 1154 / 1131 / 1117; n = 262144 level)
+static int64_t sym_tchunk(const covgram_ctx* ctx, const SymForm& f, int64_t ntile, int pstride) {
+    const int64_t panels = sym_panels(ntile, f.tpp);
+    const int64_t tileops = (panels * ntile / 2 + panels * 4) / pstride;         // (panel, tile) visits
+    const bool two_row = f.rt == 2;
+    const int64_t target = ctx->target_wgs > 0 ? ctx->target_wgs : (int64_t)ctx->num_cus * ((f.tpp == 4 || two_row) ? 3 : 2) * (pstride > 1 ? 4 : (two_row ? 5 : 8));
+    const int64_t tchunk = ctx->jsplit > 0 ? (ntile + ctx->jsplit - 1) / ctx->jsplit : (tileops + target - 1) / target;
+    return std::max<int64_t>(pstride > 1 ? 128 : 64, std::min<int64_t>(((tchunk + 3) / 4) * 4, 1024));
+}
+
+// the device copy of the work list (mfma_plan.hpp: sym_worklist), cached in the context by its key
+static int sym_worklist_cached(covgram_ctx* ctx, int64_t ntile, int tpp, int64_t tchunk, int pfirst, int pstride) {
+    CG_REQUIRE(sym_list_in_range(ntile, tpp, tchunk, pfirst, pstride), COVGRAM_EUNSUPPORTED, "dense_mfma_sym: work list out of range");
+    const int64_t key[4] = {ntile, tchunk * 16 + tpp, pfirst, pstride};
+    if (ctx->sym_map != nullptr && memcmp(ctx->sym_key, key, sizeof(key)) == 0) return COVGRAM_OK;
+    const std::vector<int32_t> list = sym_worklist(ntile, tpp, tchunk, pfirst, pstride);
+    if (list.size() > ctx->sym_map_cap) {
+        if (ctx->sym_map) { CG_CHECK_HIP(hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->sym_map); ctx->sym_map = nullptr; }
+        ctx->sym_map_cap = std::max<size_t>(list.size(), 4096);
+        CG_CHECK_HIP(hipMalloc((void**)&ctx->sym_map, ctx->sym_map_cap * sizeof(int32_t)));
+    } else if (ctx->sym_map) {
+        CG_CHECK_HIP(hipStreamSynchronize(ctx->stream));       // a launch in flight may still read the old list
+    }
+    if (!list.empty()) CG_CHECK_HIP(hipMemcpy(ctx->sym_map, list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    memcpy(ctx->sym_key, key, sizeof(key));
+    ctx->sym_map_len = list.size();
+    return COVGRAM_OK;
+}
+
+// the EQ form's instance of (split, K2): FAM = FAM_EQFAST / FAM_EQFAST_H; false: not compiled
+template <int FAM, int K2>
+static bool eq_sym_launch(const covgram_ctx* ctx, const MfmaArgs& a, const SymForm& f) {
+    constexpr bool H = FAM == FAM_EQFAST_H;
+    const KParams<float> kp{};
+    if constexpr (K2 <= MFMA_NARROW_MAXK2) {
+        if (f.rt == 2) {   // 8-tile stages at K2 <= 2 (option "mfma_sym_st" = 4: four)
+            if constexpr (K2 <= 2) { if (ctx->mfma_sym_st != 4) { mfma_sym_launch<dense_mfma_sym2_kernel<FAM, K2, 8>, 256>(a, kp); return true; } }
+            mfma_sym_launch<dense_mfma_sym2_kernel<FAM, K2, 4>, 256>(a, kp);
+        } else mfma_sym_launch<dense_mfma_sym_kernel<FAM, K2>, 512>(a, kp);
+    } else if constexpr (H && (K2 == 6 || K2 == 8)) {
+        if (f.staged_wide) mfma_sym_launch<dense_mfma_sym_kernel<FAM, K2>, 512>(a, kp);
+        else mfma_sym_launch<dense_mfma_sym_wide_kernel<FAM, K2>, 256>(a, kp);
+    } else if constexpr (!H && K2 == 6) mfma_sym_launch<dense_mfma_sym_kernel<FAM, K2>, 512>(a, kp);
+    else if constexpr (!H) mfma_sym_launch<dense_mfma_sym_wide_kernel<FAM, K2>, 256>(a, kp);
+    else return false;
+    return true;
 }
 
 // y <- alpha * scale * G_part a + beta * y for the symmetric Gramian of ONE point set and one right-hand side, where G_part
 // holds the entries (i, j), (j, i) whose upper-triangle tile lies in the panels pfirst, pfirst + pstride, ... — all of G
 // for (0, 1); the partial products of the ranks (g, P), g < P, add up to G a (covgram_mvm_sym_partial).
+// kgen == nullptr: the EQ form (hk is the dense EQ parameter block); else the generic form for kernel *kgen.  The two differ in where the
+// fragments come from, in the EF pointer and in the launcher.
 int mvm_eq_mfma_sym(covgram_ctx* ctx, const HostKernel& hk, const covgram_points* X, const float* a, float* y, double alpha, double beta,
                     int pfirst, int pstride, const covgram_kernel* kgen) {
-    // kgen == nullptr: the EQ form (hk is the dense EQ parameter block); else the generic form for kernel *kgen
     const bool fast = kgen == nullptr;
     HostKernel hkg;
     if (!fast) {   // gamma = 1/l and the profile sees s / l^2 — EQ / MaternP: the folded block (dense_mfma.hpp: mfma_folded)
@@ -906,349 +747,71 @@ int mvm_eq_mfma_sym(covgram_ctx* ctx, const HostKernel& hk, const covgram_points
         if (rcg) return rcg;
     }
     const HostKernel& hku = fast ? hk : hkg;
-    const bool iso = hku.k.trait == COVGRAM_ISOTROPIC;
-    float gamg = 0.0f;
-    const int lfam = fast ? COVGRAM_EQ : mfma_family_of(ctx, hku, &gamg);
-    if (!fast) ctx->last_sum_fused = lfam == FAM_SUM_ISO ? 1 : 0;
-    const int64_t n = X->n;
-    const int d = X->d;
-    // EQ form: the fp16 two-way split inside its gate, as the general kernel (mvm_eq_mfma, "Which split"); every rank of a multi-GPU call sees the same
-    // cloud and lengthscale, hence the same split and the same panel size
-    const double g2r2 = 1.4426950408889634074 / (hk.k.lengthscale * hk.k.lengthscale) * gate_radius2(X, X);
-    const int fmt = (fast && ctx->mfma_f16 != 0 && g2r2 <= (ctx->mfma_f16 == 2 ? mfma_gate_of(ctx) : mfma_f16_gate_of(ctx))) ? 1 : 0;
-    if (fast) ctx->last_mfma_f16 = fmt;
-    int K2 = fast ? (fmt ? eq_k2_for(2 * ((d + 3) / 4)) : eq_k2_for(d)) : mfma_k2_for(d + (iso ? 1 : 0));
-    // generic form: the fp16 split where the staged (narrow) symmetric kernel of the family has the instance (dense_mfma.hpp: mfma_sym_narrow_maxk2)
-    int gfmt = 0;
-    if (!fast) {
-        int k2h = 0;
-        gfmt = mfma_gen_fmt(ctx, hku, lfam, X, X, lfam == FAM_SUM_ISO ? 2 : 8, &k2h);   // (the Sum: its staged kernel only)
-        if (gfmt) K2 = k2h;
-        ctx->last_mfma_f16 = gfmt;
-    }
-    CG_REQUIRE(K2 > 0, COVGRAM_EUNSUPPORTED, "dense_mfma_sym: d = %d has no matrix-core instance", d);
+    const int64_t n = X->n, ntile = (n + 31) / 32;
+    // 1. kernel and split
+    const SymForm f = sym_form(ctx, hku, X, fast);
+    ctx->last_mfma_f16 = f.fmt;
+    CG_REQUIRE(f.K2 > 0, COVGRAM_EUNSUPPORTED, "dense_mfma_sym: d = %d has no matrix-core instance", X->d);
+    MfmaArgs ma{};
+    ma.X = (const float*)X->dptr; ma.n = n; ma.d = X->d; ma.ntile = ntile; ma.ldy = n; ma.nrhs = 1; ma.alpha = 1.0f; ma.beta = 0.0f; ma.final_store = 0;
+    ma.K2 = f.K2; ma.RT = 1; ma.NR = 1; ma.hk = &hku; ma.stream = ctx->stream; ma.Cn = (const float*)X->center;
+    ma.sym = 1; ma.pfirst = pfirst; ma.pstride = pstride; ma.fmt = f.fmt; ma.sym_rt = f.rt;
     // slab row stride: rows of R / S one panel apart must not sit a power of two apart (n = 49152: 192 KB stride, every panel's
     // stores to the same columns hit the same memory channel: 1.46 ms instead of 0.25); + 4.25 KB staggers them
-    // row tiles per panel: 8 waves x 1 tile, 6 for the heavy profiles' 3-waves-per-SIMD form, or 4 x 1 for long fragments (dense_mfma.hpp)
-    // generic form at one or two MFMAs per tile: two row tiles per wave as the EQ form (dense_mfma_sym2.hpp; option "mfma_sym_rt" = 1: the one-row-tile panels)
-    const int gen_rt = (!fast && ctx->mfma_sym_rt != 1 && K2 <= 2 && mfma_sym2_family(lfam)) ? 2 : 1;
-    // Six MFMAs per tile (d = 17 .. 24 with the fp16 split, 11 .. 12 with bf16): the STAGED 8-wave kernel (four column tiles per stage and barrier, one
-    // tile at a time in registers) instead of the one-tile-per-stage 4-wave kernel — round 5, tools/wide_staged_ab.py: n = 131072, d = 24 2.19 -> 1.89 ms,
-    // d = 20 2.16 -> 1.82.  Eight MFMAs per tile need 169 registers there (two waves per SIMD): 2.55 -> 2.60 ms, so they keep the 4-wave kernel
-    // (option "mfma_sym_st" = 16 forces the staged form for measurements).
-    const bool staged_wide = fast && (K2 == 6 || (K2 == 8 && fmt == 1 && ctx->mfma_sym_st == 16));
-    const int tpp = fast ? ((K2 > MFMA_NARROW_MAXK2 && !staged_wide) ? 4 : 8) : mfma_sym_tiles_per_panel(lfam, K2, gen_rt);
-    const int64_t ntile = (n + 31) / 32, panels = (ntile + tpp - 1) / tpp, npad = panels * 32 * tpp + 1088;
-    const float g = (float)(sqrt(1.4426950408889634074) / hk.k.lengthscale);
-    const float* Cn = (const float*)X->center;
+    ma.npad = sym_panels(ntile, f.tpp) * 32 * f.tpp + 1088;
+    // 2. fragments and weights
     int rc;
-    const float* W;
-    const uint4* PBu;
-    const float* EF = nullptr;
     if (fast) {
         // the fragments AND the fraction factors e_j are cached in the points handle; the kernel forms a_j e_j itself, so a
         // steady-state MVM launches no pack kernel
-        rc = eq_fragments(ctx, X, K2, g, Cn, &PBu, &EF, fmt);
-        if (rc) return rc;
-        W = a;
-    } else {                                                       // generic fragments (norm pseudo-coordinate) + W = a, packed per MVM
-        void* P;
-        rc = ws_reserve(ctx, 0, (size_t)ntile * ((size_t)K2 * 64 * sizeof(uint4) + 32 * sizeof(float)), &P);
-        if (rc) return rc;
-        uint4* PB = (uint4*)P;
-        float* Wg = (float*)(PB + ntile * K2 * 64);
-        const int64_t pe = ntile * K2 * 64;
-        hipLaunchKernelGGL(mfma_pack_gen_kernel, dim3((unsigned)((pe + 255) / 256)), dim3(256), 0, ctx->stream, (const float*)X->dptr, n, d, a,
-                           n, 1, 0, PB, Wg, K2, 1, gamg, iso ? 1 : 0, Cn, gfmt);
-        PBu = PB; W = Wg;
-    }
-    // column chunk: a multiple of the 4-tile stage; ~8 rounds of the resident workgroups (2 per CU) over the triangle
-    const int64_t lpanels = panels > pfirst ? (panels - pfirst + pstride - 1) / pstride : 0;   // this call's panels
-    const int64_t tileops = (panels * ntile / 2 + panels * 4) / pstride;         // (panel, tile) visits
-    // ~8 rounds of the resident workgroups, ~4 for one rank's share of a multi-GPU MVM (the list below puts the cut, shorter
-    // chunks last, so the last round balances); >= 64 tiles — shorter chunks do not amortise a workgroup's prologue (rows, row
-    // weights, first stage) —, >= 128 for a rank's share (tools/sym_tchunk_sweep.py, tools/sym_shard_probe.py: rank r of 8 at
-    // C2 size 170-185 us with 128-tile chunks, 183-201 with 64)
-    const bool rt2_plan = fast && K2 <= (ctx->mfma_sym_rt == 2 ? MFMA_NARROW_MAXK2 : 2) && ctx->mfma_sym_rt != 1;     // 4-wave workgroups: three per CU
-    // (4-wave workgroups: three per CU.  The two-row-tile kernels — heavier prologue: two sets of row fragments and weights per wave — take ~5 rounds:
-    //  tools/sym_rounds_ab.py, interleaved, n = 131072: EQ d = 3 980 / 962 / 958 us at 8 / 5 / 4 rounds, d = 8 1154 / 1131 / 1117; n = 262144 level)
-    const bool two_row = rt2_plan || gen_rt == 2;
-    int64_t target = ctx->target_wgs > 0 ? ctx->target_wgs : (int64_t)ctx->num_cus * ((tpp == 4 || two_row) ? 3 : 2) * (pstride > 1 ? 4 : (two_row ? 5 : 8));
-    int64_t tchunk = ctx->jsplit > 0 ? (ntile + ctx->jsplit - 1) / ctx->jsplit : (tileops + target - 1) / target;
-    tchunk = std::max<int64_t>(pstride > 1 ? 128 : 64, std::min<int64_t>(((tchunk + 3) / 4) * 4, 1024));
-    const int64_t maxc = (ntile + tchunk - 1) / tchunk;
-    void *Rp, *Sp;
-    rc = ws_reserve(ctx, 1, (size_t)maxc * npad * sizeof(float), &Rp); if (rc) return rc;
-    rc = ws_reserve(ctx, 4, (size_t)std::max<int64_t>(lpanels, 1) * npad * sizeof(float), &Sp); if (rc) return rc;
-    const double alpha_eff = alpha * hku.kp.scale;
-    // the (local panel, absolute chunk) pairs that exist, chunk-major (the workgroups in flight share a chunk's fragments in
-    // L2); cached in the context by its key
-    CG_REQUIRE(maxc <= 4096 && lpanels < ((int64_t)1 << 19), COVGRAM_EUNSUPPORTED, "dense_mfma_sym: work list out of range");
-    const int64_t key[4] = {ntile, tchunk * 16 + tpp, pfirst, pstride};
-    if (ctx->sym_map == nullptr || memcmp(ctx->sym_key, key, sizeof(key)) != 0) {
-        // whole chunks first (chunk-major), then the cut ones (a panel's first chunk, the last chunk of the row): the short
-        // workgroups fill the last round instead of leaving most of the chip idle behind a few long ones
-        std::vector<int32_t> list, tail;
-        for (int64_t c = 0; c < maxc; ++c)
-            for (int64_t lp = 0; lp < lpanels; ++lp) {
-                const int64_t p8 = tpp * ((int64_t)pfirst + (int64_t)pstride * lp);   // the panel's first tile
-                if (p8 >= (c + 1) * tchunk) break;                 // panels are ascending: the rest start right of this chunk
-                const int64_t t0 = std::max(c * tchunk, p8), t1 = std::min((c + 1) * tchunk, ntile);
-                if (t0 >= ntile) continue;
-                ((t1 - t0 == tchunk) ? list : tail).push_back((int32_t)((lp << 12) | c));
-            }
-        std::sort(tail.begin(), tail.end(), [&](int32_t u, int32_t v) {   // longer cut chunks first
-            auto len = [&](int32_t w) {
-                const int64_t lp = w >> 12, c = w & 4095, p8 = tpp * ((int64_t)pfirst + (int64_t)pstride * lp);
-                return std::min((c + 1) * tchunk, ntile) - std::max(c * tchunk, p8);
-            };
-            const int64_t lu = len(u), lv = len(v);
-            return lu != lv ? lu > lv : u < v;
-        });
-        list.insert(list.end(), tail.begin(), tail.end());
-        if (list.size() > ctx->sym_map_cap) {
-            if (ctx->sym_map) { CG_CHECK_HIP(hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->sym_map); ctx->sym_map = nullptr; }
-            ctx->sym_map_cap = std::max<size_t>(list.size(), 4096);
-            CG_CHECK_HIP(hipMalloc((void**)&ctx->sym_map, ctx->sym_map_cap * sizeof(int32_t)));
-        } else if (ctx->sym_map) {
-            CG_CHECK_HIP(hipStreamSynchronize(ctx->stream));       // a launch in flight may still read the old list
-        }
-        if (!list.empty()) CG_CHECK_HIP(hipMemcpy(ctx->sym_map, list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        memcpy(ctx->sym_key, key, sizeof(key));
-        ctx->sym_map_len = list.size();
-    }
-    const dim3 grid((unsigned)std::max<size_t>(ctx->sym_map_len, 1));
-    {
-    TimerScope tm(ctx);
-#define CG_SYM_CASE(K) case K: hipLaunchKernelGGL((dense_mfma_sym_kernel<FAM_EQFAST, K>), grid, dim3(512), 0, ctx->stream, (const float*)X->dptr, n, d, \
-                                                  PBu, W, ntile, (float*)Rp, (float*)Sp, npad, (int)tchunk, g, Cn, pfirst, pstride, ctx->sym_map, \
-                                                  KParams<float>{}, EF); break;
-#define CG_SYMW_CASE(K) case K: hipLaunchKernelGGL((dense_mfma_sym_wide_kernel<FAM_EQFAST, K>), grid, dim3(256), 0, ctx->stream, (const float*)X->dptr, n, d, \
-                                                   PBu, W, ntile, (float*)Rp, (float*)Sp, npad, (int)tchunk, g, Cn, pfirst, pstride, ctx->sym_map, \
-                                                   KParams<float>{}, EF); break;
-#define CG_SYMH_CASE(K) case K: hipLaunchKernelGGL((dense_mfma_sym_kernel<FAM_EQFAST_H, K>), grid, dim3(512), 0, ctx->stream, (const float*)X->dptr, n, d, \
-                                                   PBu, W, ntile, (float*)Rp, (float*)Sp, npad, (int)tchunk, g, Cn, pfirst, pstride, ctx->sym_map, \
-                                                   KParams<float>{}, EF); break;
-#define CG_SYMWH_CASE(K) case K: hipLaunchKernelGGL((dense_mfma_sym_wide_kernel<FAM_EQFAST_H, K>), grid, dim3(256), 0, ctx->stream, (const float*)X->dptr, n, d, \
-                                                    PBu, W, ntile, (float*)Rp, (float*)Sp, npad, (int)tchunk, g, Cn, pfirst, pstride, ctx->sym_map, \
-                                                    KParams<float>{}, EF); break;
-    ctx->last_mfma_instance = fast ? -(int64_t)(K2 * 10 + fmt) : 0;
-    // the EQ forms up to four MFMAs per tile: two row tiles per wave, 4-wave workgroups (dense_mfma_sym2.hpp) — option "mfma_sym_rt": -1 / 2 = that, 1 = the
-    // 8-wave one-row-tile kernel
-    const bool rt2 = fast && K2 <= (ctx->mfma_sym_rt == 2 ? MFMA_NARROW_MAXK2 : 2) && ctx->mfma_sym_rt != 1;
-    ctx->last_mfma_sym_rt = rt2 ? 2 : 1;
-#define CG_SYM2_CASE(F, K) case K: if (K <= 2 && ctx->mfma_sym_st != 4) hipLaunchKernelGGL((dense_mfma_sym2_kernel<F, K, (K <= 2 ? 8 : 4)>), grid, dim3(256), 0, ctx->stream, (const float*)X->dptr, n, d, \
-                                                      PBu, W, ntile, (float*)Rp, (float*)Sp, npad, (int)tchunk, g, Cn, pfirst, pstride, ctx->sym_map, KParams<float>{}, EF); \
-                                   else hipLaunchKernelGGL((dense_mfma_sym2_kernel<F, K, 4>), grid, dim3(256), 0, ctx->stream, (const float*)X->dptr, n, d, \
-                                                      PBu, W, ntile, (float*)Rp, (float*)Sp, npad, (int)tchunk, g, Cn, pfirst, pstride, ctx->sym_map, KParams<float>{}, EF); break;
-    if (rt2 && fmt) {
-        switch (K2) { CG_SYM2_CASE(FAM_EQFAST_H, 1) CG_SYM2_CASE(FAM_EQFAST_H, 2) CG_SYM2_CASE(FAM_EQFAST_H, 3) CG_SYM2_CASE(FAM_EQFAST_H, 4) default: break; }
-    } else if (rt2) {
-        switch (K2) { CG_SYM2_CASE(FAM_EQFAST, 1) CG_SYM2_CASE(FAM_EQFAST, 2) CG_SYM2_CASE(FAM_EQFAST, 3) CG_SYM2_CASE(FAM_EQFAST, 4) default: break; }
-    } else
-#undef CG_SYM2_CASE
-    if (fast && fmt) {
-        switch (K2) {
-            CG_SYMH_CASE(1) CG_SYMH_CASE(2) CG_SYMH_CASE(3) CG_SYMH_CASE(4)
-#define CG_SYMSW_CASE(K) case K: if (staged_wide) hipLaunchKernelGGL((dense_mfma_sym_kernel<FAM_EQFAST_H, K>), grid, dim3(512), 0, ctx->stream, (const float*)X->dptr, n, d, \
-                                                   PBu, W, ntile, (float*)Rp, (float*)Sp, npad, (int)tchunk, g, Cn, pfirst, pstride, ctx->sym_map, KParams<float>{}, EF); \
-                               else hipLaunchKernelGGL((dense_mfma_sym_wide_kernel<FAM_EQFAST_H, K>), grid, dim3(256), 0, ctx->stream, (const float*)X->dptr, n, d, \
-                                                   PBu, W, ntile, (float*)Rp, (float*)Sp, npad, (int)tchunk, g, Cn, pfirst, pstride, ctx->sym_map, KParams<float>{}, EF); break;
-            CG_SYMSW_CASE(6) CG_SYMSW_CASE(8)
-#undef CG_SYMSW_CASE
-            default: set_error("dense_mfma_sym: K2 = %d not compiled for the fp16 split", K2); return COVGRAM_EUNSUPPORTED;
-        }
-    } else if (fast) {
-        switch (K2) {
-            CG_SYM_CASE(1) CG_SYM_CASE(2) CG_SYM_CASE(3) CG_SYM_CASE(4)
-            case 6: hipLaunchKernelGGL((dense_mfma_sym_kernel<FAM_EQFAST, 6>), grid, dim3(512), 0, ctx->stream, (const float*)X->dptr, n, d, PBu, W, ntile, (float*)Rp,
-                                       (float*)Sp, npad, (int)tchunk, g, Cn, pfirst, pstride, ctx->sym_map, KParams<float>{}, EF); break;
-            CG_SYMW_CASE(8) CG_SYMW_CASE(12) CG_SYMW_CASE(16)
-            default: set_error("dense_mfma_sym: K2 = %d not compiled", K2); return COVGRAM_EUNSUPPORTED;
-        }
+        ma.g = (float)(sqrt(LOG2E) / hk.k.lengthscale);
+        rc = eq_fragments(ctx, X, f.K2, ma.g, ma.Cn, &ma.PB, &ma.EF, f.fmt);
+        ma.W = a;
     } else {
-        MfmaArgs ma;
-        ma.X = (const float*)X->dptr; ma.n = n; ma.d = d; ma.PB = PBu; ma.W = W; ma.ntile = ntile; ma.out = nullptr; ma.npad = npad; ma.ldy = n;
-        ma.nrhs = 1; ma.tchunk = tchunk; ma.alpha = 1.0f; ma.beta = 0.0f; ma.final_store = 0; ma.K2 = K2; ma.RT = 1; ma.NR = 1;
-        ma.hk = &hku; ma.stream = ctx->stream; ma.grid = grid; ma.Cn = Cn;
-        ma.sym = 1; ma.R = (float*)Rp; ma.S = (float*)Sp; ma.wgmap = ctx->sym_map; ma.pfirst = pfirst; ma.pstride = pstride; ma.fmt = gfmt; ma.sym_rt = gen_rt;
-        ctx->last_mfma_sym_rt = gen_rt;
-        mfma_launch_fn launch = mfma_launcher(lfam);
-        CG_REQUIRE(launch != nullptr, COVGRAM_EUNSUPPORTED, "dense_mfma_sym: family %d has no matrix-core path", lfam);
-        rc = launch(ma, false);
-        if (rc) return rc;
+        float* Wg = nullptr;
+        rc = gen_fragments(ctx, X, a, n, 1, 1, f.K2, f.gam, hku.k.trait == COVGRAM_ISOTROPIC, f.fmt, 0, &ma.PB, &Wg);
+        ma.W = Wg;
     }
-#undef CG_SYM_CASE
-#undef CG_SYMW_CASE
-#undef CG_SYMH_CASE
-#undef CG_SYMWH_CASE
+    if (rc) return rc;
+    // 3. column chunks, the row-sum slab R (one row per chunk) and the column-sum slab S (one row per local panel)
+    ma.tchunk = sym_tchunk(ctx, f, ntile, pstride);
+    void *Rp, *Sp;
+    rc = ws_reserve(ctx, 1, (size_t)sym_chunks(ntile, ma.tchunk) * ma.npad * sizeof(float), &Rp); if (rc) return rc;
+    rc = ws_reserve(ctx, 4, (size_t)std::max<int64_t>(sym_local_panels(ntile, f.tpp, pfirst, pstride), 1) * ma.npad * sizeof(float), &Sp); if (rc) return rc;
+    ma.R = (float*)Rp; ma.S = (float*)Sp;
+    // 4. work list
+    rc = sym_worklist_cached(ctx, ntile, f.tpp, ma.tchunk, pfirst, pstride);
+    if (rc) return rc;
+    ma.wgmap = ctx->sym_map;
+    ma.grid = dim3((unsigned)std::max<size_t>(ctx->sym_map_len, 1));
+    // 5. launch
+    {
+        TimerScope tm(ctx);
+        ctx->last_mfma_instance = fast ? -(int64_t)(f.K2 * 10 + f.fmt) : 0;
+        ctx->last_mfma_sym_rt = f.rt;
+        if (fast) {
+            bool compiled = false;
+            mfma_for_k2(f.K2, [&](auto k) {
+                constexpr int K = decltype(k)::value;
+                compiled = f.fmt ? eq_sym_launch<FAM_EQFAST_H, K>(ctx, ma, f) : eq_sym_launch<FAM_EQFAST, K>(ctx, ma, f);
+            });
+            CG_REQUIRE(compiled, COVGRAM_EUNSUPPORTED, f.fmt ? "dense_mfma_sym: K2 = %d not compiled for the fp16 split" : "dense_mfma_sym: K2 = %d not compiled", f.K2);
+        } else {
+            mfma_launch_fn launch = mfma_launcher(f.lfam);
+            CG_REQUIRE(launch != nullptr, COVGRAM_EUNSUPPORTED, "dense_mfma_sym: family %d has no matrix-core path", f.lfam);
+            rc = launch(ma, false);
+            if (rc) return rc;
+        }
     }
+    // 6. reduce
     hipLaunchKernelGGL(dense_mfma_sym_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(1024), 0, ctx->stream, n, (const float*)Rp,
-                       (const float*)Sp, npad, ntile, (int)tchunk, EF, y, (float)alpha_eff, (float)beta, pfirst, pstride, tpp);
+                       (const float*)Sp, ma.npad, ntile, (int)ma.tchunk, ma.EF, y, (float)(alpha * hku.kp.scale), (float)beta, pfirst, pstride, f.tpp);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("dense_mfma_sym launch failed: %s", hipGetErrorString(e)); return COVGRAM_EHIP; }
     return COVGRAM_OK;
 }
 
-// ------------------------------------------------------------------------------------------------------------------------
-// generic profiles / several right-hand sides (dense_mfma.hpp)
-// ------------------------------------------------------------------------------------------------------------------------
-#define CG_DECL(n) int launch_mfma_family_##n(const MfmaArgs&, bool query);
-CG_DECL(0) CG_DECL(2) CG_DECL(4) CG_DECL(5) CG_DECL(6) CG_DECL(7) CG_DECL(8) CG_DECL(11) CG_DECL(12) CG_DECL(13)
-#undef CG_DECL
-
-mfma_launch_fn mfma_launcher(int family) {
-    switch (family) {
-        case COVGRAM_EQ: return launch_mfma_family_0;
-        case COVGRAM_RQ: return launch_mfma_family_2;
-        case COVGRAM_CAUCHY: return launch_mfma_family_4;
-        case COVGRAM_IMQ: return launch_mfma_family_5;
-        case COVGRAM_MATERNP: return launch_mfma_family_6;
-        case COVGRAM_DOT: return launch_mfma_family_7;
-        case COVGRAM_EXPDOT: return launch_mfma_family_8;
-        case FAM_EXPR_ISO: return launch_mfma_family_11;          // Sum / Product / Power composites of the profiles above
-        case FAM_EXPR_DOT: return launch_mfma_family_12;
-        case FAM_SUM_ISO: return launch_mfma_family_13;           // a Sum of 2-3 single-profile isotropic terms in one pass (common.hpp: SumParams)
-        default: return nullptr;
-    }
-}
-
-// The generic kernels' split of the coordinates (round 5): the fp16 two-way split (dense_mfma.hpp: gen_row_fragments) for the isotropic single
-// profiles and one-pass Sums while (a) its instance exists — d + 2 positions in at most `maxk2` MFMAs of four —, and (b) the cloud lies inside
-// MFMA_F16_GATE / MFMA_GATE of the generic radius gate (gate_frac: the quantity mfma_gen_eligible admits up to 1), the EQ kernel's rule
-// (option "mfma_f16": 0 never, 2 wherever the matrix-core gate admits the cloud).  Returns the format and sets the MFMAs per tile.
-static double mfma_gen_gate_frac(const HostKernel& hk, const covgram_points* X, const covgram_points* Y);
-static int mfma_gen_fmt(const covgram_ctx* ctx, const HostKernel& hk, int lfam, const covgram_points* X, const covgram_points* Y, int maxk2, int* K2) {
-    const bool iso = hk.k.trait == COVGRAM_ISOTROPIC;
-    const int d = X->d;
-    *K2 = mfma_k2_for(d + (iso ? 1 : 0));
-    if (ctx->mfma_f16 == 0 || !iso || lfam == FAM_EXPR_ISO || lfam == FAM_EXPR_DOT) return 0;
-    int k2h = (d + 2 + 3) / 4;                                   // d + 2 positions, four per MFMA; compiled: 1, 2, 3, 4, 6, 8 (d <= 30)
-    if (k2h == 5) k2h = 6; else if (k2h == 7) k2h = 8;
-    if (k2h > maxk2 || k2h > 8) return 0;
-    const double frac = mfma_gen_gate_frac(hk, X, Y);
-    if (!(frac <= 0.01 * (double)ctx->mfma_gate_pct * (ctx->mfma_f16 == 2 ? 1.0 : MFMA_F16_GATE / MFMA_GATE))) return 0;
-    *K2 = k2h;
-    return 1;
-}
-
-// The launcher family and coordinate pre-scale of a generic matrix-core MVM: a Sum of single-profile terms runs its one-pass form
-// (FAM_SUM_ISO: the pre-scale carries the first term's argument scale) unless option "sum_fused" = 0 keeps the composite interpreter.
-static int mfma_family_of(const covgram_ctx* ctx, const HostKernel& hk, float* gamma) {
-    if (ctx->sum_fused != 0 && sum_fusable(hk)) { *gamma = (float)make_sum_params(hk).gamma; return FAM_SUM_ISO; }
-    *gamma = (float)hk.kp.gamma;
-    return hk.tu_family;
-}
-// covgram_mvm: does this composite take the one-pass Sum kernels (instead of one MVM per term)?
-bool sum_fused_applies(const covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, int nrhs) {
-    if (ctx->sum_fused == 0 || k == nullptr || k->family != COVGRAM_COMPOSITE || X->dtype != COVGRAM_F32 || Y->n == 0) return false;
-    HostKernel hk;
-    if (make_host_kernel(k, COVGRAM_F32, false, &hk) != COVGRAM_OK) return false;
-    if (!sum_fusable(hk) || !mfma_gen_eligible(ctx, hk, X, Y, nrhs)) return false;
-    // gramian(k, x) at d >= 16: the one-pass symmetric kernel has no instance (K2 > 8), and one symmetric MVM per term evaluates half the pairs
-    // of the one-pass general kernel
-    const bool same = nrhs == 1 && ctx->mfma_sym != 0 && X->dptr == Y->dptr && X->n == Y->n && (ctx->mfma_sym == 1 || X->n >= (X->d > 4 ? 10000 : MFMA_SYM_MIN_N_HEAVY));
-    if (same && mfma_k2_for(X->d + 1) > 8) return false;
-    // Measured (d = 3, n = 131072; profiles/r05_sum_fused_ab.txt, r05_sum_general_ab.txt): what one pass shares is the matrix-core work, the weighted
-    // sums and the slabs — every term's transcendentals remain, and they are what the kernels are bound by.  Three terms: 4.07 against 4.83 ms for one
-    // symmetric MVM per term, 0.95 / 1.01 against 0.98 / 1.09 on a 16384-row shard.  Two terms: one MVM per term wins or ties on both forms (symmetric
-    // 3.05 against 3.32; shard, MaternP(2) + EQ: 0.62 against 0.71 — the EQ term costs 0.15 on its own kernel —, MaternP + MaternP 0.83 against 0.87,
-    // RQ + MaternP 0.79 against 0.78): the one-pass kernel's wave-uniform family switches and its one-tile loop cost more than the second pass saves.
-    // Option "sum_fused" = 1 takes the one-pass kernels wherever they exist (tests).
-    if (ctx->sum_fused == 1) return true;
-    return hk.nterms >= 3;
-}
-
-static int mfma_k2_for(int dims) {   // MFMAs per tile for `dims` (pseudo-)coordinates, from the compiled set
-    static const int ks[] = {1, 2, 3, 4, 6, 8, 12, 16};
-    const int need = (dims + 1) / 2;
-    for (int k : ks) if (k >= need) return k;
-    return -1;
-}
-
-// (radius-gate quantity of an ISOTROPIC generic matrix-core MVM) / (what mfma_gen_eligible admits): sensitivity x Power x g^2 R^2 over
-// 0.5 MFMA_GATE / log2(e), single profiles and composites alike; infinity where a profile has no matrix-core form
-static double mfma_gen_gate_frac(const HostKernel& hk, const covgram_points* X, const covgram_points* Y) {
-    const double limit = 0.5 * MFMA_GATE / 1.4426950408889634074;
-    auto sens_of = [](int fam, const KParams<double>& q) -> double {
-        switch (fam) {
-            case COVGRAM_EQ: case COVGRAM_RQ: return 0.5;
-            case COVGRAM_CAUCHY: return 1.0;
-            case COVGRAM_IMQ: return 0.5 / q.param;                      // param holds c^2
-            case COVGRAM_MATERNP: return q.p < 1 ? INFINITY : (fabs(q.mp_d1) > 0.5 ? fabs(q.mp_d1) : 0.5);
-            default: return INFINITY;
-        }
-    };
-    const double Pn = gate_radius2(X, Y);
-    if (!(Pn < 1e30)) return INFINITY;
-    if (hk.tu_family >= COVGRAM_NFAMILY) {
-        double worst = 0.0;
-        int fi = 0;
-        for (int t = 0; t < hk.nterms; ++t) {
-            double sum = 0.0;
-            for (int f = 0; f < hk.nfac[t]; ++f, ++fi) sum += sens_of(hk.ffam[fi], hk.fkp[fi]) * hk.fkp[fi].power * hk.fkp[fi].gamma2;
-            worst = std::max(worst, sum);
-        }
-        return worst * Pn / limit;
-    }
-    return sens_of(hk.tu_family, hk.kp) * hk.k.power * Pn / (hk.k.lengthscale * hk.k.lengthscale) / limit;
-}
-
-bool mfma_gen_eligible(const covgram_ctx* ctx, const HostKernel& hk, const covgram_points* X, const covgram_points* Y, int nrhs) {
-    if (ctx->dense_variant == 1 || X->dtype != COVGRAM_F32 || Y->n == 0) return false;
-    if (mfma_launcher(hk.tu_family) == nullptr) return false;
-    if (hk.tu_family == COVGRAM_MATERNP && hk.k.p < 1) return false;          // MaternP(0) = Exp: not differentiable in s at 0
-    // MaternP(p >= 1): up to round 4 the lane-per-row kernels (packed fp32 profile) beat the matrix-core ones (profile entry by entry) at d <= 4.
-    // Round 5: the profile arithmetic runs on register pairs (dense_mfma.hpp: mfma_profile_pairs) and the order is a compile-time constant of the
-    // instance: the general kernel is ahead at every d (16384 x 131072, d = 3: 428 against 543 us lane-per-row; d = 8: 631 against 862;
-    // profiles/r05_sum_fused_ab.txt), the symmetric one too (n = 131072, d = 3: 2.0 against 2.6 ms) — MaternP(p >= 1) no longer has an exception here.
-    const bool iso = hk.k.trait == COVGRAM_ISOTROPIC;
-    if (hk.tu_family >= COVGRAM_NFAMILY) {
-        // composite: every factor must be one of the smooth matrix-core profiles, and the relative errors of a product add up:
-        // the largest sum over a term's factors of (sensitivity x power / l^2) takes the place of the single profile's
-        if (mfma_k2_for(X->d + (iso ? 1 : 0)) < 0) return false;
-        double worst = 0.0;
-        int fi = 0;
-        for (int t = 0; t < hk.nterms; ++t) {
-            double sum = 0.0;
-            for (int f = 0; f < hk.nfac[t]; ++f, ++fi) {
-                const KParams<double>& q = hk.fkp[fi];
-                double sens;
-                switch (hk.ffam[fi]) {
-                    case COVGRAM_EQ: case COVGRAM_RQ: sens = 0.5; break;
-                    case COVGRAM_CAUCHY: sens = 1.0; break;
-                    case COVGRAM_IMQ: sens = 0.5 / q.param; break;                 // param holds c^2
-                    case COVGRAM_MATERNP: if (q.p < 1) return false; sens = fabs(q.mp_d1) > 0.5 ? fabs(q.mp_d1) : 0.5; break;
-                    case COVGRAM_DOT: case COVGRAM_EXPDOT: sens = 0.0; break;
-                    default: return false;                                     // Exp, gammaExp, Matern(nu), asin: direct differences only
-                }
-                sum += sens * q.power * q.gamma2;
-            }
-            worst = std::max(worst, sum);
-        }
-        if (ctx->dense_variant == 2) return true;
-        if (!iso) return sqrt(X->max_norm2) * sqrt(Y->max_norm2) < 1e30;
-        const double Pn = gate_radius2(X, Y);                                  // natural units: every factor has its own 1 / l^2
-        return worst * Pn <= 0.5 * mfma_gate_of(ctx) / 1.4426950408889634074;
-    }
-    if (mfma_k2_for(X->d + (iso ? 1 : 0)) < 0) return false;
-    if (ctx->dense_variant == 2) return true;
-    const double P = (iso ? gate_radius2(X, Y) : sqrt(X->max_norm2) * sqrt(Y->max_norm2)) /
-                     (hk.k.lengthscale * hk.k.lengthscale);
-    if (!(P < 1e30)) return false;
-    if (!iso) return true;                                                     // x.y itself: no cancellation to gate
-    // relative sensitivity of the profile to an absolute error in s (natural units): |phi'/phi| at its maximum
-    double sens = 1.0;
-    switch (hk.tu_family) {
-        case COVGRAM_EQ: case COVGRAM_RQ: sens = 0.5; break;
-        case COVGRAM_CAUCHY: sens = 1.0; break;
-        case COVGRAM_IMQ: sens = 0.5 / (hk.k.param * hk.k.param); break;   // 1/sqrt(s + c^2) at s = 0 (s already / l^2)
-        case COVGRAM_MATERNP: sens = fabs(hk.kp.mp_d1) > 0.5 ? fabs(hk.kp.mp_d1) : 0.5; break;
-        default: break;
-    }
-    return sens * hk.k.power * P <= 0.5 * mfma_gate_of(ctx) / 1.4426950408889634074;   // the EQ gate in natural units
-}
-
+// ---- generic profiles / several right-hand sides (dense_mfma.hpp) --------------------
 // y[:, 0..nrhs) <- alpha * scale * G a + beta * y (device pointers, column-major with lda / ldy)
 int mvm_mfma_gen(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, const float* a, int64_t lda,
                  float* y, int64_t ldy, int32_t nrhs, double alpha, double beta) {
@@ -1257,108 +820,78 @@ int mvm_mfma_gen(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points
     int rc = make_host_kernel(k, COVGRAM_F32, !(k->family == COVGRAM_EQ || k->family == COVGRAM_MATERNP), &hk);
     if (rc) return rc;
     const int64_t n = X->n, m = Y->n;
-    const int d = X->d;
     const bool iso = hk.k.trait == COVGRAM_ISOTROPIC;
     const int64_t ntile = (m + 31) / 32;
     float gam;
     const int lfam = mfma_family_of(ctx, hk, &gam);
-    int K2bf = 0;
-    const int gfmt_all = mfma_gen_fmt(ctx, hk, lfam, X, Y, 8, &K2bf);   // the VALU forms (up to four right-hand sides); the many-column GEMM form keeps bf16
-    const int K2m = mfma_k2_for(d + (iso ? 1 : 0));                      // ... with this many MFMAs per tile
-    int K2 = K2m;
+    int K2h = 0;
+    const int gfmt = mfma_gen_fmt(ctx, hk, lfam, X, Y, 8, &K2h);        // the VALU forms (up to four right-hand sides): their split and MFMAs per tile
+    const int K2m = mfma_k2_for(X->d + (iso ? 1 : 0));                   // the many-column GEMM form keeps bf16, with this many MFMAs per tile
     ctx->last_sum_fused = lfam == FAM_SUM_ISO ? 1 : 0;
     mfma_launch_fn launch = mfma_launcher(lfam);
     const double alpha_eff = alpha * hk.kp.scale;
+    MfmaArgs ma{};
+    ma.X = (const float*)X->dptr; ma.n = n; ma.d = X->d; ma.ntile = ntile; ma.ldy = ldy; ma.alpha = (float)alpha_eff; ma.beta = (float)beta;
+    ma.hk = &hk; ma.stream = ctx->stream; ma.Cn = (const float*)Y->center;
+    // plan, slab and grid of one launch over `rows` rows per wave and `nrpad` output columns per chunk
+    auto plan = [&](int rows, int64_t target, int nrpad, float* y_c, ColumnPlan* pl) {
+        *pl = plan_columns(n, ntile, rows, ctx->target_wgs > 0 ? ctx->target_wgs : target, ctx->jsplit, 8);
+        ma.npad = pl->npad; ma.tchunk = pl->tchunk; ma.final_store = pl->js == 1 ? 1 : 0;
+        ma.grid = dim3((unsigned)pl->rowtiles, (unsigned)pl->js);
+        return split_out(ctx, *pl, nrpad, y_c, &ma.out);
+    };
     int cdone = 0;
     // many right-hand sides: blocks of up to 64 on the fp32 matrix cores (dense_mfma_mrhs_kernel).  Its time is flat up to 32 columns
     // (n = 32768: 0.76 ms EQ, 0.86 ms MaternP(2)); the VALU form steps up every four columns (EQ d = 3: 0.29 / 0.56 / 0.81 ms at 4 / 8 /
     // 12; MaternP(2): 0.48 / 0.94 / 1.40): the crossover is 9 columns for the cheap profiles at d <= 3, 5 otherwise —
     // option "mfma_mrhs": -1 this rule, 0 never, 1 from 2 columns (tests)
-    const bool cheap = K2 <= 2 && (hk.tu_family == COVGRAM_EQ || hk.tu_family == COVGRAM_CAUCHY || hk.tu_family == COVGRAM_IMQ ||
-                                   hk.tu_family == COVGRAM_DOT || hk.tu_family == COVGRAM_EXPDOT);
+    const bool cheap = K2m <= 2 && (hk.tu_family == COVGRAM_EQ || hk.tu_family == COVGRAM_CAUCHY || hk.tu_family == COVGRAM_IMQ ||
+                                    hk.tu_family == COVGRAM_DOT || hk.tu_family == COVGRAM_EXPDOT);
     const int mrhs_min = ctx->mfma_mrhs == 1 ? 2 : (cheap ? 9 : 5);
     while (nrhs - cdone >= mrhs_min && ctx->mfma_mrhs != 0) {
         const int c0 = cdone;
         const int nr = std::min(64, nrhs - c0);
         const int NB = nr > 32 ? 2 : 1;
         float* y_c = y + (size_t)c0 * ldy;
-        void* P;
-        const size_t fb = (size_t)ntile * K2 * 64 * sizeof(uint4), wb = (size_t)ntile * 32 * sizeof(float);
-        rc = ws_reserve(ctx, 0, fb + wb + (size_t)ntile * NB * 64 * 16 * sizeof(float), &P);
+        float* Wd;                                                   // the pack kernel's weight output: unused here; the A operands sit behind it
+        rc = gen_fragments(ctx, Y, a, lda, 0, 1, K2m, gam, iso, 0, (size_t)ntile * NB * 64 * 16 * sizeof(float), &ma.PB, &Wd);
         if (rc) return rc;
-        uint4* PB = (uint4*)P;
-        float* Wd = (float*)((char*)P + fb);                       // the pack kernel's weight output: unused here
-        float* AP = (float*)((char*)P + fb + wb);
-        const int64_t pe = ntile * K2 * 64;
-        hipLaunchKernelGGL(mfma_pack_gen_kernel, dim3((unsigned)((pe + 255) / 256)), dim3(256), 0, ctx->stream, (const float*)Y->dptr, m, d, a,
-                           lda, 0, 0, PB, Wd, K2, 1, gam, iso ? 1 : 0, (const float*)Y->center, 0);
+        float* AP = Wd + ntile * 32;
         const int64_t ae = ntile * NB * 64 * 16;
         hipLaunchKernelGGL(mfma_pack_rhs_kernel, dim3((unsigned)((ae + 255) / 256)), dim3(256), 0, ctx->stream, a, lda, c0 + nr, c0, m, AP, NB);
-        const int64_t rowtiles = (n + 31) / 32, npad = rowtiles * 32;
-        int64_t target = ctx->target_wgs > 0 ? ctx->target_wgs : (int64_t)ctx->num_cus * 32;        // the fp32 MFMAs bound this kernel: 2 rounds of 4 waves per SIMD
-        int64_t js = ctx->jsplit > 0 ? ctx->jsplit : std::max<int64_t>(1, (target + rowtiles / 2) / rowtiles);
-        js = std::max<int64_t>(1, std::min<int64_t>(js, std::max<int64_t>(1, ntile / 8)));
-        const int64_t tchunk = (ntile + js - 1) / js;
-        js = (ntile + tchunk - 1) / tchunk;
-        float* out = y_c;
-        if (js > 1) { void* slab; rc = ws_reserve(ctx, 1, (size_t)js * 32 * NB * npad * sizeof(float), &slab); if (rc) return rc; out = (float*)slab; }
-        MfmaArgs ma;
-        ma.K2 = K2; ma.NR = 32 * NB; ma.RT = 1; ma.mrhs = NB;
-        ma.hk = &hk; ma.stream = ctx->stream; ma.Cn = (const float*)Y->center;
-        ma.X = (const float*)X->dptr; ma.n = n; ma.d = d; ma.PB = PB; ma.W = AP; ma.ntile = ntile; ma.out = out; ma.npad = npad; ma.ldy = ldy;
-        ma.nrhs = nr; ma.tchunk = tchunk; ma.alpha = (float)alpha_eff; ma.beta = (float)beta; ma.final_store = js == 1 ? 1 : 0;
-        ma.grid = dim3((unsigned)rowtiles, (unsigned)js);
+        ColumnPlan pl;
+        rc = plan(32, (int64_t)ctx->num_cus * 32, 32 * NB, y_c, &pl);   // the fp32 MFMAs bound this kernel: 2 rounds of 4 waves per SIMD
+        if (rc) return rc;
+        ma.K2 = K2m; ma.NR = 32 * NB; ma.RT = 1; ma.mrhs = NB; ma.fmt = 0; ma.lds = 0; ma.W = AP; ma.nrhs = nr;
         { TimerScope tm(ctx); rc = launch(ma, false); }
         if (rc) return rc;
-        if (js > 1)
-            hipLaunchKernelGGL(dense_reduce_kernel<float>, dim3((unsigned)((n + 63) / 64), nr), dim3(256), 0, ctx->stream, (const float*)out, npad,
-                               32 * NB, (int)js, y_c, n, ldy, nr, (float)alpha_eff, (float)beta);
+        if (pl.js > 1) reduce_split(ctx, ma.out, pl, 32 * NB, y_c, n, ldy, nr, alpha_eff, beta);
         cdone += nr;
     }
-    const int gfmt = gfmt_all;
-    if (gfmt) K2 = K2bf;                                                  // (mfma_gen_fmt returned the fp16 split's MFMAs per tile)
+    const int K2 = gfmt ? K2h : K2m;                                     // (mfma_gen_fmt returned the fp16 split's MFMAs per tile)
     ctx->last_mfma_f16 = gfmt;
     for (int c0 = cdone; c0 < nrhs; c0 += 4) {
         const int nr = std::min(4, nrhs - c0);
         const int NR = nr == 1 ? 1 : 4;
-        const float* a_c = a + (size_t)c0 * lda;
         float* y_c = y + (size_t)c0 * ldy;
-        void* P;
-        rc = ws_reserve(ctx, 0, (size_t)ntile * ((size_t)K2 * 64 * sizeof(uint4) + (size_t)NR * 32 * sizeof(float)), &P);
+        float* W;
+        rc = gen_fragments(ctx, Y, a + (size_t)c0 * lda, lda, nr, NR, K2, gam, iso, gfmt, 0, &ma.PB, &W);
         if (rc) return rc;
-        uint4* PB = (uint4*)P;
-        float* W = (float*)(PB + ntile * K2 * 64);
-        const int64_t pe = ntile * K2 * 64;
-        hipLaunchKernelGGL(mfma_pack_gen_kernel, dim3((unsigned)((pe + 255) / 256)), dim3(256), 0, ctx->stream, (const float*)Y->dptr, m, d, a_c,
-                           lda, nr, 0, PB, W, K2, NR, gam, iso ? 1 : 0, (const float*)Y->center, gfmt);
-        MfmaArgs ma;
-        ma.K2 = K2; ma.NR = NR; ma.fmt = gfmt;
+        ma.K2 = K2; ma.NR = NR; ma.fmt = gfmt; ma.mrhs = 0; ma.lds = 0; ma.W = W; ma.nrhs = nr;
         ma.RT = (NR == 1 && K2 <= 4 && ctx->rows_per_lane != 1) ? 2 : 1;
-        ma.hk = &hk; ma.stream = ctx->stream; ma.Cn = (const float*)Y->center;
         const int nb = launch(ma, true);
-        const int64_t rowtiles = (n + 32 * ma.RT - 1) / (32 * ma.RT);
-        const int64_t npad = rowtiles * 32 * ma.RT;
-        int64_t target = ctx->target_wgs > 0 ? ctx->target_wgs : (int64_t)ctx->num_cus * nb * 4;
-        int64_t js = ctx->jsplit > 0 ? ctx->jsplit : std::max<int64_t>(1, (target + rowtiles / 2) / rowtiles);
         // (the 64-tiles-per-wave stop of mvm_eq_mfma does not carry over: these profiles cost several times EQ's per tile, so a wave's fixed
         //  costs amortise over far fewer tiles — tools/rect_sweep.py, MaternP(2) 4096 x 65536: 32 splits 156 us, 128-256 splits 120-127 us)
-        js = std::max<int64_t>(1, std::min<int64_t>(js, std::max<int64_t>(1, ntile / 8)));
-        const int64_t tchunk = (ntile + js - 1) / js;
-        js = (ntile + tchunk - 1) / tchunk;
-        float* out = y_c;
-        if (js > 1) { void* slab; rc = ws_reserve(ctx, 1, (size_t)js * NR * npad * sizeof(float), &slab); if (rc) return rc; out = (float*)slab; }
-        ma.X = (const float*)X->dptr; ma.n = n; ma.d = d; ma.PB = PB; ma.W = W; ma.ntile = ntile; ma.out = out; ma.npad = npad; ma.ldy = ldy;
-        ma.nrhs = nr; ma.tchunk = tchunk; ma.alpha = (float)alpha_eff; ma.beta = (float)beta; ma.final_store = js == 1 ? 1 : 0;
-        ma.grid = dim3((unsigned)rowtiles, (unsigned)js);
+        ColumnPlan pl;
+        rc = plan(32 * ma.RT, (int64_t)ctx->num_cus * nb * 4, NR, y_c, &pl);
+        if (rc) return rc;
         // long fragments (d > 8) and long column chunks: four waves share every column tile through LDS, one tile per stage
         // (tools/mfma_lds_ab.py <kernel>: 11-28 % faster at d = 12 .. 24; at d <= 8 the barrier per tile costs 5-18 %, so not there)
-        ma.lds = (ctx->mfma_lds == 1 || (ctx->mfma_lds < 0 && K2 > 4 && tchunk >= MFMA_LDS_MIN_TILES && rowtiles >= 64)) ? 1 : 0;
+        ma.lds = (ctx->mfma_lds == 1 || (ctx->mfma_lds < 0 && K2 > 4 && pl.tchunk >= MFMA_LDS_MIN_TILES && pl.rowtiles >= 64)) ? 1 : 0;
         ctx->last_mfma_lds = ma.lds;
         { TimerScope tm(ctx); rc = launch(ma, false); }
         if (rc) return rc;
-        if (js > 1)
-            hipLaunchKernelGGL(dense_reduce_kernel<float>, dim3((unsigned)((n + 63) / 64), nr), dim3(256), 0, ctx->stream, (const float*)out, npad,
-                               NR, (int)js, y_c, n, ldy, nr, (float)alpha_eff, (float)beta);
+        if (pl.js > 1) reduce_split(ctx, ma.out, pl, NR, y_c, n, ldy, nr, alpha_eff, beta);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("dense_mfma launch failed: %s", hipGetErrorString(e)); return COVGRAM_EHIP; }

@@ -8,6 +8,7 @@
 // (Exp = MaternP(0), gammaExp) never take this path: an absolute error of 1e-7 P in s would become 3e-4 sqrt(P) in r.
 #pragma once
 #include "dense_mvm.hpp"
+#include <type_traits>
 
 namespace covgram {
 
@@ -664,7 +665,7 @@ template <> struct SymParamsOf<FAM_EQFAST_H> { using type = KParams<float>; };
 // profiles/r05_tile_body_probe.txt).  NOT 6: a workgroup's waves go round the CU's four SIMDs, so two 6-wave workgroups load them 4 / 2 / 4 / 2 and
 // the barriers pace every wave by the fullest SIMD (measured: MaternP(2) at C2 size 3.35 ms, VALU active 53 % of the time).
 // ORD: MaternP's order at compile time (mfma_profile_block)
-template <int FAM> constexpr int mfma_sym_nw = (FAM == COVGRAM_MATERNP || FAM == COVGRAM_RQ || FAM == FAM_SUM_ISO) ? 4 : 8;
+constexpr int mfma_sym_nw(int fam) { return (fam == COVGRAM_MATERNP || fam == COVGRAM_RQ || fam == FAM_SUM_ISO) ? 4 : 8; }   // (compile time: the launchers; run time: mfma_sym_tiles_per_panel)
 template <int FAM, int K2, int NW_ = 8, int ORD = 0, int GFMT = 0>
 __global__ __launch_bounds__(64 * NW_) __attribute__((amdgpu_waves_per_eu(NW_ == 8 ? 4 : 3, NW_ == 8 ? 4 : 3))) void dense_mfma_sym_kernel(
     const float* __restrict__ X, int64_t n, int32_t d, const uint4* __restrict__ PB, const float* __restrict__ W, int64_t ntile,
@@ -1052,28 +1053,44 @@ struct MfmaArgs {
     hipStream_t stream;
     dim3 grid;
     const float* Cn = nullptr;   // common centre of isotropic kernels (dense_mvm.hpp)
-    // symmetric form (dense_mfma_sym_kernel): row-sum slab R, column-sum slab S, the explicit workgroup list
     int32_t fmt = 0;             // 1: the generic kernels' fp16 two-way split (gen_row_fragments: GFMT = 1; isotropic profiles, K2 <= 4)
     int32_t lds = 0;             // 1: dense_mfma_gen_kernel<.., LDS = 2> (grid.x counts workgroups of 4 waves)
     int32_t mrhs = 0;            // 1 / 2: dense_mfma_mrhs_kernel with that many blocks of 32 right-hand sides (W = the packed A operands)
+    // symmetric form (dense_mfma_sym_kernel): row-sum slab R, column-sum slab S, the explicit workgroup list
     int32_t sym = 0;
     int32_t sym_rt = 1;          // 2: dense_mfma_sym2_kernel (two row tiles per wave, 8-tile panels) where the family has the instance (mfma_sym2_has)
     float* R = nullptr; float* S = nullptr;
     const int32_t* wgmap = nullptr;
     int32_t pfirst = 0, pstride = 1;
+    // EQ forms (dense_mfma_eq_kernel, the symmetric kernels at FAM_EQFAST*): the coordinate pre-scale, the cached fraction factors of the column norms (nullptr:
+    // W holds packed weights) and the column count, the arrival counters and final output of the in-kernel slab sum, the diagnostic clock stamps
+    float g = 0.0f; const float* EF = nullptr; int64_t mcols = 0;
+    unsigned* tickets = nullptr; float* yfinal = nullptr; unsigned long long* stamps = nullptr;
 };
 
-// returns the resident blocks per CU of the instance when `query` is set (no launch), COVGRAM_OK / error otherwise
+// ---- one function per kernel family spells its argument list ---------------------------------------------------------------------------------
 template <int FAM, int K2, int RT, int NR, int ORD, int GFMT>
 static void mfma_gen_launch_f(const MfmaArgs& a) {
-    if (a.lds)
-        hipLaunchKernelGGL((dense_mfma_gen_kernel<FAM, K2, RT, NR, 2, ORD, GFMT>), dim3((a.grid.x + 3) / 4, a.grid.y), dim3(256), 0, a.stream, a.X, a.n, a.d,
-                           a.PB, a.W, a.ntile, a.out, a.npad, a.ldy, a.nrhs, a.tchunk, a.alpha, a.beta, a.final_store, a.Cn,
-                           make_params<FAM, float>(*a.hk));
-    else
-        hipLaunchKernelGGL((dense_mfma_gen_kernel<FAM, K2, RT, NR, 0, ORD, GFMT>), a.grid, dim3(64), 0, a.stream, a.X, a.n, a.d, a.PB, a.W, a.ntile, a.out,
-                           a.npad, a.ldy, a.nrhs, a.tchunk, a.alpha, a.beta, a.final_store, a.Cn, make_params<FAM, float>(*a.hk));
+    auto go = [&](auto lds, dim3 grid, int block) {
+        hipLaunchKernelGGL((dense_mfma_gen_kernel<FAM, K2, RT, NR, decltype(lds)::value, ORD, GFMT>), grid, dim3(block), 0, a.stream, a.X, a.n, a.d, a.PB, a.W, a.ntile,
+                           a.out, a.npad, a.ldy, a.nrhs, a.tchunk, a.alpha, a.beta, a.final_store, a.Cn, make_params<FAM, float>(*a.hk));
+    };
+    if (a.lds) go(std::integral_constant<int, 2>{}, dim3((a.grid.x + 3) / 4, a.grid.y), 256);   // (grid.x counts waves: workgroups of 4)
+    else go(std::integral_constant<int, 0>{}, a.grid, 64);
 }
+template <int FAM, int K2, int NB>
+static int mfma_mrhs_one(const MfmaArgs& a) {
+    hipLaunchKernelGGL((dense_mfma_mrhs_kernel<FAM, K2, NB>), a.grid, dim3(64), 0, a.stream, a.X, a.n, a.d, a.PB, a.W, a.ntile, a.out, a.npad,
+                       a.ldy, a.nrhs, a.tchunk, a.alpha, a.beta, a.final_store, a.Cn, make_params<FAM, float>(*a.hk));
+    return COVGRAM_OK;
+}
+// dense_mfma_sym_kernel, dense_mfma_sym_wide_kernel and dense_mfma_sym2_kernel share a signature; kp: the family's parameter block (EQ forms: unused)
+template <auto Kernel, int BLOCK, typename KP>
+static void mfma_sym_launch(const MfmaArgs& a, const KP& kp) {
+    hipLaunchKernelGGL(Kernel, a.grid, dim3(BLOCK), 0, a.stream, a.X, a.n, a.d, a.PB, a.W, a.ntile, a.R, a.S, a.npad, (int32_t)a.tchunk, a.g, a.Cn,
+                       a.pfirst, a.pstride, a.wgmap, kp, a.EF);
+}
+
 // the fp16 split's instances exist for the isotropic families up to eight MFMAs per tile (d <= 30) — the host asks for nothing else
 template <int FAM, int K2> constexpr bool mfma_gen_has_f16 = fam_is_iso<FAM> && !fam_is_expr<FAM> && K2 <= 8;   // d + 2 positions of four per MFMA: d <= 30
 template <int FAM, int K2, int RT, int NR, int ORD>
@@ -1081,6 +1098,7 @@ static void mfma_gen_launch(const MfmaArgs& a) {
     if constexpr (mfma_gen_has_f16<FAM, K2>) { if (a.fmt == 1) { mfma_gen_launch_f<FAM, K2, RT, NR, ORD, 1>(a); return; } }
     mfma_gen_launch_f<FAM, K2, RT, NR, ORD, 0>(a);
 }
+// returns the resident blocks per CU of the instance when `query` is set (no launch), COVGRAM_OK / error otherwise
 template <int FAM, int K2, int RT, int NR>
 static int mfma_gen_one(const MfmaArgs& a, bool query) {
     if (query) {
@@ -1106,53 +1124,41 @@ static int mfma_gen_one(const MfmaArgs& a, bool query) {
     return COVGRAM_OK;
 }
 
-// the two-row-tile symmetric kernel's generic instances: isotropic single profiles at one or two MFMAs per tile (d <= 3 bf16, d <= 6 fp16).  NOT the
-// one-pass Sum: two row tiles of its term-by-term body spill into the tile loop (measured 6.3 against 4.0 ms for three terms, tools/gen_sym_rt_ab.py)
-template <int FAM, int K2> constexpr bool mfma_sym2_has = fam_is_iso<FAM> && !fam_is_expr<FAM> && FAM != FAM_SUM_ISO && K2 <= 2;
-inline bool mfma_sym2_family(int launcher_family) {
-    switch (launcher_family) { case COVGRAM_EQ: case COVGRAM_RQ: case COVGRAM_CAUCHY: case COVGRAM_IMQ: case COVGRAM_MATERNP: return true; default: return false; }
-}
-template <int FAM, int K2, int ORD>
-static void mfma_sym_narrow(const MfmaArgs& a) {
-    constexpr int NW = mfma_sym_nw<FAM>;
-    if constexpr (mfma_sym2_has<FAM, K2>) {
-        if (a.sym_rt == 2) {
-            if (a.fmt == 1)
-                hipLaunchKernelGGL((dense_mfma_sym2_kernel<FAM, K2, 8, ORD, 1>), a.grid, dim3(256), 0, a.stream, a.X, a.n, a.d, a.PB, a.W, a.ntile, a.R, a.S, a.npad,
-                                   (int32_t)a.tchunk, 0.0f, a.Cn, a.pfirst, a.pstride, a.wgmap, make_params<FAM, float>(*a.hk), (const float*)nullptr);
-            else
-                hipLaunchKernelGGL((dense_mfma_sym2_kernel<FAM, K2, 8, ORD, 0>), a.grid, dim3(256), 0, a.stream, a.X, a.n, a.d, a.PB, a.W, a.ntile, a.R, a.S, a.npad,
-                                   (int32_t)a.tchunk, 0.0f, a.Cn, a.pfirst, a.pstride, a.wgmap, make_params<FAM, float>(*a.hk), (const float*)nullptr);
-            return;
-        }
-    }
-    if constexpr (mfma_gen_has_f16<FAM, K2>) {
-        if (a.fmt == 1) {
-            hipLaunchKernelGGL((dense_mfma_sym_kernel<FAM, K2, NW, ORD, 1>), a.grid, dim3(64 * NW), 0, a.stream, a.X, a.n, a.d, a.PB, a.W, a.ntile, a.R, a.S, a.npad,
-                               (int32_t)a.tchunk, 0.0f, a.Cn, a.pfirst, a.pstride, a.wgmap, make_params<FAM, float>(*a.hk), (const float*)nullptr);
-            return;
-        }
-    }
-    hipLaunchKernelGGL((dense_mfma_sym_kernel<FAM, K2, NW, ORD, 0>), a.grid, dim3(64 * NW), 0, a.stream, a.X, a.n, a.d, a.PB, a.W, a.ntile, a.R, a.S, a.npad,
-                       (int32_t)a.tchunk, 0.0f, a.Cn, a.pfirst, a.pstride, a.wgmap, make_params<FAM, float>(*a.hk), (const float*)nullptr);
-}
-// which symmetric form serves (family, K2): the 8- or 6-wave panels with stages of four tiles (narrow), or four waves and one tile per stage
+// ---- the generic symmetric kernels ---------------------------------------------------------------------------------------------------------
+// Which symmetric form serves (launcher family, K2, row tiles per wave) — ONE description, constexpr functions of the family NUMBER: the launchers below
+// evaluate them at compile time, the driver at run time (dense_mfma.hip sizes panels, slabs and the work list from mfma_sym_tiles_per_panel).
+// The two-row-tile kernel's generic instances: isotropic single profiles at one or two MFMAs per tile (d <= 3 bf16, d <= 6 fp16).  NOT the one-pass Sum:
+// two row tiles of its term-by-term body spill into the tile loop (measured 6.3 against 4.0 ms for three terms, tools/gen_sym_rt_ab.py)
+constexpr bool mfma_sym2_has(int fam, int k2) { return fam_iso(fam) && !fam_expr(fam) && fam != FAM_SUM_ISO && k2 <= 2; }
+// the 8- or 4-wave panels with stages of four tiles (narrow, mfma_sym_nw row tiles per panel) up to this K2, beyond it four waves and one tile per stage
 // (wide).  The one-pass Sum takes the wide form from K2 = 3 on (its 6-wave instances spill 12-40 B at K2 = 3, 4) and has no instance beyond K2 = 8.
 // (round 5: six MFMAs per tile too for the 8-wave families — Cauchy, IMQ, EQ^p, dot products —, one tile at a time in registers; as the EQ form, dense_mfma.hip)
-template <int FAM> constexpr int mfma_sym_narrow_maxk2 = FAM == FAM_SUM_ISO ? 2 : ((mfma_sym_nw<FAM> == 8 && !fam_is_expr<FAM>) ? 6 : MFMA_NARROW_MAXK2);
-inline int mfma_sym_tiles_per_panel(int launcher_family, int k2, int sym_rt = 1) {
-    if (sym_rt == 2 && k2 <= 2 && mfma_sym2_family(launcher_family)) return 8;   // dense_mfma_sym2_kernel: 4 waves x 2 row tiles
-    const bool heavy = launcher_family == COVGRAM_MATERNP || launcher_family == COVGRAM_RQ || launcher_family == FAM_SUM_ISO;
-    const bool expr = launcher_family == FAM_EXPR_ISO || launcher_family == FAM_EXPR_DOT;
-    const int narrow_max = launcher_family == FAM_SUM_ISO ? 2 : ((heavy || expr) ? MFMA_NARROW_MAXK2 : 6);
-    return (k2 > narrow_max || heavy) ? 4 : 8;
+constexpr int mfma_sym_narrow_maxk2(int fam) { return fam == FAM_SUM_ISO ? 2 : ((mfma_sym_nw(fam) == 8 && !fam_expr(fam)) ? 6 : MFMA_NARROW_MAXK2); }
+constexpr int mfma_sym_tiles_per_panel(int fam, int k2, int sym_rt = 1) {
+    if (sym_rt == 2 && mfma_sym2_has(fam, k2)) return 8;   // dense_mfma_sym2_kernel: 4 waves x 2 row tiles
+    return k2 > mfma_sym_narrow_maxk2(fam) ? 4 : mfma_sym_nw(fam);
+}
+
+template <int FAM, int K2, int ORD>
+static void mfma_sym_narrow(const MfmaArgs& a) {
+    constexpr int NW = mfma_sym_nw(FAM);
+    const auto kp = make_params<FAM, float>(*a.hk);
+    if constexpr (mfma_sym2_has(FAM, K2)) {
+        if (a.sym_rt == 2) {
+            if (a.fmt == 1) mfma_sym_launch<dense_mfma_sym2_kernel<FAM, K2, 8, ORD, 1>, 256>(a, kp);
+            else mfma_sym_launch<dense_mfma_sym2_kernel<FAM, K2, 8, ORD, 0>, 256>(a, kp);
+            return;
+        }
+    }
+    if constexpr (mfma_gen_has_f16<FAM, K2>) { if (a.fmt == 1) { mfma_sym_launch<dense_mfma_sym_kernel<FAM, K2, NW, ORD, 1>, 64 * NW>(a, kp); return; } }
+    mfma_sym_launch<dense_mfma_sym_kernel<FAM, K2, NW, ORD, 0>, 64 * NW>(a, kp);
 }
 template <int FAM, int K2>
 static int mfma_sym_one(const MfmaArgs& a) {
     if constexpr (FAM == FAM_SUM_ISO && K2 > 8) {
         set_error("dense_mfma_sym: the one-pass Sum has no instance at K2 = %d", K2); return COVGRAM_EUNSUPPORTED;
     } else
-    if constexpr (K2 <= mfma_sym_narrow_maxk2<FAM>) {
+    if constexpr (K2 <= mfma_sym_narrow_maxk2(FAM)) {
         if constexpr (FAM == COVGRAM_MATERNP) {            // the order is a compile-time constant of the instance
             switch (a.hk->k.power == 1 ? a.hk->k.p : 0) {
                 case 1: mfma_sym_narrow<FAM, K2, 1>(a); break;
@@ -1164,23 +1170,10 @@ static int mfma_sym_one(const MfmaArgs& a) {
             if (a.hk->nterms == 2) mfma_sym_narrow<FAM, K2, 2>(a); else mfma_sym_narrow<FAM, K2, 3>(a);
         } else mfma_sym_narrow<FAM, K2, 0>(a);
     } else {
-        if constexpr (mfma_gen_has_f16<FAM, K2>) {
-            if (a.fmt == 1) {
-                hipLaunchKernelGGL((dense_mfma_sym_wide_kernel<FAM, K2, 1>), a.grid, dim3(256), 0, a.stream, a.X, a.n, a.d, a.PB, a.W, a.ntile, a.R, a.S,
-                                   a.npad, (int32_t)a.tchunk, 0.0f, a.Cn, a.pfirst, a.pstride, a.wgmap, make_params<FAM, float>(*a.hk), (const float*)nullptr);
-                return COVGRAM_OK;
-            }
-        }
-        hipLaunchKernelGGL((dense_mfma_sym_wide_kernel<FAM, K2, 0>), a.grid, dim3(256), 0, a.stream, a.X, a.n, a.d, a.PB, a.W, a.ntile, a.R, a.S,
-                           a.npad, (int32_t)a.tchunk, 0.0f, a.Cn, a.pfirst, a.pstride, a.wgmap, make_params<FAM, float>(*a.hk), (const float*)nullptr);
+        const auto kp = make_params<FAM, float>(*a.hk);
+        if constexpr (mfma_gen_has_f16<FAM, K2>) { if (a.fmt == 1) { mfma_sym_launch<dense_mfma_sym_wide_kernel<FAM, K2, 1>, 256>(a, kp); return COVGRAM_OK; } }
+        mfma_sym_launch<dense_mfma_sym_wide_kernel<FAM, K2, 0>, 256>(a, kp);
     }
-    return COVGRAM_OK;
-}
-
-template <int FAM, int K2, int NB>
-static int mfma_mrhs_one(const MfmaArgs& a) {
-    hipLaunchKernelGGL((dense_mfma_mrhs_kernel<FAM, K2, NB>), a.grid, dim3(64), 0, a.stream, a.X, a.n, a.d, a.PB, a.W, a.ntile, a.out, a.npad,
-                       a.ldy, a.nrhs, a.tchunk, a.alpha, a.beta, a.final_store, a.Cn, make_params<FAM, float>(*a.hk));
     return COVGRAM_OK;
 }
 
@@ -1194,19 +1187,18 @@ static int mfma_gen_K(const MfmaArgs& a, bool query) {
     return mfma_gen_one<FAM, K2, 1, 1>(a, query);
 }
 
+// calls f(std::integral_constant<int, K2>) for a compiled number of MFMAs per tile (the set of mfma_k2_for, dense_mfma.hip); false: not compiled
+template <int... Ks, typename F>
+static bool mfma_for_k2_in(int K2, F&& f) { return ((K2 == Ks && (f(std::integral_constant<int, Ks>{}), true)) || ...); }
+template <typename F>
+static bool mfma_for_k2(int K2, F&& f) { return mfma_for_k2_in<1, 2, 3, 4, 6, 8, 12, 16>(K2, f); }
+
 template <int FAM>
 int launch_mfma_family(const MfmaArgs& a, bool query) {
-    switch (a.K2) {
-        case 1: return mfma_gen_K<FAM, 1>(a, query);
-        case 2: return mfma_gen_K<FAM, 2>(a, query);
-        case 3: return mfma_gen_K<FAM, 3>(a, query);
-        case 4: return mfma_gen_K<FAM, 4>(a, query);
-        case 6: return mfma_gen_K<FAM, 6>(a, query);
-        case 8: return mfma_gen_K<FAM, 8>(a, query);
-        case 12: return mfma_gen_K<FAM, 12>(a, query);
-        case 16: return mfma_gen_K<FAM, 16>(a, query);
-        default: set_error("dense_mfma: K2 = %d not compiled", a.K2); return COVGRAM_EUNSUPPORTED;
-    }
+    int rc = COVGRAM_OK;
+    if (mfma_for_k2(a.K2, [&](auto k) { rc = mfma_gen_K<FAM, decltype(k)::value>(a, query); })) return rc;
+    set_error("dense_mfma: K2 = %d not compiled", a.K2);
+    return COVGRAM_EUNSUPPORTED;
 }
 
 typedef int (*mfma_launch_fn)(const MfmaArgs&, bool query);

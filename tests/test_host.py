@@ -356,6 +356,19 @@ def test_post_build_isa_lint():
     assert r.stdout.count("ok:") >= 6, r.stdout
 
 
+def test_mfma_plan_header_properties(tmp_path):
+    """csrc/mfma_plan.hpp — the column split and the symmetric (panel, chunk) work list of the matrix-core drivers, plain arithmetic without HIP —
+    compiled into the stand-alone tests/mfma_plan_check.cpp with the host compiler and AddressSanitizer + UBSan (runtimes linked statically: the
+    program runs directly, nothing is preloaded): every (panel, tile) of the triangle walked exactly once, no empty workgroup, whole chunks ahead
+    of cut ones in non-increasing length, entries inside the 19 + 12-bit packing; column plans that cover every tile with >= 8 tiles per wave."""
+    import subprocess
+    exe = tmp_path / "mfma_plan_check"
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-static-libasan", "-static-libubsan", os.path.join(ROOT, "tests", "mfma_plan_check.cpp"), "-o", str(exe)])
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "mfma_plan ok" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+
+
 def test_docs_quote_the_recorded_numbers():
     """VERDICT r3 and r4 both found the READMEs quoting headline numbers that the recorded files do not hold.  The marked statements — README.md's
     headline block, and every profiles/README.md row tagged <!-- check:rNN --> — must agree within 2 % with profiles/rNN_bench_n1.json and the
