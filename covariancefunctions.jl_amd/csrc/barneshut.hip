@@ -33,6 +33,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
+#include "driver.hpp"
 #include "profiles.hpp"
 
 namespace covgram {
@@ -699,110 +700,84 @@ static int bh_build(covgram_bh* F, const covgram_points* X, const covgram_points
     return COVGRAM_OK;
 }
 
-// the first stage of a product on the ctx stream: ws, then sums and com of NS channels
-template <typename T, int DM, int NS>
-static void bh_launch_moments(covgram_bh* F, const T* w, hipStream_t st) {
+// parents from children, level by level: the moments of a node are CH values per channel, NS channels
+template <int CH, int NS>
+static void bh_up_sweep(covgram_bh* F) {
+    hipStream_t st = F->ctx->stream;
     const int64_t nn = F->nnodes;
-    hipLaunchKernelGGL((bh_leaf_moments_kernel<T, DM, NS>), dim3((unsigned)((F->nleaves + 255) / 256)), dim3(256), 0, st, F->leaves, F->nleaves, F->lo(),
-                       F->hi(), F->indices, (const T*)F->Ys, w, (T*)F->ws, F->mom, nn);
     for (int L = F->maxdepth; L > BH_TOP_DEPTH; --L) {
         const int64_t cnt = F->off[L + 1] - F->off[L];
         if (cnt > 0)
-            hipLaunchKernelGGL((bh_up_level_kernel<DM, NS>), dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, F->order, F->off[L], cnt, F->right(),
+            hipLaunchKernelGGL((bh_up_level_kernel<CH, NS>), dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, F->order, F->off[L], cnt, F->right(),
                                F->mom, nn);
     }
     const int top = std::min<int>(F->maxdepth, BH_TOP_DEPTH);
     if (F->off[top + 1] > 0)
-        hipLaunchKernelGGL((bh_up_top_kernel<DM, NS>), dim3(1), dim3(256), 0, st, F->order, F->off_dev, top, F->right(), F->mom, nn);
-    hipLaunchKernelGGL((bh_finalize_kernel<T, DM, NS>), dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, F->mom, nn, (T*)F->sums, (T*)F->com);
+        hipLaunchKernelGGL((bh_up_top_kernel<CH, NS>), dim3(1), dim3(256), 0, st, F->order, F->off_dev, top, F->right(), F->mom, nn);
 }
 
+// the first stage of a product on the ctx stream: ws, then sums and com of NS channels
 template <typename T, int DM, int NS>
-static void bh_launch_product(covgram_bh* F, const T* w, T* b, double alpha, double beta, double theta, const T* diag, int64_t diag_len, hipStream_t st) {
-    if (F->nnodes > 0) bh_launch_moments<T, DM, NS>(F, w, st);
-    BhWalk<T> g;
-    g.Xs = (const T*)F->Xs; g.xperm = F->xperm; g.n = F->n; g.Ys = (const T*)F->Ys; g.ws = (const T*)F->ws;
-    g.lo = F->lo(); g.hi = F->hi(); g.skip = F->skip(); g.rad = (const T*)F->rad; g.sums = (const T*)F->sums; g.com = (const T*)F->com;
-    g.nnodes = (int32_t)F->nnodes; g.family = F->hk.k.family; g.theta = (T)theta;
-    g.alpha_k = (T)(alpha * F->hk.kp.scale); g.alpha = (T)alpha; g.beta = (T)beta;
-    g.w = w; g.diag = diag; g.diag_len = diag_len; g.b = b;
-    auto* tm = timer_next(F->ctx);
-    if (tm) (void)hipEventRecord(tm->first, st);
-    hipLaunchKernelGGL((bh_walk_kernel<T, DM, NS>), dim3((unsigned)((F->n + 63) / 64)), dim3(64), 0, st, g, cast_params<T>(F->hk.kp));
-    if (tm) (void)hipEventRecord(tm->second, st);
-}
-
-template <typename T, int NS>
-static void bh_product_dm(covgram_bh* F, const void* w, void* b, double alpha, double beta, double theta, const void* diag, int64_t diag_len, hipStream_t st) {
-    switch (F->DM) {
-        case 2: bh_launch_product<T, 2, NS>(F, (const T*)w, (T*)b, alpha, beta, theta, (const T*)diag, diag_len, st); break;
-        case 4: bh_launch_product<T, 4, NS>(F, (const T*)w, (T*)b, alpha, beta, theta, (const T*)diag, diag_len, st); break;
-        default: bh_launch_product<T, 8, NS>(F, (const T*)w, (T*)b, alpha, beta, theta, (const T*)diag, diag_len, st); break;
-    }
-}
-
-template <typename T>
-static void bh_moments_dm(covgram_bh* F, const void* w, hipStream_t st) {
-    switch (F->DM) {
-        case 2: bh_launch_moments<T, 2, 1>(F, (const T*)w, st); break;
-        case 4: bh_launch_moments<T, 4, 1>(F, (const T*)w, st); break;
-        default: bh_launch_moments<T, 8, 1>(F, (const T*)w, st); break;
-    }
+static void bh_launch_moments(covgram_bh* F, const T* w) {
+    hipStream_t st = F->ctx->stream;
+    const int64_t nn = F->nnodes;
+    hipLaunchKernelGGL((bh_leaf_moments_kernel<T, DM, NS>), dim3((unsigned)((F->nleaves + 255) / 256)), dim3(256), 0, st, F->leaves, F->nleaves, F->lo(),
+                       F->hi(), F->indices, (const T*)F->Ys, w, (T*)F->ws, F->mom, nn);
+    bh_up_sweep<DM, NS>(F);
+    hipLaunchKernelGGL((bh_finalize_kernel<T, DM, NS>), dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, F->mom, nn, (T*)F->sums, (T*)F->com);
 }
 
 // taylor!: ws, then sums, centres and centred first moments (one channel; the storage of the split product holds it: nnodes (2 + 2 DM)
 // doubles <= 2 nnodes (2 + DM), and centre + m1 are the 2 DM values per node of com)
 template <typename T, int DM>
-static void bh_launch_taylor_moments(covgram_bh* F, const T* w, int use_com, hipStream_t st) {
+static void bh_launch_taylor_moments(covgram_bh* F, const T* w, int use_com) {
+    hipStream_t st = F->ctx->stream;
     const int64_t nn = F->nnodes;
     hipLaunchKernelGGL((bh_taylor_leaf_moments_kernel<T, DM>), dim3((unsigned)((F->nleaves + 255) / 256)), dim3(256), 0, st, F->leaves, F->nleaves,
                        F->lo(), F->hi(), F->indices, (const T*)F->Ys, w, (T*)F->ws, F->mom);
-    for (int L = F->maxdepth; L > BH_TOP_DEPTH; --L) {
-        const int64_t cnt = F->off[L + 1] - F->off[L];
-        if (cnt > 0)
-            hipLaunchKernelGGL((bh_up_level_kernel<2 * DM, 1>), dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, F->order, F->off[L], cnt,
-                               F->right(), F->mom, nn);
-    }
-    const int top = std::min<int>(F->maxdepth, BH_TOP_DEPTH);
-    if (F->off[top + 1] > 0)
-        hipLaunchKernelGGL((bh_up_top_kernel<2 * DM, 1>), dim3(1), dim3(256), 0, st, F->order, F->off_dev, top, F->right(), F->mom, nn);
+    bh_up_sweep<2 * DM, 1>(F);
     hipLaunchKernelGGL((bh_taylor_finalize_kernel<T, DM>), dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, F->mom, nn, use_com,
                        (const T*)F->centers, (int)F->d, (T*)F->sums, (T*)F->com);
 }
 
-template <typename T, int DM>
-static void bh_launch_taylor(covgram_bh* F, const T* w, T* b, double alpha, double beta, double theta, int use_com, const T* diag, int64_t diag_len,
-                             hipStream_t st) {
-    if (F->nnodes > 0) bh_launch_taylor_moments<T, DM>(F, w, use_com, st);
+// what either walk kernel reads: the handle's arrays and the arguments of this product
+template <typename T>
+static BhWalk<T> bh_walk_args(const covgram_bh* F, const T* w, T* b, double alpha, double beta, double theta, const T* diag, int64_t diag_len) {
     BhWalk<T> g;
     g.Xs = (const T*)F->Xs; g.xperm = F->xperm; g.n = F->n; g.Ys = (const T*)F->Ys; g.ws = (const T*)F->ws;
     g.lo = F->lo(); g.hi = F->hi(); g.skip = F->skip(); g.rad = (const T*)F->rad; g.sums = (const T*)F->sums; g.com = (const T*)F->com;
     g.nnodes = (int32_t)F->nnodes; g.family = F->hk.k.family; g.theta = (T)theta;
     g.alpha_k = (T)(alpha * F->hk.kp.scale); g.alpha = (T)alpha; g.beta = (T)beta;
     g.w = w; g.diag = diag; g.diag_len = diag_len; g.b = b;
-    auto* tm = timer_next(F->ctx);
-    if (tm) (void)hipEventRecord(tm->first, st);
-    hipLaunchKernelGGL((bh_taylor_walk_kernel<T, DM>), dim3((unsigned)((F->n + 63) / 64)), dim3(64), 0, st, g, cast_params<T>(F->hk.kp));
-    if (tm) (void)hipEventRecord(tm->second, st);
+    return g;
 }
 
-template <typename T>
-static void bh_taylor_dm(covgram_bh* F, const void* w, void* b, double alpha, double beta, double theta, int use_com, const void* diag, int64_t diag_len,
-                         hipStream_t st) {
-    switch (F->DM) {
-        case 2: bh_launch_taylor<T, 2>(F, (const T*)w, (T*)b, alpha, beta, theta, use_com, (const T*)diag, diag_len, st); break;
-        case 4: bh_launch_taylor<T, 4>(F, (const T*)w, (T*)b, alpha, beta, theta, use_com, (const T*)diag, diag_len, st); break;
-        default: bh_launch_taylor<T, 8>(F, (const T*)w, (T*)b, alpha, beta, theta, use_com, (const T*)diag, diag_len, st); break;
-    }
+// the moments of g.w, then the walk (the timed kernel), one lane per target
+template <typename T, int DM, int NS>
+static void bh_launch_product(covgram_bh* F, const BhWalk<T>& g) {
+    if (F->nnodes > 0) bh_launch_moments<T, DM, NS>(F, g.w);
+    TimerScope timed(F->ctx);
+    hipLaunchKernelGGL((bh_walk_kernel<T, DM, NS>), dim3((unsigned)((F->n + 63) / 64)), dim3(64), 0, F->ctx->stream, g, cast_params<T>(F->hk.kp));
 }
 
-template <typename T>
-static void bh_taylor_moments_dm(covgram_bh* F, const void* w, int use_com, hipStream_t st) {
-    switch (F->DM) {
-        case 2: bh_launch_taylor_moments<T, 2>(F, (const T*)w, use_com, st); break;
-        case 4: bh_launch_taylor_moments<T, 4>(F, (const T*)w, use_com, st); break;
-        default: bh_launch_taylor_moments<T, 8>(F, (const T*)w, use_com, st); break;
-    }
+template <typename T, int DM>
+static void bh_launch_taylor(covgram_bh* F, const BhWalk<T>& g, int use_com) {
+    if (F->nnodes > 0) bh_launch_taylor_moments<T, DM>(F, g.w, use_com);
+    TimerScope timed(F->ctx);
+    hipLaunchKernelGGL((bh_taylor_walk_kernel<T, DM>), dim3((unsigned)((F->n + 63) / 64)), dim3(64), 0, F->ctx->stream, g, cast_params<T>(F->hk.kp));
+}
+
+// f(T{}, integral_constant<int, DM>{}): the handle's element type and padded dimension (2, 4, 8) as compile-time values
+template <typename Fn>
+static void bh_dispatch(const covgram_bh* F, Fn&& f) {
+    using std::integral_constant;
+    by_dtype(F->dtype, [&](auto t0) {
+        switch (F->DM) {
+            case 2: f(t0, integral_constant<int, 2>{}); break;
+            case 4: f(t0, integral_constant<int, 4>{}); break;
+            default: f(t0, integral_constant<int, 8>{}); break;
+        }
+    });
 }
 
 }  // namespace covgram
@@ -810,7 +785,7 @@ static void bh_taylor_moments_dm(covgram_bh* F, const void* w, int use_com, hipS
 using namespace covgram;
 
 // What covgram_bh_mvm and covgram_bh_taylor_mvm share: the argument checks, theta < 0 = the handle's, the staging of host buffers and
-// the copy back.  launch(a_dev, y_dev, theta, diag_dev, diag_len, stream) enqueues the product itself.
+// the copy back.  launch(a_dev, y_dev, theta, diag_dev, diag_len) enqueues the product itself.
 template <typename Launch>
 static int bh_product_call(covgram_bh* F, const void* a, void* y, double beta, double theta, const void* diag, int64_t diag_len, int32_t loc,
                            Launch launch) {
@@ -828,29 +803,39 @@ static int bh_product_call(covgram_bh* F, const void* a, void* y, double beta, d
     covgram_ctx* ctx = F->ctx;
     const size_t ts = dtype_size(F->dtype);
     CG_DEVICE(ctx);
-    const void *a_dev = a, *d_dev = diag;
-    void* y_dev = y;
-    if (loc == COVGRAM_HOST) {                   // a is staged before anything is written back: any overlap of a and y is harmless
-        void *sa, *sy, *sd;
-        int rc = ws_reserve(ctx, 2, (size_t)std::max<int64_t>(m, 1) * ts, &sa); if (rc) return rc;
-        rc = ws_reserve(ctx, 3, (size_t)n * ts, &sy); if (rc) return rc;
-        if (m > 0) CG_CHECK_HIP(hipMemcpyAsync(sa, a, (size_t)m * ts, hipMemcpyHostToDevice, ctx->stream));
-        if (beta != 0.0) CG_CHECK_HIP(hipMemcpyAsync(sy, y, (size_t)n * ts, hipMemcpyHostToDevice, ctx->stream));
-        if (diag_len > 0) {
-            rc = ws_reserve(ctx, 4, (size_t)diag_len * ts, &sd); if (rc) return rc;
-            CG_CHECK_HIP(hipMemcpyAsync(sd, diag, (size_t)diag_len * ts, hipMemcpyHostToDevice, ctx->stream));
-            d_dev = sd;
-        }
-        a_dev = sa; y_dev = sy;
-    }
-    // (device pointers: y may be a itself — the walk reads the weights from the handle's tree-ordered copy, which the moments stage
-    //  has completed before the walk starts, and a lane reads a[i] for the diagonal term before it writes y[i])
-    launch(a_dev, y_dev, theta, d_dev, diag_len, ctx->stream);
-    CG_CHECK_HIP(hipGetLastError());
+    // Staged serves HOST pointers only.  DEVICE pointers go through as they are, y may be a itself: the walk reads the weights from the
+    // handle's tree-ordered copy, which the moments stage has completed before the walk starts, and a lane reads a[i] for the diagonal term
+    // before it writes y[i] — Staged's private copy of an overlapping a would be a device-to-device copy that nothing needs
+    Staged st;
+    st.a = a; st.y = y;
+    const void* d_dev = diag;
     if (loc == COVGRAM_HOST) {
-        CG_CHECK_HIP(hipMemcpyAsync(y, y_dev, (size_t)n * ts, hipMemcpyDeviceToHost, ctx->stream));
-        CG_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+        int rc = st.begin(ctx, loc, ts, a, m, m, y, n, n, 1, beta); if (rc) return rc;
+        void* sd = nullptr; int64_t ld;
+        if (diag_len > 0) { rc = ws_reserve(ctx, 4, staged_bytes(diag_len, 1, ts), &sd); if (rc) return rc; }
+        char* cur = (char*)sd;
+        rc = stage_operand(ctx, loc, ts, cur, diag, diag_len, diag_len, 1, &d_dev, &ld); if (rc) return rc;
     }
+    launch(st.a, st.y, theta, d_dev, diag_len);
+    CG_CHECK_HIP(hipGetLastError());
+    return st.finish();
+}
+
+// What covgram_bh_moments and covgram_bh_taylor_moments share.  The weights as the moment kernels see them: HOST: a copy in workspace slot 2
+static int bh_stage_w(covgram_bh* F, const void* w, int32_t loc, const void** w_dev) {
+    const size_t ts = dtype_size(F->dtype);
+    void* sw = nullptr;
+    if (loc == COVGRAM_HOST) { int rc = ws_reserve(F->ctx, 2, staged_bytes(F->m, 1, ts), &sw); if (rc) return rc; }
+    char* cur = (char*)sw;
+    int64_t ld;
+    return stage_operand(F->ctx, loc, ts, cur, w, F->m, F->m, 1, w_dev, &ld);
+}
+// `rows` rows of `row` bytes, `pitch` bytes apart in the handle, to the caller's packed array of loc (dst == NULL: not asked for)
+static int bh_copy_rows(covgram_ctx* ctx, void* dst, const void* src, size_t row, size_t pitch, size_t rows, int32_t loc) {
+    if (!dst) return COVGRAM_OK;
+    const hipMemcpyKind kind = loc == COVGRAM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (pitch == row) CG_CHECK_HIP(hipMemcpyAsync(dst, src, row * rows, kind, ctx->stream));
+    else CG_CHECK_HIP(hipMemcpy2DAsync(dst, row, src, pitch, row, rows, kind, ctx->stream));
     return COVGRAM_OK;
 }
 
@@ -885,7 +870,7 @@ int covgram_bh_create(covgram_ctx* ctx, covgram_bh** out, const covgram_kernel* 
     covgram_bh* F = new covgram_bh();
     F->ctx = ctx; F->n = X->n; F->m = Y->n; F->d = X->d; F->dtype = dtype; F->leafsize = leafsize; F->theta = theta; F->hk = hk;
     F->DM = X->d <= 2 ? 2 : (X->d <= 4 ? 4 : 8);
-    rc = dtype == COVGRAM_F32 ? bh_build<float>(F, X, Y) : bh_build<double>(F, X, Y);
+    rc = by_dtype(dtype, [&](auto t0) { return bh_build<decltype(t0)>(F, X, Y); });
     if (rc) { bh_free(F); delete F; return rc; }
     ctx->live_handles++;
     *out = F;
@@ -931,36 +916,27 @@ int covgram_bh_moments(covgram_bh* F, const void* w, void* sums, void* com, int3
     if (F->nnodes == 0) return COVGRAM_OK;
     CG_REQUIRE(w != nullptr, COVGRAM_EINVAL, "w is NULL");
     covgram_ctx* ctx = F->ctx;
-    const size_t ts = dtype_size(F->dtype);
+    const size_t ts = dtype_size(F->dtype), nn = (size_t)F->nnodes;
     CG_DEVICE(ctx);
-    const void* w_dev = w;
-    if (loc == COVGRAM_HOST) {
-        void* sw;
-        int rc = ws_reserve(ctx, 2, (size_t)F->m * ts, &sw); if (rc) return rc;
-        CG_CHECK_HIP(hipMemcpyAsync(sw, w, (size_t)F->m * ts, hipMemcpyHostToDevice, ctx->stream));
-        w_dev = sw;
-    }
-    if (F->dtype == COVGRAM_F32) bh_moments_dm<float>(F, w_dev, ctx->stream);
-    else bh_moments_dm<double>(F, w_dev, ctx->stream);
+    const void* w_dev;
+    int rc = bh_stage_w(F, w, loc, &w_dev); if (rc) return rc;
+    bh_dispatch(F, [&](auto t0, auto dm) { bh_launch_moments<decltype(t0), decltype(dm)::value, 1>(F, (const decltype(t0)*)w_dev); });
     CG_CHECK_HIP(hipGetLastError());
-    const hipMemcpyKind kind = loc == COVGRAM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    if (sums) CG_CHECK_HIP(hipMemcpyAsync(sums, F->sums, (size_t)F->nnodes * ts, kind, ctx->stream));     // one channel: [nnodes]
-    if (com) CG_CHECK_HIP(hipMemcpy2DAsync(com, (size_t)F->d * ts, F->com, (size_t)F->DM * ts, (size_t)F->d * ts, (size_t)F->nnodes, kind, ctx->stream));
+    rc = bh_copy_rows(ctx, sums, F->sums, nn * ts, nn * ts, 1, loc); if (rc) return rc;             // one channel: [nnodes]
+    rc = bh_copy_rows(ctx, com, F->com, (size_t)F->d * ts, (size_t)F->DM * ts, nn, loc); if (rc) return rc;
     if (loc == COVGRAM_HOST) CG_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     return COVGRAM_OK;
 }
 
 int covgram_bh_mvm(covgram_bh* F, const void* a, void* y, double alpha, double beta, double theta, int32_t split, const void* diag, int64_t diag_len,
                    int32_t loc) {
-    return bh_product_call(F, a, y, beta, theta, diag, diag_len, loc,
-                           [&](const void* a_dev, void* y_dev, double th, const void* d_dev, int64_t dl, hipStream_t st) {
-        if (F->dtype == COVGRAM_F32) {
-            if (split) bh_product_dm<float, 2>(F, a_dev, y_dev, alpha, beta, th, d_dev, dl, st);
-            else bh_product_dm<float, 1>(F, a_dev, y_dev, alpha, beta, th, d_dev, dl, st);
-        } else {
-            if (split) bh_product_dm<double, 2>(F, a_dev, y_dev, alpha, beta, th, d_dev, dl, st);
-            else bh_product_dm<double, 1>(F, a_dev, y_dev, alpha, beta, th, d_dev, dl, st);
-        }
+    return bh_product_call(F, a, y, beta, theta, diag, diag_len, loc, [&](const void* a_dev, void* y_dev, double th, const void* d_dev, int64_t dl) {
+        bh_dispatch(F, [&](auto t0, auto dm) {
+            using T = decltype(t0);
+            const BhWalk<T> g = bh_walk_args<T>(F, (const T*)a_dev, (T*)y_dev, alpha, beta, th, (const T*)d_dev, dl);
+            if (split) bh_launch_product<T, decltype(dm)::value, 2>(F, g);
+            else bh_launch_product<T, decltype(dm)::value, 1>(F, g);
+        });
     });
 }
 
@@ -970,33 +946,27 @@ int covgram_bh_taylor_moments(covgram_bh* F, const void* w, int32_t use_com, voi
     if (F->nnodes == 0) return COVGRAM_OK;
     CG_REQUIRE(w != nullptr, COVGRAM_EINVAL, "w is NULL");
     covgram_ctx* ctx = F->ctx;
-    const size_t ts = dtype_size(F->dtype);
+    const size_t ts = dtype_size(F->dtype), nn = (size_t)F->nnodes;
     CG_DEVICE(ctx);
-    const void* w_dev = w;
-    if (loc == COVGRAM_HOST) {
-        void* sw;
-        int rc = ws_reserve(ctx, 2, (size_t)F->m * ts, &sw); if (rc) return rc;
-        CG_CHECK_HIP(hipMemcpyAsync(sw, w, (size_t)F->m * ts, hipMemcpyHostToDevice, ctx->stream));
-        w_dev = sw;
-    }
-    if (F->dtype == COVGRAM_F32) bh_taylor_moments_dm<float>(F, w_dev, use_com != 0, ctx->stream);
-    else bh_taylor_moments_dm<double>(F, w_dev, use_com != 0, ctx->stream);
+    const void* w_dev;
+    int rc = bh_stage_w(F, w, loc, &w_dev); if (rc) return rc;
+    bh_dispatch(F, [&](auto t0, auto dm) { bh_launch_taylor_moments<decltype(t0), decltype(dm)::value>(F, (const decltype(t0)*)w_dev, use_com != 0); });
     CG_CHECK_HIP(hipGetLastError());
-    const hipMemcpyKind kind = loc == COVGRAM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     const size_t row = (size_t)F->d * ts, pitch = (size_t)2 * F->DM * ts;       // per node: the centre, then m1, DM values each
-    if (sums) CG_CHECK_HIP(hipMemcpyAsync(sums, F->sums, (size_t)F->nnodes * ts, kind, ctx->stream));
-    if (centers) CG_CHECK_HIP(hipMemcpy2DAsync(centers, row, F->com, pitch, row, (size_t)F->nnodes, kind, ctx->stream));
-    if (m1) CG_CHECK_HIP(hipMemcpy2DAsync(m1, row, (const char*)F->com + (size_t)F->DM * ts, pitch, row, (size_t)F->nnodes, kind, ctx->stream));
+    rc = bh_copy_rows(ctx, sums, F->sums, nn * ts, nn * ts, 1, loc); if (rc) return rc;
+    rc = bh_copy_rows(ctx, centers, F->com, row, pitch, nn, loc); if (rc) return rc;
+    rc = bh_copy_rows(ctx, m1, (const char*)F->com + (size_t)F->DM * ts, row, pitch, nn, loc); if (rc) return rc;
     if (loc == COVGRAM_HOST) CG_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     return COVGRAM_OK;
 }
 
 int covgram_bh_taylor_mvm(covgram_bh* F, const void* a, void* y, double alpha, double beta, double theta, int32_t use_com, const void* diag,
                           int64_t diag_len, int32_t loc) {
-    return bh_product_call(F, a, y, beta, theta, diag, diag_len, loc,
-                           [&](const void* a_dev, void* y_dev, double th, const void* d_dev, int64_t dl, hipStream_t st) {
-        if (F->dtype == COVGRAM_F32) bh_taylor_dm<float>(F, a_dev, y_dev, alpha, beta, th, use_com != 0, d_dev, dl, st);
-        else bh_taylor_dm<double>(F, a_dev, y_dev, alpha, beta, th, use_com != 0, d_dev, dl, st);
+    return bh_product_call(F, a, y, beta, theta, diag, diag_len, loc, [&](const void* a_dev, void* y_dev, double th, const void* d_dev, int64_t dl) {
+        bh_dispatch(F, [&](auto t0, auto dm) {
+            using T = decltype(t0);
+            bh_launch_taylor<T, decltype(dm)::value>(F, bh_walk_args<T>(F, (const T*)a_dev, (T*)y_dev, alpha, beta, th, (const T*)d_dev, dl), use_com != 0);
+        });
     });
 }
 

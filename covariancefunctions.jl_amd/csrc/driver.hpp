@@ -1,6 +1,10 @@
-// driver.hpp — what the C-ABI drivers share (api.hip, matrix.hip, block_mvm.hip, sm.hip, sparse.hip, ...): staging of host pointers,
-// dtype dispatch, the timer bracket, the Sum split.  Host code only; the per-family kernel units include common.hpp, not this.
+// driver.hpp — what the C-ABI drivers share: staging of host pointers, dtype dispatch, the timer bracket, the Sum split.  Served units: the
+// point-pair entries (api.hip, matrix.hip, block_mvm.hip, sm.hip, sparse.hip, bilin_grad.hip, input_grad.hip, dense_mfma.hip, pivchol.hip) and the
+// structured operators (toeplitz.hip, toeplitz_direct.hip, kron.hip, lowrank.hip, barneshut.hip).  Host code only; the per-family kernel units
+// include common.hpp, not this.
 #pragma once
+#include <type_traits>
+
 #include "common.hpp"
 
 namespace covgram {
@@ -10,6 +14,13 @@ template <typename F>
 inline decltype(auto) by_dtype(int dtype, F&& f) {
     if (dtype == COVGRAM_F32) return f(float{});
     return f(double{});
+}
+
+// f(std::true_type{}) or f(std::false_type{}): the same for a flag that is a template argument of the launch
+template <typename F>
+inline decltype(auto) by_bool(bool b, F&& f) {
+    if (b) return f(std::true_type{});
+    return f(std::false_type{});
 }
 
 // HIP-event bracket around the dominant kernel of a product (option "time_kernels"): the first event is recorded here, the second on EVERY way
@@ -46,6 +57,20 @@ private:
     int64_t host_ld_ = 0, rows_ = 0, cols_ = 0;
     size_t ts_ = 0;
 };
+
+// One further operand of a call (rows x cols, column-major, leading dimension ld: a factor, a first column, a right-hand side) as the kernels
+// see it.  HOST: a packed device copy (*ldd = rows) at the cursor `cur` into a workspace the caller reserved — staged_bytes() of it per
+// operand — which moves on to the next 256-byte boundary; the copy is enqueued on the ctx stream.  DEVICE: the caller's array.
+inline size_t staged_bytes(int64_t rows, int64_t cols, size_t ts) { return ((size_t)rows * (size_t)cols * ts + 255) & ~(size_t)255; }
+inline int stage_operand(covgram_ctx* ctx, int loc, size_t ts, char*& cur, const void* src, int64_t ld, int64_t rows, int64_t cols, const void** dev,
+                         int64_t* ldd) {
+    *dev = src; *ldd = ld;
+    if (loc != COVGRAM_HOST || rows <= 0 || cols <= 0) return COVGRAM_OK;
+    CG_CHECK_HIP(hipMemcpy2DAsync(cur, (size_t)rows * ts, src, (size_t)ld * ts, (size_t)rows * ts, (size_t)cols, hipMemcpyHostToDevice, ctx->stream));
+    *dev = cur; *ldd = rows;
+    cur += staged_bytes(rows, cols, ts);
+    return COVGRAM_OK;
+}
 
 int check_pair(const covgram_ctx* ctx, const covgram_points* X, const covgram_points* Y);
 

@@ -10,7 +10,7 @@
 
 #include <rocblas/rocblas.h>
 
-#include "common.hpp"
+#include "driver.hpp"
 #include "kron_limits.hpp"
 
 namespace covgram {
@@ -226,53 +226,41 @@ int covgram_kron_mvm(covgram_ctx* ctx, const void* const* factors, const int64_t
         }
     }
     CG_DEVICE(ctx);
-    if (loc == COVGRAM_DEVICE) {   // a and y may overlap (include/covgram.h): the mode products read a private copy of a
-        int rc0 = unalias_input(ctx, &a, &lda, nin, nrhs, y, ldy, nout, ts);
-        if (rc0) return rc0;
-    }
-    // right-hand sides that lie one after the other are one more (slowest) tensor index; padded ones are packed first
-    const bool packed_a = (lda == nin) || nrhs == 1, packed_y = (ldy == nout) || nrhs == 1;
-    const bool host = (loc == COVGRAM_HOST);
-    // workspace: [bufA | bufB | staged a | staged y | staged factors]
+    Staged st;
+    int rc = st.begin(ctx, loc, ts, a, lda, nin, y, ldy, nout, nrhs, beta);
+    if (rc) return rc;
+    // right-hand sides that lie one after the other are one more (slowest) tensor index.  Staged packs them on HOST; DEVICE ones that are padded
+    // (ld > extent, several columns) are packed here and y unpacked below — device-to-device copies that Staged, whose DEVICE side hands the
+    // caller's arrays through, has no place for
+    const bool pack_a = st.lda != nin && nrhs > 1, pack_y = st.ldy != nout && nrhs > 1;
+    // workspace: [bufA | bufB | packed a | packed y | staged factors | multiplied-out pair of small trailing factors]
+    const size_t tens = staged_bytes(maxel, nrhs, ts), abytes = staged_bytes(nin, nrhs, ts), ybytes = staged_bytes(nout, nrhs, ts);
     size_t fbytes = 0;
-    if (host) for (int i = 0; i < q; ++i) fbytes += (((size_t)rows[i] * cols[i] * ts) + 15) & ~(size_t)15;
-    const size_t tens = (((size_t)maxel * nrhs * ts) + 255) & ~(size_t)255;
-    const size_t abytes = (((size_t)nin * nrhs * ts) + 255) & ~(size_t)255, ybytes = (((size_t)nout * nrhs * ts) + 255) & ~(size_t)255;
-    const bool stage_a = host || !packed_a, stage_y = host || !packed_y;
-    const size_t mbytes = (size_t)kron::MERGE_MAX_SIDE * kron::MERGE_MAX_SIDE * ts;      // the multiplied-out pair of small trailing factors
-    const size_t need = 2 * tens + (stage_a ? abytes : 0) + (stage_y ? ybytes : 0) + fbytes + mbytes + 1024;
-    void* w; int rc = ws_reserve(ctx, 1, need, &w); if (rc) return rc;
+    if (loc == COVGRAM_HOST) for (int i = 0; i < q; ++i) fbytes += staged_bytes(rows[i], cols[i], ts);
+    const size_t mbytes = (size_t)kron::MERGE_MAX_SIDE * kron::MERGE_MAX_SIDE * ts;
+    void* w; rc = ws_reserve(ctx, 1, 2 * tens + (pack_a ? abytes : 0) + (pack_y ? ybytes : 0) + fbytes + mbytes, &w); if (rc) return rc;
     char* base = (char*)w;
     void* bufA = base; void* bufB = base + tens;
     char* p = base + 2 * tens;
-    const void* a_dev = a; void* y_dev = y;
-    const void* fdev[16]; int64_t ldd[16];
-    for (int i = 0; i < q; ++i) { fdev[i] = factors[i]; ldd[i] = lds[i]; }
-    const hipMemcpyKind up = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-    if (stage_a) {
-        CG_CHECK_HIP(hipMemcpy2DAsync(p, (size_t)nin * ts, a, (size_t)lda * ts, (size_t)nin * ts, nrhs, up, ctx->stream));
+    const void* a_dev = st.a; void* y_dev = st.y;
+    if (pack_a) {
+        CG_CHECK_HIP(hipMemcpy2DAsync(p, (size_t)nin * ts, st.a, (size_t)st.lda * ts, (size_t)nin * ts, nrhs, hipMemcpyDeviceToDevice, ctx->stream));
         a_dev = p; p += abytes;
     }
-    if (stage_y) {
-        if (beta != 0.0) CG_CHECK_HIP(hipMemcpy2DAsync(p, (size_t)nout * ts, y, (size_t)ldy * ts, (size_t)nout * ts, nrhs, up, ctx->stream));
+    if (pack_y) {
+        if (beta != 0.0) CG_CHECK_HIP(hipMemcpy2DAsync(p, (size_t)nout * ts, st.y, (size_t)st.ldy * ts, (size_t)nout * ts, nrhs, hipMemcpyDeviceToDevice, ctx->stream));
         y_dev = p; p += ybytes;
     }
-    if (host) {
-        for (int i = 0; i < q; ++i) {
-            CG_CHECK_HIP(hipMemcpy2DAsync(p, (size_t)rows[i] * ts, factors[i], (size_t)lds[i] * ts, (size_t)rows[i] * ts, cols[i], hipMemcpyHostToDevice, ctx->stream));
-            fdev[i] = p; ldd[i] = rows[i]; p += (((size_t)rows[i] * cols[i] * ts) + 15) & ~(size_t)15;
-        }
-    }
-    void* merged = (void*)(((uintptr_t)p + 255) & ~(uintptr_t)255);
-    if (dtype == COVGRAM_F32) rc = kron::kron_run<float>(ctx, fdev, rows, cols, ldd, q, nrhs, (const float*)a_dev, (float*)y_dev, (float)alpha, (float)beta, (float*)bufA, (float*)bufB, (float*)merged);
-    else rc = kron::kron_run<double>(ctx, fdev, rows, cols, ldd, q, nrhs, (const double*)a_dev, (double*)y_dev, alpha, beta, (double*)bufA, (double*)bufB, (double*)merged);
+    const void* fdev[16]; int64_t ldd[16];
+    for (int i = 0; i < q; ++i) { rc = stage_operand(ctx, loc, ts, p, factors[i], lds[i], rows[i], cols[i], &fdev[i], &ldd[i]); if (rc) return rc; }
+    void* merged = p;
+    rc = by_dtype(dtype, [&](auto t0) {
+        using T = decltype(t0);
+        return kron::kron_run<T>(ctx, fdev, rows, cols, ldd, q, nrhs, (const T*)a_dev, (T*)y_dev, (T)alpha, (T)beta, (T*)bufA, (T*)bufB, (T*)merged);
+    });
     if (rc) return rc;
-    if (stage_y) {
-        const hipMemcpyKind down = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-        CG_CHECK_HIP(hipMemcpy2DAsync(y, (size_t)ldy * ts, y_dev, (size_t)nout * ts, (size_t)nout * ts, nrhs, down, ctx->stream));
-    }
-    if (host) CG_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    return COVGRAM_OK;
+    if (pack_y) CG_CHECK_HIP(hipMemcpy2DAsync(st.y, (size_t)st.ldy * ts, y_dev, (size_t)nout * ts, (size_t)nout * ts, nrhs, hipMemcpyDeviceToDevice, ctx->stream));
+    return st.finish();
 }
 
 }  // extern "C"

@@ -13,7 +13,9 @@
 // streaming passes over the point-major point sets themselves (dot_vta / dot_xz kernels), any d, any number of right-hand sides.
 #include <algorithm>
 
-#include "common.hpp"
+#include <type_traits>
+
+#include "driver.hpp"
 #include "pack.hpp"
 
 namespace covgram {
@@ -419,16 +421,15 @@ static int lowrank_mfma_run(covgram_ctx* ctx, const T* U, int64_t ldu, const T* 
     const int NJ = p <= TM ? 1 : (sizeof(T) == 8 && p > 2 * TM ? 4 : 2);
     const int NI = sizeof(T) == 4 ? (r <= 32 ? 1 : (r <= 64 ? 2 : 4)) : (r <= 32 ? 2 : 4);
     const dim3 grid((unsigned)nslab, (unsigned)((r + NI * TM - 1) / (NI * TM)), (unsigned)((p + NJ * TM - 1) / (NJ * TM)));
-#define CG_LRM(I, J) lrm_vta_launch<T, I, J>(ctx, aligned, grid, V, ldv, m, r, A, lda, p, zpart, per)
-    if constexpr (sizeof(T) == 4) {
-        if (NJ == 1) { if (NI == 1) CG_LRM(1, 1); else if (NI == 2) CG_LRM(2, 1); else CG_LRM(4, 1); }
-        else { if (NI == 1) CG_LRM(1, 2); else if (NI == 2) CG_LRM(2, 2); else CG_LRM(4, 2); }
-    } else {
-        if (NJ == 1) { if (NI == 2) CG_LRM(2, 1); else CG_LRM(4, 1); }
-        else if (NJ == 2) { if (NI == 2) CG_LRM(2, 2); else CG_LRM(4, 2); }
-        else { if (NI == 2) CG_LRM(2, 4); else CG_LRM(4, 4); }
-    }
-#undef CG_LRM
+    auto vta = [&](auto ni, auto nj) { lrm_vta_launch<T, decltype(ni)::value, decltype(nj)::value>(ctx, aligned, grid, V, ldv, m, r, A, lda, p, zpart, per); };
+    auto with_ni = [&](auto nj) {                                 // NI: fp32 1 / 2 / 4, fp64 2 / 4
+        using std::integral_constant;
+        if constexpr (sizeof(T) == 4) { if (NI == 1) return vta(integral_constant<int, 1>{}, nj); }
+        if (NI == 2) vta(integral_constant<int, 2>{}, nj); else vta(integral_constant<int, 4>{}, nj);
+    };
+    if (NJ == 1) with_ni(std::integral_constant<int, 1>{});
+    else if (NJ == 2) with_ni(std::integral_constant<int, 2>{});
+    else if constexpr (sizeof(T) == 8) with_ni(std::integral_constant<int, 4>{});
     const int64_t rp = r * (int64_t)p;
     hipLaunchKernelGGL(lowrank_zsum_kernel<T>, dim3((unsigned)((rp + 31) / 32)), dim3(256), 0, ctx->stream, (const T*)zpart, nslab, rp, Z);
     // second product: Z block in LDS (<= 64 KB), row stride odd (fp32) / = 2 mod 32 (fp64) and >= r rounded up to the MFMA's K
@@ -700,17 +701,33 @@ static int dot_factored_run(covgram_ctx* ctx, const covgram_points* X, const cov
         unsigned* ticket = nullptr;
         rc = tickets_reserve(ctx, 1, &ticket);
         if (rc) return rc;
-#define CG_DOTG(GV) do { if (grp && vecY && G == GV) { hipLaunchKernelGGL((dot_vtag_kernel<T, GV>), dim3((unsigned)nslab), dim3(256), 0, ctx->stream, (const T*)Y->dptr, m, a, zpart, per, ticket, z); ydone = true; } } while (0)
-#define CG_DOT1(DCV) do { if (vecY) hipLaunchKernelGGL((dot_vta1_kernel<T, DCV, true>), dim3((unsigned)nslab), dim3(256), 0, ctx->stream, (const T*)Y->dptr, m, d, a, zpart, per, ticket, z); \
-                          else hipLaunchKernelGGL((dot_vta1_kernel<T, DCV, false>), dim3((unsigned)nslab), dim3(256), 0, ctx->stream, (const T*)Y->dptr, m, d, a, zpart, per, ticket, z); } while (0)
-        bool ydone = false;
-        CG_DOTG(2); CG_DOTG(4); CG_DOTG(8); CG_DOTG(16); CG_DOTG(32);
-        if (!ydone) { if (d <= 4) CG_DOT1(4); else if (d <= 8) CG_DOT1(8); else CG_DOT1(16); }
-#undef CG_DOT1
-#undef CG_DOTG
-#define CG_XZG(GV) do { if (grp && vecX && G == GV) { hipLaunchKernelGGL((dot_xzg_kernel<T, GV>), dim3((unsigned)((n + (256 / GV) * 8 - 1) / ((256 / GV) * 8))), dim3(256), 0, ctx->stream, (const T*)X->dptr, n, (const T*)z, y, alpha, beta); xdone = true; } } while (0)
-        CG_XZG(2); CG_XZG(4); CG_XZG(8); CG_XZG(16); CG_XZG(32);
-#undef CG_XZG
+        using std::integral_constant;
+        const T* Yp = (const T*)Y->dptr;
+        // the lane-group kernels (G = 2 .. 32 lanes per row) where they apply, one launch of f(G) for the G of this d
+        auto by_group = [&](bool applies, auto f) {
+            bool done = false;
+            auto at = [&](auto g) { if (applies && G == decltype(g)::value) { f(g); done = true; } };
+            at(integral_constant<int, 2>{}); at(integral_constant<int, 4>{}); at(integral_constant<int, 8>{});
+            at(integral_constant<int, 16>{}); at(integral_constant<int, 32>{});
+            return done;
+        };
+        const bool ydone = by_group(grp && vecY, [&](auto g) {
+            hipLaunchKernelGGL((dot_vtag_kernel<T, decltype(g)::value>), dim3((unsigned)nslab), dim3(256), 0, ctx->stream, Yp, m, a, zpart, per, ticket, z);
+        });
+        if (!ydone) {
+            auto vta1 = [&](auto dc) {
+                by_bool(vecY, [&](auto vec) {
+                    hipLaunchKernelGGL((dot_vta1_kernel<T, decltype(dc)::value, decltype(vec)::value>), dim3((unsigned)nslab), dim3(256), 0, ctx->stream, Yp, m, d, a,
+                                       zpart, per, ticket, z);
+                });
+            };
+            if (d <= 4) vta1(integral_constant<int, 4>{}); else if (d <= 8) vta1(integral_constant<int, 8>{}); else vta1(integral_constant<int, 16>{});
+        }
+        xdone = by_group(grp && vecX, [&](auto g) {
+            constexpr int GV = decltype(g)::value;
+            hipLaunchKernelGGL((dot_xzg_kernel<T, GV>), dim3((unsigned)((n + (256 / GV) * 8 - 1) / ((256 / GV) * 8))), dim3(256), 0, ctx->stream, (const T*)X->dptr, n,
+                               (const T*)z, y, alpha, beta);
+        });
     } else {
         hipLaunchKernelGGL(dot_vta_kernel<T>, dim3((unsigned)nslab), dim3(256), 0, ctx->stream, (const T*)Y->dptr, m, d, a, lda, nrhs, zpart, per);
         hipLaunchKernelGGL(lowrank_zsum_kernel<T>, dim3((unsigned)((dq + 31) / 32)), dim3(256), 0, ctx->stream, (const T*)zpart, nslab, dq, z);
@@ -727,8 +744,10 @@ static int dot_factored_run(covgram_ctx* ctx, const covgram_points* X, const cov
 int mvm_dot_factored(covgram_ctx* ctx, const HostKernel& hk, const covgram_points* X, const covgram_points* Y, const void* a, int64_t lda, void* y,
                      int64_t ldy, int32_t nrhs, double alpha, double beta) {
     const double al = alpha * hk.kp.scale;
-    if (X->dtype == COVGRAM_F32) return dot_factored_run<float>(ctx, X, Y, (const float*)a, lda, (float*)y, ldy, nrhs, (float)al, (float)beta);
-    return dot_factored_run<double>(ctx, X, Y, (const double*)a, lda, (double*)y, ldy, nrhs, al, beta);
+    return by_dtype(X->dtype, [&](auto t0) {
+        using T = decltype(t0);
+        return dot_factored_run<T>(ctx, X, Y, (const T*)a, lda, (T*)y, ldy, nrhs, (T)al, (T)beta);
+    });
 }
 
 }  // namespace covgram
@@ -748,11 +767,10 @@ int covgram_lowrank_mvm(covgram_ctx* ctx, const void* U, int64_t ldu, const void
     CG_REQUIRE(r <= 8192, COVGRAM_EUNSUPPORTED, "lowrank: r = %lld exceeds 8192", (long long)r);
     const size_t ts = dtype_size(dtype);
     CG_DEVICE(ctx);
-    if (loc == COVGRAM_DEVICE) {   // a and y may overlap (include/covgram.h): both passes read a private copy of a
-        int rc0 = unalias_input(ctx, &a, &lda, m, nrhs, y, ldy, n, ts);
-        if (rc0) return rc0;
-    }
-    const bool mfma = nrhs >= 8 && (dtype == COVGRAM_F32 ? lowrank_mfma_fits<float>(r) : lowrank_mfma_fits<double>(r));
+    Staged st;
+    int rc = st.begin(ctx, loc, ts, a, lda, m, y, ldy, n, nrhs, beta);
+    if (rc) return rc;
+    const bool mfma = nrhs >= 8 && by_dtype(dtype, [&](auto t0) { return lowrank_mfma_fits<decltype(t0)>(r); });
     const int pz = mfma ? nrhs : 1;                              // columns of Z held at once
     // row slabs of V: ~4 workgroups per CU (GEMV form: ~2, i.e. at least two sweeps per slab at n = 2^20 — a slab of ONE sweep spends as long in
     // its 32-column LDS reduction as on its loads: 28.4 us at 4.7 TB/s for 134 MB), slab length a multiple of one sweep of the block (256 threads x 16 bytes)
@@ -761,46 +779,32 @@ int covgram_lowrank_mvm(covgram_ctx* ctx, const void* U, int64_t ldu, const void
     int64_t per = (m + (int64_t)ctx->num_cus * wg_per_cu - 1) / ((int64_t)ctx->num_cus * wg_per_cu);
     per = std::max<int64_t>(sweep, ((per + sweep - 1) / sweep) * sweep);
     const int64_t nslab = (m + per - 1) / per;
-    size_t need = ((size_t)nslab * r * pz + (size_t)r * pz) * ts + 512;
-    if (loc == COVGRAM_HOST) need += ((size_t)n * r + (size_t)m * r + ((size_t)m + n) * nrhs) * ts + 64;
-    void* w; int rc = ws_reserve(ctx, 1, need, &w); if (rc) return rc;
+    // workspace slot 1: [zpart | z | HOST: packed U | packed V]
+    const size_t zpb = staged_bytes(nslab * r, pz, ts), zb = staged_bytes(r, pz, ts);
+    void* w; rc = ws_reserve(ctx, 1, zpb + zb + (loc == COVGRAM_HOST ? staged_bytes(n, r, ts) + staged_bytes(m, r, ts) : 0), &w); if (rc) return rc;
     char* p = (char*)w;
-    void* zpart = p; p += (((size_t)nslab * r * pz * ts) + 255) & ~(size_t)255;
-    void* z = p; p += (((size_t)r * pz * ts) + 255) & ~(size_t)255;
-    const void *Ud = U, *Vd = V, *ad = a; void* yd = y; int64_t ldud = ldu, ldvd = ldv, ldad = lda, ldyd = ldy;
-    if (loc == COVGRAM_HOST) {
-        CG_CHECK_HIP(hipMemcpy2DAsync(p, (size_t)n * ts, U, (size_t)ldu * ts, (size_t)n * ts, r, hipMemcpyHostToDevice, ctx->stream)); Ud = p; ldud = n; p += (size_t)n * r * ts;
-        CG_CHECK_HIP(hipMemcpy2DAsync(p, (size_t)m * ts, V, (size_t)ldv * ts, (size_t)m * ts, r, hipMemcpyHostToDevice, ctx->stream)); Vd = p; ldvd = m; p += (size_t)m * r * ts;
-        CG_CHECK_HIP(hipMemcpy2DAsync(p, (size_t)m * ts, a, (size_t)lda * ts, (size_t)m * ts, nrhs, hipMemcpyHostToDevice, ctx->stream)); ad = p; ldad = m; p += (size_t)m * nrhs * ts;
-        if (beta != 0.0) CG_CHECK_HIP(hipMemcpy2DAsync(p, (size_t)n * ts, y, (size_t)ldy * ts, (size_t)n * ts, nrhs, hipMemcpyHostToDevice, ctx->stream));
-        yd = p; ldyd = n;
-    }
-    if (mfma) {
-        if (dtype == COVGRAM_F32)
-            rc = lowrank_mfma_run<float>(ctx, (const float*)Ud, ldud, (const float*)Vd, ldvd, n, m, r, (const float*)ad, ldad, (float*)yd, ldyd, nrhs,
-                                         (float)alpha, (float)beta, (float*)zpart, (float*)z, nslab, per);
-        else
-            rc = lowrank_mfma_run<double>(ctx, (const double*)Ud, ldud, (const double*)Vd, ldvd, n, m, r, (const double*)ad, ldad, (double*)yd, ldyd,
-                                          nrhs, alpha, beta, (double*)zpart, (double*)z, nslab, per);
-        if (rc) return rc;
-    } else {
-        // small r: the last slab's workgroup sums the partials inside lowrank_vta_kernel (one counter, zero between launches); a long z keeps
-        // the separate one-workgroup-per-32-columns kernel
-        unsigned* ticket = nullptr;
-        if (r <= 128) { rc = tickets_reserve(ctx, 1, &ticket); if (rc) return rc; }
-        for (int c = 0; c < nrhs; ++c) {                         // GEMV pair per column
-            const char* ac = (const char*)ad + (size_t)c * ldad * ts;
-            char* yc = (char*)yd + (size_t)c * ldyd * ts;
-            if (dtype == COVGRAM_F32) lowrank_run<float>(ctx, Ud, ldud, Vd, ldvd, n, m, r, ac, yc, alpha, beta, zpart, z, nslab, per, ticket);
-            else lowrank_run<double>(ctx, Ud, ldud, Vd, ldvd, n, m, r, ac, yc, alpha, beta, zpart, z, nslab, per, ticket);
-        }
-    }
+    void* zpart = p; p += zpb;
+    void* z = p; p += zb;
+    const void *Ud, *Vd; int64_t ldud, ldvd;
+    rc = stage_operand(ctx, loc, ts, p, U, ldu, n, r, &Ud, &ldud); if (rc) return rc;
+    rc = stage_operand(ctx, loc, ts, p, V, ldv, m, r, &Vd, &ldvd); if (rc) return rc;
+    // small r, GEMV form: the last slab's workgroup sums the partials inside lowrank_vta_kernel (one counter, zero between launches); a long z
+    // keeps the separate one-workgroup-per-32-columns kernel
+    unsigned* ticket = nullptr;
+    if (!mfma && r <= 128) { rc = tickets_reserve(ctx, 1, &ticket); if (rc) return rc; }
+    rc = by_dtype(dtype, [&](auto t0) -> int {
+        using T = decltype(t0);
+        if (mfma)
+            return lowrank_mfma_run<T>(ctx, (const T*)Ud, ldud, (const T*)Vd, ldvd, n, m, r, (const T*)st.a, st.lda, (T*)st.y, st.ldy, nrhs, (T)alpha, (T)beta,
+                                       (T*)zpart, (T*)z, nslab, per);
+        for (int c = 0; c < nrhs; ++c)                           // GEMV pair per column
+            lowrank_run<T>(ctx, Ud, ldud, Vd, ldvd, n, m, r, (const T*)st.a + (size_t)c * st.lda, (T*)st.y + (size_t)c * st.ldy, alpha, beta, zpart, z, nslab, per,
+                           ticket);
+        return COVGRAM_OK;
+    });
+    if (rc) return rc;
     CG_CHECK_HIP(hipGetLastError());
-    if (loc == COVGRAM_HOST) {
-        CG_CHECK_HIP(hipMemcpy2DAsync(y, (size_t)ldy * ts, yd, (size_t)n * ts, (size_t)n * ts, nrhs, hipMemcpyDeviceToHost, ctx->stream));
-        CG_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return COVGRAM_OK;
+    return st.finish();
 }
 
 }  // extern "C"

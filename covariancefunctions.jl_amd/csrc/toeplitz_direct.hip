@@ -19,7 +19,7 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "common.hpp"
+#include "driver.hpp"
 
 namespace covgram {
 
@@ -320,30 +320,25 @@ using namespace covgram;
 
 extern "C" {
 
-// staging helper: device copies of host inputs in workspace slot 1 (layout decided by the caller)
-static int stage_in(covgram_ctx* ctx, char*& p, const void* src, size_t bytes, int32_t loc, const void** dev) {
-    if (loc == COVGRAM_DEVICE) { *dev = src; return COVGRAM_OK; }
-    CG_CHECK_HIP(hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-    *dev = p; p += (bytes + 255) & ~(size_t)255;
-    return COVGRAM_OK;
-}
+// Staging of the three solvers: the recursion's workspace vectors and the HOST copies of r and b share workspace slot 1 (stage_operand), the
+// result goes through Staged::begin_tile (a vector is a tile of one column; Trench's matrix is the packed tile itself).
 
 int covgram_toeplitz_durbin(covgram_ctx* ctx, const void* r, int64_t n, void* y, int32_t dtype, int32_t loc) {
     CG_REQUIRE(ctx && r && y, COVGRAM_EINVAL, "NULL argument");
     CG_REQUIRE(n >= 1, COVGRAM_EINVAL, "durbin: need n >= 1");
     CG_REQUIRE(n <= COVGRAM_TOEPLITZ_DIRECT_MAX_N, COVGRAM_EUNSUPPORTED, "durbin: n = %lld is above the direct solvers' cap of %d (one uninterruptible launch of n - 1 dependent O(n) steps): use the preconditioned CG over the FFT MVM", (long long)n, COVGRAM_TOEPLITZ_DIRECT_MAX_N);
     CG_REQUIRE(dtype == COVGRAM_F32 || dtype == COVGRAM_F64, COVGRAM_EINVAL, "unknown dtype %d", dtype);
-    const size_t ts = dtype_size(dtype), vb = ((size_t)n * ts + 255) & ~(size_t)255;
+    const size_t ts = dtype_size(dtype);
     CG_DEVICE(ctx);
-    void* w; int rc = ws_reserve(ctx, 1, 2 * vb + 512, &w); if (rc) return rc;
+    void* w; int rc = ws_reserve(ctx, 1, staged_bytes(n, 1, ts), &w); if (rc) return rc;
     char* p = (char*)w;
-    const void* rd; rc = stage_in(ctx, p, r, (size_t)n * ts, loc, &rd); if (rc) return rc;
-    void* yd = loc == COVGRAM_DEVICE ? y : (void*)p;
-    if (dtype == COVGRAM_F32) durbin_run<float>(ctx, (const float*)rd, n, (float*)yd);
-    else durbin_run<double>(ctx, (const double*)rd, n, (double*)yd);
+    const void* rd; int64_t ld;
+    rc = stage_operand(ctx, loc, ts, p, r, n, n, 1, &rd, &ld); if (rc) return rc;
+    Staged out;
+    rc = out.begin_tile(ctx, loc, ts, y, n, n, 1); if (rc) return rc;
+    by_dtype(dtype, [&](auto t0) { using T = decltype(t0); durbin_run<T>(ctx, (const T*)rd, n, (T*)out.y); });
     CG_CHECK_HIP(hipGetLastError());
-    if (loc == COVGRAM_HOST) { CG_CHECK_HIP(hipMemcpyAsync(y, yd, (size_t)n * ts, hipMemcpyDeviceToHost, ctx->stream)); CG_CHECK_HIP(hipStreamSynchronize(ctx->stream)); }
-    return COVGRAM_OK;
+    return out.finish();
 }
 
 int covgram_toeplitz_levinson(covgram_ctx* ctx, const void* r, const void* b, int64_t n, void* x, int32_t dtype, int32_t loc) {
@@ -351,29 +346,27 @@ int covgram_toeplitz_levinson(covgram_ctx* ctx, const void* r, const void* b, in
     CG_REQUIRE(n >= 1, COVGRAM_EINVAL, "levinson: need n >= 1");
     CG_REQUIRE(n <= COVGRAM_TOEPLITZ_DIRECT_MAX_N, COVGRAM_EUNSUPPORTED, "levinson: n = %lld is above the direct solvers' cap of %d (one uninterruptible launch of n - 1 dependent O(n) steps): use the preconditioned CG over the FFT MVM", (long long)n, COVGRAM_TOEPLITZ_DIRECT_MAX_N);
     CG_REQUIRE(dtype == COVGRAM_F32 || dtype == COVGRAM_F64, COVGRAM_EINVAL, "unknown dtype %d", dtype);
-    const size_t ts = dtype_size(dtype), vb = ((size_t)n * ts + 255) & ~(size_t)255;
+    const size_t ts = dtype_size(dtype);
     CG_DEVICE(ctx);
-    void* w; int rc = ws_reserve(ctx, 1, 4 * vb + 512, &w); if (rc) return rc;
-    char* p = (char*)w;
-    void* yw = p; p += vb;                                         // the recursion's y (workspace)
     if (n == 1) {                                                  // K = [1]
         if (loc == COVGRAM_HOST) memcpy(x, b, ts); else CG_CHECK_HIP(hipMemcpyAsync(x, b, ts, hipMemcpyDeviceToDevice, ctx->stream));
         return COVGRAM_OK;
     }
-    const void *rd, *bd;
-    rc = stage_in(ctx, p, r, (size_t)(n - 1) * ts, loc, &rd); if (rc) return rc;
-    rc = stage_in(ctx, p, b, (size_t)n * ts, loc, &bd); if (rc) return rc;
-    void* xd = loc == COVGRAM_DEVICE ? x : (void*)p;
-#define CG_LEVINSON(T)                                                                                                                \
-    {                                                                                                                                  \
-        if (n <= LR_MAX_N) levinson_reg_launch<T, true>(ctx->stream, (const T*)rd, (const T*)bd, (T*)xd, (T*)yw, n);                  \
-        else hipLaunchKernelGGL((levinson_kernel<T, true>), dim3(1), dim3(LV_THREADS), 0, ctx->stream, (const T*)rd, (const T*)bd, (T*)xd, (T*)yw, n); \
-    }
-    if (dtype == COVGRAM_F32) CG_LEVINSON(float) else CG_LEVINSON(double)
-#undef CG_LEVINSON
+    void* w; int rc = ws_reserve(ctx, 1, 3 * staged_bytes(n, 1, ts), &w); if (rc) return rc;
+    char* p = (char*)w;
+    void* yw = p; p += staged_bytes(n, 1, ts);                     // the recursion's y (workspace)
+    const void *rd, *bd; int64_t ld;
+    rc = stage_operand(ctx, loc, ts, p, r, n - 1, n - 1, 1, &rd, &ld); if (rc) return rc;
+    rc = stage_operand(ctx, loc, ts, p, b, n, n, 1, &bd, &ld); if (rc) return rc;
+    Staged out;
+    rc = out.begin_tile(ctx, loc, ts, x, n, n, 1); if (rc) return rc;
+    by_dtype(dtype, [&](auto t0) {
+        using T = decltype(t0);
+        if (n <= LR_MAX_N) levinson_reg_launch<T, true>(ctx->stream, (const T*)rd, (const T*)bd, (T*)out.y, (T*)yw, n);
+        else hipLaunchKernelGGL((levinson_kernel<T, true>), dim3(1), dim3(LV_THREADS), 0, ctx->stream, (const T*)rd, (const T*)bd, (T*)out.y, (T*)yw, n);
+    });
     CG_CHECK_HIP(hipGetLastError());
-    if (loc == COVGRAM_HOST) { CG_CHECK_HIP(hipMemcpyAsync(x, xd, (size_t)n * ts, hipMemcpyDeviceToHost, ctx->stream)); CG_CHECK_HIP(hipStreamSynchronize(ctx->stream)); }
-    return COVGRAM_OK;
+    return out.finish();
 }
 
 int covgram_toeplitz_trench(covgram_ctx* ctx, const void* r, int64_t n, void* B, int64_t ldb, int32_t dtype, int32_t loc) {
@@ -381,40 +374,35 @@ int covgram_toeplitz_trench(covgram_ctx* ctx, const void* r, int64_t n, void* B,
     CG_REQUIRE(n >= 1 && ldb >= n, COVGRAM_EINVAL, "trench: need n >= 1 and ldb >= n");
     CG_REQUIRE(n <= COVGRAM_TOEPLITZ_DIRECT_MAX_N, COVGRAM_EUNSUPPORTED, "trench: n = %lld is above the direct solvers' cap of %d", (long long)n, COVGRAM_TOEPLITZ_DIRECT_MAX_N);
     CG_REQUIRE(dtype == COVGRAM_F32 || dtype == COVGRAM_F64, COVGRAM_EINVAL, "unknown dtype %d", dtype);
-    const size_t ts = dtype_size(dtype), vb = ((size_t)n * ts + 255) & ~(size_t)255;
+    const size_t ts = dtype_size(dtype), vb = staged_bytes(n, 1, ts);
     CG_DEVICE(ctx);
-    const size_t mat = loc == COVGRAM_HOST ? (size_t)n * n * ts : 0;
-    void* w; int rc = ws_reserve(ctx, 1, 4 * vb + mat + 1024, &w); if (rc) return rc;
+    void* w; int rc = ws_reserve(ctx, 1, 3 * vb + 256, &w); if (rc) return rc;
     char* p = (char*)w;
     void* yw = p; p += vb;
     void* nu = p; p += vb;
     void* gam = p; p += 256;
-    void* Bd = B; int64_t ld = ldb;
-    const void* rd = nullptr;
-    if (n > 1) { rc = stage_in(ctx, p, r, (size_t)(n - 1) * ts, loc, &rd); if (rc) return rc; }
-    if (loc == COVGRAM_HOST) { Bd = p; ld = n; }
+    const void* rd = nullptr; int64_t ld;
+    if (n > 1) { rc = stage_operand(ctx, loc, ts, p, r, n - 1, n - 1, 1, &rd, &ld); if (rc) return rc; }
+    Staged out;
+    rc = out.begin_tile(ctx, loc, ts, B, ldb, n, n); if (rc) return rc;
     const unsigned gd = (unsigned)((n + 255) / 256), gt = (unsigned)((n + 31) / 32);
-#define CG_TRENCH(T)                                                                                                                   \
-    {                                                                                                                                  \
-        if (n > 1) {                                                                                                                   \
-            durbin_run<T>(ctx, (const T*)rd, n - 1, (T*)yw);                                                                           \
-            hipLaunchKernelGGL(trench_head_kernel<T>, dim3(1), dim3(LV_THREADS), 0, ctx->stream, (const T*)rd, (const T*)yw, n - 1, (T*)nu, (T*)gam); \
-        } else {                                                                                                                       \
-            const T one = (T)1;                                                                                                        \
-            CG_CHECK_HIP(hipMemcpyAsync(gam, &one, sizeof(T), hipMemcpyHostToDevice, ctx->stream));                                    \
-            CG_CHECK_HIP(hipStreamSynchronize(ctx->stream));                                                                           \
-        }                                                                                                                              \
-        hipLaunchKernelGGL(trench_diag_kernel<T>, dim3(gd), dim3(256), 0, ctx->stream, (const T*)yw, (const T*)nu, (const T*)gam, n, (T*)Bd, ld); \
-        hipLaunchKernelGGL(mirror_lower_kernel<T>, dim3(gt, gt), dim3(256), 0, ctx->stream, (T*)Bd, n, ld);                            \
-    }
-    if (dtype == COVGRAM_F32) CG_TRENCH(float) else CG_TRENCH(double)
-#undef CG_TRENCH
+    rc = by_dtype(dtype, [&](auto t0) -> int {
+        using T = decltype(t0);
+        if (n > 1) {
+            durbin_run<T>(ctx, (const T*)rd, n - 1, (T*)yw);
+            hipLaunchKernelGGL(trench_head_kernel<T>, dim3(1), dim3(LV_THREADS), 0, ctx->stream, (const T*)rd, (const T*)yw, n - 1, (T*)nu, (T*)gam);
+        } else {
+            const T one = (T)1;
+            CG_CHECK_HIP(hipMemcpyAsync(gam, &one, sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+            CG_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+        }
+        hipLaunchKernelGGL(trench_diag_kernel<T>, dim3(gd), dim3(256), 0, ctx->stream, (const T*)yw, (const T*)nu, (const T*)gam, n, (T*)out.y, out.ldy);
+        hipLaunchKernelGGL(mirror_lower_kernel<T>, dim3(gt, gt), dim3(256), 0, ctx->stream, (T*)out.y, n, out.ldy);
+        return COVGRAM_OK;
+    });
+    if (rc) return rc;
     CG_CHECK_HIP(hipGetLastError());
-    if (loc == COVGRAM_HOST) {
-        CG_CHECK_HIP(hipMemcpy2DAsync(B, (size_t)ldb * ts, Bd, (size_t)n * ts, (size_t)n * ts, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-        CG_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return COVGRAM_OK;
+    return out.finish();
 }
 
 }  // extern "C"

@@ -345,14 +345,33 @@ def _staged_entry_points(cg, ctx, dt):
             return back(1), Y0, rows_y
         return run
 
-    def tile_like(call, rows, cols, seed):
+    def tile_like(call, rows, cols, seed, inputs=(), pad=3):
+        """call(po, ldo, loc, *inputs as pointers of loc): a rows x cols output in a prefilled column-major buffer of leading dimension rows + pad"""
         def run(loc, inplace):
-            ldo = rows + 3
+            ldo = rows + pad
             O = np.random.default_rng(seed).standard_normal((cols, ldo)).astype(dt)
             O0 = O.copy()
-            (po,), back = buffers(loc, [O])
-            f.check(call(po, ldo, loc))
+            (po, *pin), back = buffers(loc, [O] + list(inputs))
+            f.check(call(po, ldo, loc, *pin))
             return back(0), O0, rows
+        return run
+
+    def op_like(call, rows_a, rows_y, seed, nrhs=1, pad=(5, 3), operands=lambda r: ()):
+        """A structured operator, y <- alpha G a + beta y: call(pa, lda, py, ldy, loc, *operands as pointers of loc).  a and y are padded (lda = rows_a +
+        pad[0], ldy = rows_y + pad[1]); operands(rng) are the operator's own arrays (first column, factors, U and V, a diagonal), packed: HOST packs
+        them anyway, so both calls hand the kernels the same leading dimensions.  inplace (rows_a == rows_y): y is a."""
+        def run(loc, inplace):
+            r = np.random.default_rng(seed)
+            ops = [np.ascontiguousarray(o, dtype=dt) for o in operands(r)]
+            lda, ldy = rows_a + pad[0], rows_y + pad[1]
+            if inplace:
+                lda = ldy
+            A = r.standard_normal((nrhs, lda)).astype(dt); Yv = r.standard_normal((nrhs, ldy)).astype(dt)
+            Y0 = Yv.copy()
+            own = [Yv] if inplace else [A, Yv]
+            ptrs, back = buffers(loc, own + ops)
+            f.check(call(ptrs[0], lda, ptrs[len(own) - 1], ldy, loc, *ptrs[len(own):]))
+            return back(len(own) - 1), Y0, rows_y
         return run
 
     d = _SD
@@ -378,7 +397,103 @@ def _staged_entry_points(cg, ctx, dt):
             lambda po, ldo, loc, kind=kind: lib.covgram_block_matrix(ctx, kind, kp, hx, hy, po, ldo, loc), _SN * B, _SM * B, 35))
     eps["covgram_sm_matrix"] = (False, tile_like(lambda po, ldo, loc: lib.covgram_sm_matrix(hsm, hx, hy, po, ldo, loc), _SN, _SM, 36))
 
+    # ---- the structured operators: the smallest shapes that reach every branch of their drivers ----
+    # Toeplitz (n, m, symmetric, circulant, beta): rocFFT path; four-step path without a fused row kernel (N = 2^15, M' = 16); fused radix-4 row
+    # kernel (N = 2^17, M' = 64); radix-16 row kernel (N = 2^22, M' = 4096: fp64 runs its persistent grid, fp32 one pair per workgroup) with a real
+    # and a complex spectrum; circulant.  A case has one handle per loc, created from pointers of that loc by the first run that needs it; they live
+    # until close(), so that rocFFT is set up once (covgram_toeplitz_destroy of the last live handle tears it down: half a second per cycle).
+    htz = []
+    def toeplitz(n, m, sym, circ, beta):
+        handles = {}
+        def call(pa, lda, py, ldy, loc, pvc, pvr=None):
+            if loc not in handles:
+                handles[loc] = f._P()
+                f.check(lib.covgram_toeplitz_create(ctx, C.byref(handles[loc]), pvc, pvr, n, m, code, loc, int(circ)))
+                htz.append(handles[loc])
+            return lib.covgram_toeplitz_mvm(handles[loc], pa, py, -0.7, beta, loc)
+        def operands(r):
+            vc, vr = r.standard_normal(n), r.standard_normal(m)
+            vr[0] = vc[0]
+            return (vc,) if sym or circ else (vc, vr)
+        return (n == m, op_like(call, m, n, 41, pad=(0, 0), operands=operands))
+    for tag, n, m, sym, circ, beta in (("rocfft", 300, 200, False, False, 1.3), ("fourstep", 9000, 9000, False, False, 0.0),
+                                       ("row4", 33000, 33000, False, False, 1.3), ("row16:symmetric", 1 << 21, 1 << 21, True, False, 1.3),
+                                       ("row16", 1 << 21, 1 << 21, False, False, 0.0), ("circulant", 33, 33, False, True, 1.3)):
+        eps["covgram_toeplitz_mvm:" + tag] = toeplitz(n, m, sym, circ, beta)
+
+    # Kronecker: three small factors at nrhs = 1 and at nrhs = 3 with padded a and y (packed on the device), and a factor with a side of 1024
+    def kron(shapes, nrhs, pad):
+        q = len(shapes)
+        rows = (C.c_int64 * q)(*[sh[0] for sh in shapes]); cols = (C.c_int64 * q)(*[sh[1] for sh in shapes])
+        nin, nout = int(np.prod([sh[1] for sh in shapes])), int(np.prod([sh[0] for sh in shapes]))
+        def call(pa, lda, py, ldy, loc, *pf):
+            return lib.covgram_kron_mvm(ctx, (f._P * q)(*pf), rows, cols, rows, q, code, pa, lda, py, ldy, nrhs, -0.7, 1.3, loc)
+        return (False, op_like(call, nin, nout, 42, nrhs=nrhs, pad=pad, operands=lambda r: [r.standard_normal((sh[1], sh[0])) for sh in shapes]))
+    eps["covgram_kron_mvm:small"] = kron([(3, 5), (4, 2), (2, 6)], 1, (0, 0))
+    eps["covgram_kron_mvm:small:nrhs3"] = kron([(3, 5), (4, 2), (2, 6)], 3, (5, 3))
+    eps["covgram_kron_mvm:side1024"] = kron([(1024, 8), (8, 8)], 1, (0, 0))
+
+    # low rank U V' (n = m = 300): the ticketed z sum (r <= 128), the separate z-sum kernel, the matrix-core form (nrhs >= 8; lda a multiple of the
+    # vector width in both calls: one kernel instance)
+    def lowrank(r_, nrhs, pad):
+        n = m = 300
+        def call(pa, lda, py, ldy, loc, pu, pv):
+            return lib.covgram_lowrank_mvm(ctx, pu, n, pv, m, n, m, r_, code, pa, lda, py, ldy, nrhs, -0.7, 1.3, loc)
+        return (True, op_like(call, m, n, 43, nrhs=nrhs, pad=pad, operands=lambda r: (r.standard_normal((r_, n)), r.standard_normal((r_, m)))))
+    for r_, nrhs, ldt, pad in ((5, 1, np.float64, (5, 3)), (300, 1, np.float64, (5, 3)), (16, 8, np.float32, (8, 3))):
+        if dt == ldt:
+            eps["covgram_lowrank_mvm:r%d:nrhs%d" % (r_, nrhs)] = lowrank(r_, nrhs, pad)
+
+    # Barnes-Hut: fp64 on gramian(k, x), n = 300 (leafsize 16: several levels), without a diagonal and with one of length 1 and n; fp32 rectangular,
+    # d = 2; no rows at all.  Both products, each in both of its forms.
+    hbh = []
+    def barneshut(hr, hc, n, m, diag_len):
+        h = f._P()
+        f.check(lib.covgram_bh_create(ctx, C.byref(h), kp, hr, hc, 0.5, 16))
+        hbh.append(h)
+        def entry(fn, flag):
+            def call(pa, lda, py, ldy, loc, pd=None):
+                return fn(h, pa, py, -0.7, 1.3, -1.0, flag, pd, diag_len, loc)
+            return (n == m, op_like(call, m, n, 44, pad=(0, 0), operands=lambda r: (0.5 + r.random(diag_len),) if diag_len else ()))
+        return {"%s:%s%d" % (name, what, flag): entry(fn, flag) for name, fn, what in (
+            ("covgram_bh_mvm", lib.covgram_bh_mvm, "split"), ("covgram_bh_taylor_mvm", lib.covgram_bh_taylor_mvm, "use_com")) for flag in (0, 1)}
+    bh_cases = []
+    if dt == np.float64:
+        X3 = rng.standard_normal((300, _SD)).astype(dt)
+        h3 = make_points(cg, ctx, X3)
+        keep.append(X3); hbh_points = [h3]
+        bh_cases += [(":diag%d" % dl, h3, h3, 300, 300, dl) for dl in (0, 1, 300)]
+    else:
+        X2 = rng.standard_normal((_SN, 2)).astype(dt); Y2 = rng.standard_normal((_SM, 2)).astype(dt)
+        hx2, hy2 = make_points(cg, ctx, X2), make_points(cg, ctx, Y2)
+        keep += [X2, Y2]; hbh_points = [hx2, hy2]
+        bh_cases.append((":d2", hx2, hy2, _SN, _SM, 0))
+    h0 = make_points(cg, ctx, np.zeros((0, _SD), dtype=dt))
+    hbh_points.append(h0)
+    bh_cases.append((":norows", h0, hy, 0, _SM, 0))
+    for tag, hr, hc, n, m, dl in bh_cases:
+        eps.update({name + tag: e for name, e in barneshut(hr, hc, n, m, dl).items()})
+
+    # the direct Toeplitz solvers at n = 1, 2 and 300 (sizes 16384 and 16500: test_host_pointer_direct_toeplitz_solvers): vectors are tiles of
+    # one column without padding, Trench's matrix has ldb = n + 3
+    for n in (1, 2, 300):
+        vc = 1.5 * (np.arange(n + 1) == 0) + np.exp(-np.abs(np.linspace(0.0, 3.0, n + 1)))     # diagonal 2.5: well conditioned
+        r1 = (vc[1:] / vc[0]).astype(dt)                                                        # n entries; Levinson and Trench read n - 1
+        b1 = np.random.default_rng(45).standard_normal(n).astype(dt)
+        eps["covgram_toeplitz_levinson:n%d" % n] = (False, tile_like(
+            lambda po, ldo, loc, pb, pr=None, n=n: lib.covgram_toeplitz_levinson(ctx, pr, pb, n, po, code, loc), n, 1, 46, inputs=[b1, r1][:2 if n > 1 else 1], pad=0))
+        eps["covgram_toeplitz_durbin:n%d" % n] = (False, tile_like(
+            lambda po, ldo, loc, pr, n=n: lib.covgram_toeplitz_durbin(ctx, pr, n, po, code, loc), n, 1, 47, inputs=[r1], pad=0))
+        eps["covgram_toeplitz_trench:n%d" % n] = (False, tile_like(
+            lambda po, ldo, loc, pr=None, n=n: lib.covgram_toeplitz_trench(ctx, pr, n, po, ldo, code, loc), n, n, 48, inputs=[r1][:1 if n > 1 else 0]))
+
     def close():
+        for h in htz:
+            assert lib.covgram_toeplitz_destroy(h) == 0
+        for h in hbh:
+            assert lib.covgram_bh_destroy(h) == 0
+        for h in hbh_points:
+            assert lib.covgram_points_destroy(h) == 0
         assert lib.covgram_sm_destroy(hsm) == 0
         for h in hsp.values():
             assert lib.covgram_sparse_destroy(h) == 0
@@ -391,8 +506,9 @@ def _staged_entry_points(cg, ctx, dt):
 @pytest.mark.parametrize("dt", [np.float32, np.float64])
 def test_host_pointers_give_the_bits_of_device_pointers(cg, ctx, dt):
     """covgram_mvm, _grad_mvm, _valgrad_mvm, _hess_mvm, _valgradhess_mvm, _sm_mvm, _sparse_mvm (y <- alpha G a + beta y, and in place: y is a)
-    and covgram_matrix, _block_matrix (four kinds), _sm_matrix at n = 130, m = 67, d = 3: the HOST call returns the bits of the DEVICE call, and
-    neither writes the padding rows between the extent and the leading dimension."""
+    and covgram_matrix, _block_matrix (four kinds), _sm_matrix at n = 130, m = 67, d = 3, and the structured operators at the shapes listed in
+    _staged_entry_points (covgram_toeplitz_mvm, _kron_mvm, _lowrank_mvm, _bh_mvm, _bh_taylor_mvm, _toeplitz_levinson, _durbin, _trench): the HOST
+    call returns the bits of the DEVICE call, and neither writes the padding rows between the extent and the leading dimension."""
     f = cg._ffi
     eps, close = _staged_entry_points(cg, ctx, dt)
     try:
@@ -404,7 +520,7 @@ def test_host_pointers_give_the_bits_of_device_pointers(cg, ctx, dt):
                 assert host.tobytes() == dev.tobytes(), (name, inplace, float(np.abs(host.astype(np.float64) - dev).max()))
                 if not inplace:
                     assert np.array_equal(host[:, rows:], h0[:, rows:]) and np.array_equal(dev[:, rows:], d0[:, rows:]), (name, "padding rows")
-                    assert not np.array_equal(host[:, :rows], h0[:, :rows]), (name, "nothing written")
+                    assert rows == 0 or not np.array_equal(host[:, :rows], h0[:, :rows]), (name, "nothing written")
     finally:
         close()
 
@@ -417,7 +533,17 @@ _TIMED_LAUNCHES = {
     "covgram_mvm": 1, "covgram_grad_mvm": 2, "covgram_valgrad_mvm": 2, "covgram_hess_mvm": 3, "covgram_valgradhess_mvm": 3, "covgram_sm_mvm": 1,
     "covgram_sparse_mvm": 1, "covgram_matrix": 0, "covgram_block_matrix:gradient": 1, "covgram_block_matrix:value_gradient": 1,
     "covgram_block_matrix:hessian": 1, "covgram_block_matrix:value_gradient_hessian": 1, "covgram_sm_matrix": 1,
+    # the structured operators, by entry point (every shape of one entry counts the same; profiles/structured_driver_ab.txt): only the Barnes-Hut
+    # walks are bracketed, and a factorization without rows returns before any launch
+    "covgram_toeplitz_mvm": 0, "covgram_kron_mvm": 0, "covgram_lowrank_mvm": 0, "covgram_bh_mvm": 1, "covgram_bh_taylor_mvm": 1, "norows": 0,
+    "covgram_toeplitz_levinson": 0, "covgram_toeplitz_durbin": 0, "covgram_toeplitz_trench": 0,
 }
+
+
+def _timed_launches(name):
+    if name in _TIMED_LAUNCHES:
+        return _TIMED_LAUNCHES[name]
+    return _TIMED_LAUNCHES["norows" if name.endswith(":norows") else name.split(":")[0]]
 
 
 @pytest.mark.parametrize("dt", [np.float32, np.float64])
@@ -436,7 +562,7 @@ def test_timer_bracket_counts_one_pair_per_bracketed_launch(cg, dt):
                 f.check(lib.covgram_ctx_kernel_time(h, C.byref(ms), C.byref(cnt), 1))
                 run(loc, False)
                 f.check(lib.covgram_ctx_kernel_time(h, C.byref(ms), C.byref(cnt), 1))
-                assert cnt.value == _TIMED_LAUNCHES[name] and ms.value >= 0.0, (name, loc, cnt.value)
+                assert cnt.value == _timed_launches(name) and ms.value >= 0.0, (name, loc, cnt.value)
         f.check(lib.covgram_ctx_set_option(h, b"time_kernels", 0))
     finally:
         close()
