@@ -555,8 +555,8 @@ def bilinear_gradient(G, U, A):
                                                     the multipliers: ∂/∂U_c = +(2 / U_c) out[2 + c])
     A Sum of such terms takes one launch per term, gradients concatenate; a Constant term's derivative is Σ W.  More than 32 columns
     run in chunks of 32 summed in fp64.  Everything else — a Product of two non-constant kernels, dot-product kernels, Matérn with real
-    ν, spectral mixtures, block Gramians, Toeplitz / Kronecker / sparse / Barnes–Hut operators, ShardedGramian — raises
-    UnsupportedKernel by name before any device call."""
+    ν, spectral mixtures (their own pass: spectral_mixture_gradient), block Gramians, Toeplitz / Kronecker / sparse / Barnes–Hut operators,
+    ShardedGramian — raises UnsupportedKernel by name before any device call."""
     scaled, plan, U, A, Ut, At = _bilinear_setup("bilinear_gradient", G, U, A)
     n, m = G.shape
     d = G.x.shape[1]
@@ -686,6 +686,46 @@ class SpectralMixtureGramian(_OwnsHandle, _PointPairGramian):
 
     def _matrix(self, out, ldo):
         _ffi.check(_ffi.lib().covgram_sm_matrix(self.handle, self._px.handle, self._py.handle, out, ldo, _ffi.DEVICE))
+
+
+def spectral_mixture_gradient(G, U, A):
+    """(value, grad) of the bilinear form Σ_t U[:, t]ᵀ G A[:, t] = Σ_ij W_ij k(x_i, y_j), W = U Aᵀ, with respect to the weights,
+    frequencies and lengthscales of the spectral mixture G was built from, in ONE fused pass over the pairs (csrc/sm_grad.hip,
+    covgram_bilinear_grad_sm): all Q(1 + 2d) derivatives at once, W formed per pair in registers, nothing of size n × m exists.
+    `G` is a SpectralMixtureGramian; U is (n,) or (n, nvec), A (m,) or (m, nvec).  `value` is a float64 0-dim CPU tensor, `grad` a
+    float64 CPU tensor in hyperparameters(G.k) order; the chain rules from the device's numbers to the leaves of the kernel tree are
+    kernels.spectral_mixture_chain_rules.  More than 32 columns run in chunks of 32 summed in fp64.  The parameters are those the
+    handle holds: rounded once to the points' dtype.  Anything but a SpectralMixtureGramian of a tree spectral_mixture_spec accepts
+    raises UnsupportedKernel by name before any device call.  Gradients with respect to the points and autograd through the product
+    of a mixture are out of scope: bilinear_input_gradient and gram_product refuse mixtures."""
+    fn = "spectral_mixture_gradient"
+    if type(G) is not SpectralMixtureGramian:
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"{fn}: {type(G).__name__} is not supported (the SpectralMixtureGramian of gramian(k, x[, y]) only)")
+    n, m = G.shape
+    d = G.x.shape[1]
+    if K.spectral_mixture_spec(G.k, d) is None:
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"{fn}: {type(G.k).__name__} is not a spectral mixture with a device path")
+    U = _vec_arg(U, n, G.dtype, G.device, "U")
+    A = _vec_arg(A, m, G.dtype, G.device, "A")
+    U = U[:, None] if U.dim() == 1 else U
+    A = A[:, None] if A.dim() == 1 else A
+    if U.dim() != 2 or A.dim() != 2 or U.shape[1] != A.shape[1] or U.shape[1] < 1:
+        raise _ffi.DimensionMismatch(_ffi.EINVAL, f"DimensionMismatch: U has shape {tuple(U.shape)}, A {tuple(A.shape)}: equal column counts expected")
+    Ut, At = U.t().contiguous(), A.t().contiguous()            # (nvec, n) row-major == column-major n × nvec
+    nvec = U.shape[1]
+    nout = int(G.w.shape[0]) * (1 + 2 * d)
+    lib = _ffi.lib()
+    G._px.ctx.bind_stream()
+    py = None if G._py is G._px else G._py.handle
+    acc = torch.zeros(nout, dtype=torch.float64)
+    for c0 in range(0, nvec, BILINEAR_MAX_NVEC):
+        nv = min(BILINEAR_MAX_NVEC, nvec - c0)
+        o = torch.empty(nout, dtype=torch.float64, device=G.device)
+        _ffi.check(lib.covgram_bilinear_grad_sm(G.handle, G._px.handle, py, _ffi._P(Ut[c0:].data_ptr()), max(n, 1), _ffi._P(At[c0:].data_ptr()),
+                                                max(m, 1), nv, C.cast(o.data_ptr(), C.POINTER(C.c_double)), _ffi.DEVICE))
+        acc += o.cpu()
+    value, grad = K.spectral_mixture_chain_rules(G.k, acc.numpy(), d)
+    return torch.tensor(value, dtype=torch.float64), torch.tensor(grad, dtype=torch.float64)
 
 
 BLOCK_MATRIX_MAX_D = 64     # covgram_block_matrix, gradient kinds: rows in registers (include/covgram.h)

@@ -113,6 +113,7 @@ class Constant(IsotropicKernel):
         if check and not (c >= 0):
             raise DomainError(f"Constant is not positive semi-definite: {c}")
         self.c = float(c)
+        self.check = bool(check)                               # with_hyperparameters rebuilds a signed weight the way it was built
 
     def profile(self, s):
         return self.c
@@ -287,7 +288,8 @@ class CosineKernel(StationaryKernel):
     def __call__(self, *args):
         if len(args) == 2:
             x = np.atleast_1d(np.asarray(args[0], dtype=np.float64)); y = np.atleast_1d(np.asarray(args[1], dtype=np.float64))
-            return math.cos(2 * math.pi * float(np.dot(self.c, x - y)))
+            c = self.c if self.c.size != 1 else np.broadcast_to(self.c, x.shape)   # a scalar c over d dimensions, as spectral_mixture_spec reads it
+            return math.cos(2 * math.pi * float(np.dot(c, x - y)))
         return math.cos(2 * math.pi * float(args[0]))
 
 
@@ -770,9 +772,10 @@ _NO_PARAMETER = (ExponentiatedQuadratic, Exponential, Cauchy, MaternP, Matern, D
 def hyperparameters(k):
     """[(path, name, value)]: the leaves of the kernel expression `k` in a fixed order — depth first, arguments left to right, a
     wrapper's own parameter after its inner kernel's.  Leaves: Constant.c ("scale"), Lengthscale.l ("l"), RationalQuadratic.alpha,
-    GammaExponential.gamma, InverseMultiQuadratic.c ("c"), and the entries of a diagonal ScaledInputKernel in the parametrisation the
-    object stores: "l" for ARD(k, l) (lengthscales), "U" for ScaledInputKernel(k, U) (the multipliers).  `path` is the tuple of steps
-    from the root (argument index of a Sum / Product, "k" into a wrapper, the dimension of an ARD entry).  MaternP's p, Matern's nu
+    GammaExponential.gamma, InverseMultiQuadratic.c ("c"), the entries of a Cosine's frequency vector ("mu"), and the entries of a
+    diagonal ScaledInputKernel in the parametrisation the object stores: "l" for ARD(k, l) (lengthscales), "U" for
+    ScaledInputKernel(k, U) (the multipliers).  `path` is the tuple of steps from the root (argument index of a Sum / Product, "k"
+    into a wrapper, the dimension of an ARD or Cosine entry).  MaternP's p, Matern's nu
     and Power's exponent are structure, not parameters.  Any other node raises UnsupportedKernel naming it."""
     def walk(k, path):
         if isinstance(k, Constant):
@@ -786,6 +789,8 @@ def hyperparameters(k):
         if isinstance(k, ScaledInputKernel) and k.diagonal:
             name, vals = ("l", k.l) if k.l is not None else ("U", k.U)
             return walk(k.k, path + ("k",)) + [(path + (c,), name, float(v)) for c, v in enumerate(vals)]
+        if isinstance(k, CosineKernel):
+            return [(path + (c,), "mu", float(v)) for c, v in enumerate(k.c)]
         if type(k) in _OWN_PARAMETER:
             name = _OWN_PARAMETER[type(k)]
             return [(path, name, getattr(k, name))]
@@ -804,7 +809,9 @@ def with_hyperparameters(k, theta):
     it = iter(theta)
     def build(k):
         if isinstance(k, Constant):
-            return Constant(next(it))
+            return Constant(next(it), getattr(k, "check", True))
+        if isinstance(k, CosineKernel):
+            return CosineKernel(np.array([next(it) for _ in range(k.c.size)]))
         if isinstance(k, (Sum, Product)):
             return type(k)(tuple(build(a) for a in k.args))
         if isinstance(k, Power):
@@ -929,6 +936,65 @@ def spectral_mixture_spec(k, d=None):
     mu = np.stack([r[1] for r in out]).astype(np.float64)
     inv_l = np.sqrt(np.stack([r[2] for r in out]).astype(np.float64))
     return w, mu, inv_l
+
+
+def _sm_eq_factor_jet(k):
+    """(a, [∂a/∂θ]) of an EQ factor _sm_eq_factor accepts: its squared inverse lengthscale(s) a — a number or a length-d vector — and
+    the derivative of a with respect to each of the factor's leaves, in hyperparameters order (each a number or a length-d vector)."""
+    if isinstance(k, ExponentiatedQuadratic):
+        return 1.0, []
+    if isinstance(k, Lengthscale):
+        a, da = _sm_eq_factor_jet(k.k)
+        return a / k.l ** 2, [t / k.l ** 2 for t in da] + [-2.0 * a / k.l ** 3]
+    a, da = _sm_eq_factor_jet(k.k)                             # a diagonal ScaledInputKernel over an isotropic factor: a_c = a U_c²
+    U = k.U
+    own = []
+    for c in range(U.size):
+        e = np.zeros(U.size)
+        e[c] = -2.0 * a / float(k.l[c]) ** 3 if k.l is not None else 2.0 * a * float(U[c])   # ARD stores l: U_c = 1 / l_c
+        own.append(e)
+    return a * U ** 2, [t * U ** 2 for t in da] + own
+
+
+def spectral_mixture_chain_rules(k, out, d):
+    """The host chain rules of spectral_mixture_gradient: `k` a tree spectral_mixture_spec(k, d) accepts, `out` the Q × (1 + 2d)
+    numbers of covgram_bilinear_grad_sm (row q: ∂F/∂w_q, ∂F/∂μ_qk, E_qk with ∂F/∂(inv_l_qk²) = −½ E_qk).  Returns (value, grad): the
+    bilinear form Σ_q w_q out[q, 0] and its gradient in hyperparameters(k) order.  For term q with Constants c_1 … c_p (w_q = Π c_j)
+    and EQ factors f contributing a_fk to inv_l_qk² = Σ_f a_fk:
+        ∂/∂c_i = (Π_{j≠i} c_j) out[q, 0]
+        ∂/∂μ_k = out[q, 1 + k] for a vector Cosine, Σ_k out[q, 1 + k] for a scalar c broadcast over d
+        ∂/∂θ   = −½ Σ_k E_qk ∂a_fk/∂θ for a parameter θ of factor f: Lengthscale(EQ, l): Σ_k E_qk / l³; ARD(EQ, l): E_qk / l_k³;
+                 ScaledInputKernel(EQ, U): −U_k E_qk; nested lengthscales by the product rule (_sm_eq_factor_jet)."""
+    d = int(d)
+    out = np.asarray(out, dtype=np.float64).reshape(-1, 1 + 2 * d)
+    terms = []
+
+    def flatten(f, kind, into):
+        if isinstance(f, kind):
+            for a in f.args:
+                flatten(a, kind, into)
+        else:
+            into.append(f)
+    flatten(k, Sum, terms)
+    if len(terms) != out.shape[0]:
+        raise _ffi.DimensionMismatch(_ffi.EINVAL, f"spectral_mixture_chain_rules: {len(terms)} terms, {out.shape[0]} rows of out")
+    value, grad = 0.0, []
+    for q, t in enumerate(terms):
+        factors = []
+        flatten(t, Product, factors)
+        consts = [f.c for f in factors if isinstance(f, Constant)]
+        value += float(np.prod(consts)) * out[q, 0]
+        E = out[q, 1 + d:]
+        ci = 0
+        for f in factors:
+            if isinstance(f, Constant):
+                grad.append(float(np.prod(consts[:ci] + consts[ci + 1:])) * out[q, 0])
+                ci += 1
+            elif isinstance(f, CosineKernel):
+                grad += [float(v) for v in out[q, 1:1 + d]] if f.c.size == d else [float(out[q, 1:1 + d].sum())]
+            else:
+                grad += [float(-0.5 * np.sum(E * da)) for da in _sm_eq_factor_jet(f)[1]]
+    return value, grad
 
 
 def require_sm_spec(k, d=None):

@@ -377,20 +377,25 @@ def inv_quad_logdet_gradient(A: LazyOperator, b: torch.Tensor, probes=16, maxite
                              generator=None):
     """(bᵀA⁻¹b, log det A, x = A⁻¹b, grad_inv_quad, grad_logdet, info): inv_quad_logdet and the derivatives of its two terms with respect
     to the hyper-parameters of the kernel, for A = G + σ²I or G + Diagonal(d) (as _split_shift splits it; G alone works too) with G the
-    Gramian of gramian(k, x).  ONE mbcg on [b | Z], exactly as inv_quad_logdet runs it, then with α = A⁻¹b and the probe solves A⁻¹z_t
+    Gramian of gramian(k, x) — or the SpectralMixtureGramian of a spectral mixture, whose bilinear forms spectral_mixture_gradient
+    evaluates in place of bilinear_gradient.  ONE mbcg on [b | Z], exactly as inv_quad_logdet runs it, then with α = A⁻¹b and the probe solves A⁻¹z_t
         grad_inv_quad = −αᵀ(∂G/∂θ)α,     grad_logdet ≈ (1/p) Σ_t (M⁻¹z_t)ᵀ(∂G/∂θ)(A⁻¹z_t)   (M⁻¹z = z without a preconditioner),
     both float64 CPU tensors in hyperparameters(k) order.  The negative log marginal likelihood ½ bᵀA⁻¹b + ½ log det A has the gradient
     ½ (grad_inv_quad + grad_logdet).  When the diagonal term is a scalar shift — every entry of the 1-D tensor equal — the derivative
     with respect to σ² is appended to both: −αᵀα and (1/p) Σ_t (M⁻¹z_t)ᵀ(A⁻¹z_t).
-    The bilinear forms are evaluated one column at a time (1 + p calls of bilinear_gradient with nvec = 1), NOT as one rank-(1 + p)
+    The bilinear forms are evaluated one column at a time (1 + p calls of bilinear_gradient or spectral_mixture_gradient with nvec = 1), NOT as one rank-(1 + p)
     pass: that is what gives the per-probe terms, info["grad_logdet_values"] (p × parameters), and from them
     info["grad_logdet_stderr"], the per-parameter standard error of grad_logdet.  The gradient of precond.logdet() is not part of
     grad_logdet: with a preconditioner that depends on θ the estimate is that of tr(A⁻¹∂A) all the same, since E[(M⁻¹z)zᵀ] = I for z ~ N(0, M)."""
-    from .gramian import Gramian, bilinear_gradient, _bilinear_plan
+    from .gramian import Gramian, SpectralMixtureGramian, bilinear_gradient, spectral_mixture_gradient, _bilinear_plan
     G, diag = _split_shift(A)
-    if type(G) is not Gramian:
+    if type(G) is SpectralMixtureGramian:
+        form_gradient = spectral_mixture_gradient
+    elif type(G) is Gramian:
+        form_gradient = bilinear_gradient
+        _bilinear_plan(G.k)                                     # UnsupportedKernel by name, before the solve
+    else:
         raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"inv_quad_logdet_gradient: {type(G).__name__} is not supported (gramian(k, x) [+ diagonal] only)")
-    _bilinear_plan(G.k)                                         # UnsupportedKernel by name, before the solve
     n = A.shape[0]
     if not torch.is_tensor(b) or b.dim() != 1 or b.shape[0] != n:
         raise _ffi.DimensionMismatch(_ffi.EINVAL, f"DimensionMismatch: b has shape {tuple(getattr(b, 'shape', ()))}, expected ({n},)")
@@ -401,8 +406,8 @@ def inv_quad_logdet_gradient(A: LazyOperator, b: torch.Tensor, probes=16, maxite
     p = Z.shape[1]
     est, vals, stderr = _slq(info, range(1, p + 1), precond)
     MZ = precond(Z) if precond is not None else Z
-    _, gq = bilinear_gradient(G, x, x)
-    rows = [bilinear_gradient(G, MZ[:, t].contiguous(), X[:, 1 + t].contiguous())[1] for t in range(p)]
+    _, gq = form_gradient(G, x, x)
+    rows = [form_gradient(G, MZ[:, t].contiguous(), X[:, 1 + t].contiguous())[1] for t in range(p)]
     gq = -gq
     scalar_shift = diag is not None and diag.numel() > 0 and bool((diag == diag.reshape(-1)[0]).all())
     if scalar_shift:

@@ -792,6 +792,16 @@ function Base.Matrix(S::DeviceSpectralMixture{T}) where {T <: DevFloat}
 end
 Base.getindex(S::DeviceSpectralMixture, i::Integer, j::Integer) = Matrix(S)[i, j]   # (for show and tests; not a hot path)
 
+# --- hyper-parameter gradients of Σ_t U[:, t]' S A[:, t] in one pass (covgram_bilinear_grad_sm): a (1 + 2d) × Q Float64 matrix whose column q is
+#     [∂F/∂w_q; ∂F/∂μ_q (d numbers); E_q (d numbers, ∂F/∂(invl_kq²) = −E_kq / 2)], W = U A' (include/covgram.h)
+function sm_bilinear_grad(S::DeviceSpectralMixture{T}, U::StridedVecOrMat{T}, A::StridedVecOrMat{T}) where {T <: DevFloat}
+    size(U, 1) == S.n && size(A, 1) == S.m && size(U, 2) == size(A, 2) || throw(DimensionMismatch("sm_bilinear_grad: U is n × nvec, A is m × nvec"))
+    out = Matrix{Float64}(undef, 1 + 2 * size(S.μ, 1), length(S.w))
+    check(ccall((:covgram_bilinear_grad_sm, libcovgram), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int32, Ptr{Float64}, Int32),
+                S.handle, S.X.handle, S.Y.handle, U, max(stride(U, 2), S.n), A, max(stride(A, 2), S.m), size(U, 2), out, HOST))
+    return out
+end
+
 # --- hyper-parameter gradients of Σ_t U[:, t]' G A[:, t] in one pass (covgram_bilinear_grad): out = [Σ W k, Σ W ∂k/∂param, Σ W (∂k/∂s) Δ_c² ...]
 #     (one number Σ W (∂k/∂s) s for per_dim = false) in Float64, W = U A'; simple isotropic kernels only (include/covgram.h)
 function bilinear_grad(G::Gramian{T}, U::StridedVecOrMat{T}, A::StridedVecOrMat{T}; per_dim::Bool = false) where {T <: DevFloat}

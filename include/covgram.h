@@ -73,7 +73,8 @@ extern "C" {
                                COVGRAM_BCG_* layout of their state (batched CG on a block of right-hand sides);
                                the covgram_sm_* handle (SpectralMixture Gramians: one fused product and Matrix(G));
                                covgram_bilinear_grad (hyper-parameter gradients of bilinear forms in one pass);
-                               covgram_bilinear_input_grad (their gradients with respect to the row points in one pass).
+                               covgram_bilinear_input_grad (their gradients with respect to the row points in one pass);
+                               covgram_bilinear_grad_sm (the hyper-parameter gradients of a SpectralMixture Gramian's bilinear forms).
                                A binding checks covgram_version() against the header it mirrors at load time */
 
 typedef enum covgram_status {
@@ -654,6 +655,25 @@ int covgram_bilinear_grad(covgram_ctx* ctx, const covgram_kernel* k, const covgr
  *   loc == DEVICE the call is stream-ordered and never synchronises.  Option "time_kernels" brackets the pair kernel and its reduction. */
 int covgram_bilinear_input_grad(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, const void* U, int64_t ldu,
                                 const void* A, int64_t lda, int32_t nvec, double* dX, int32_t loc);
+
+/* ---- Hyper-parameter gradients of the bilinear forms sum_t u_t' G a_t of a SpectralMixture Gramian in ONE pass over the pairs
+ * (csrc/sm_grad.hip), W = U A' as in covgram_bilinear_grad.  With r = x_i - y_j by direct differences, phi_q = 2 pi mu_q . r and
+ * e_q = exp(-1/2 sum_k (r_k inv_l_qk)^2), `out` holds ncomp (1 + 2 d) DOUBLES whatever the points' dtype, component-major:
+ *     out[q (1 + 2 d)]             = sum_ij W_ij cos phi_q e_q                     dF/dw_q (NOT multiplied by w_q)
+ *     out[q (1 + 2 d) + 1 + k]     = sum_ij W_ij (-2 pi w_q) r_k sin phi_q e_q     dF/dmu_qk
+ *     out[q (1 + 2 d) + 1 + d + k] = sum_ij W_ij w_q cos phi_q e_q r_k^2           E_qk: dF/d(inv_l_qk^2) = -1/2 E_qk
+ * so that the value is sum_q w_q out[q (1 + 2 d)].  w, mu and inv_l are the handle's parameters as covgram_sm_create rounded them.
+ * U is n x nvec (ldu >= n), A is m x nvec (lda >= m), column-major, in the points' dtype; `loc` applies to U, A and out; Y == NULL
+ *   means Y = X.  X, Y and S must agree in ctx, dtype and d (COVGRAM_EINVAL, as covgram_sm_mvm); nvec outside 1 .. 32 or a NULL out:
+ *   COVGRAM_EINVAL.
+ * The phases mu_q . x_i and mu_q . y_j are formed per point and reduced in fp64 (as covgram_sm_mvm does); the pair loop has no
+ *   trigonometric instruction.  A pair with r = 0 (with Y == NULL the whole diagonal) adds exactly W_ij to the first output of every
+ *   component and exactly 0 to the others; rows and columns beyond the sets add exactly 0.
+ * A lane adds at most 128 pairs in the points' precision before the sum continues in fp64; partial sums are added in a fixed order, no
+ *   atomics: two calls with the same arguments agree bit for bit.  n m == 0 gives zeros.  With loc == DEVICE the call is stream-ordered
+ *   and never synchronises.  Option "time_kernels" brackets the phase kernels, the pair kernel and its reduction. */
+int covgram_bilinear_grad_sm(covgram_sm* S, const covgram_points* X, const covgram_points* Y, const void* U, int64_t ldu, const void* A,
+                             int64_t lda, int32_t nvec, double* out, int32_t loc);
 
 /* Test hook: the double-precision parameter block handed to the device kernels for `k`
  * (out45[0..8] = gamma, gamma^2, scale, param, c0, 2p+1, Taylor bound, d1, d2; then the MaternP tables
