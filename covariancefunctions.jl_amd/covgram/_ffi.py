@@ -98,6 +98,7 @@ PROTOTYPES = {
     "covgram_ctx_get_info": (C.c_int, [_P, C.c_char_p, C.POINTER(_I64)]),
     "covgram_sync": (C.c_int, [_P]),
     "covgram_ctx_kernel_time": (C.c_int, [_P, C.POINTER(_D), C.POINTER(_I64), _I32]),
+    "covgram_ctx_read_stamps": (C.c_int, [_P, C.POINTER(C.c_uint64), _I64, C.POINTER(_I64)]),
     "covgram_points_create": (C.c_int, [_P, C.POINTER(_P), _P, _I64, _I32, _I32, _I32]),
     "covgram_points_slice": (C.c_int, [_P, _I64, _I64, C.POINTER(_P)]),
     "covgram_points_destroy": (C.c_int, [_P]),

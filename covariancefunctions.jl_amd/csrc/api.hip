@@ -707,13 +707,13 @@ static const CtxField kOptions[] = {
     CG_FIELD(dense_variant), CG_FIELD(toeplitz_fused), CG_FIELD(toeplitz_colfft), CG_FIELD(toeplitz_persist), CG_FIELD(kron_fill), CG_FIELD(mfma_f16),
     CG_FIELD(mfma_gate_pct), CG_FIELD(mfma_fuse_w), CG_FIELD(toeplitz_real_spectrum), CG_FIELD(rows_per_lane), CG_FIELD(jsplit), CG_FIELD(target_wgs),
     CG_FIELD(grad_keep_r), CG_FIELD(grad_expand), CG_FIELD(grad_bcast), CG_FIELD(mfma_lds), CG_FIELD(mfma_sym), CG_FIELD(dense_sym), CG_FIELD(dense_bcast),
-    CG_FIELD(mfma_stamp), CG_FIELD(inkernel_reduce), CG_FIELD(matrix_variant), CG_FIELD(mfma_mrhs), CG_FIELD(composite_termwise), CG_FIELD(sum_fused),
+    CG_FIELD(mfma_stamp), CG_FIELD(mfma_graded), CG_FIELD(inkernel_reduce), CG_FIELD(matrix_variant), CG_FIELD(mfma_mrhs), CG_FIELD(composite_termwise), CG_FIELD(sum_fused),
     CG_FIELD(lowrank_reverse), CG_FIELD(mfma_sym_rt), CG_FIELD(mfma_sym_st), CG_FIELD(lowrank_wgs), CG_FIELD(time_kernels)};
 static const CtxField kInfo[] = {
     CG_FIELD(last_dense_path), CG_FIELD(last_jsplit), CG_FIELD(last_kron_path), CG_FIELD(last_mfma_lds), CG_FIELD(last_mfma_sym), CG_FIELD(last_dense_sym),
     CG_FIELD(last_dense_bcast), CG_FIELD(last_mfma_f16), CG_FIELD(last_inkernel_reduce), CG_FIELD(last_grad_expand), CG_FIELD(last_grad_bcast),
     CG_FIELD(last_grad_path), CG_FIELD(last_grad_jsplit), CG_FIELD(last_hess_path), CG_FIELD(last_vgh_path), CG_FIELD(last_matrix_path),
-    CG_FIELD(last_block_matrix_path), CG_FIELD(last_sum_fused), CG_FIELD(last_mfma_instance), CG_FIELD(last_mfma_sym_rt), CG_FIELD(num_cus)};
+    CG_FIELD(last_block_matrix_path), CG_FIELD(last_sum_fused), CG_FIELD(last_mfma_instance), CG_FIELD(last_mfma_graded), CG_FIELD(last_mfma_sym_rt), CG_FIELD(num_cus)};
 #undef CG_FIELD
 
 int covgram_ctx_set_option(covgram_ctx* ctx, const char* key, int64_t value) {
@@ -752,6 +752,17 @@ int covgram_ctx_get_info(covgram_ctx* ctx, const char* key, int64_t* value) {
     }
     set_error("unknown info key '%s'", key);
     return COVGRAM_EINVAL;
+}
+
+int covgram_ctx_read_stamps(covgram_ctx* ctx, uint64_t* out, int64_t cap, int64_t* count) {
+    CG_REQUIRE(ctx && count && cap >= 0 && (out || cap == 0), COVGRAM_EINVAL, "NULL argument");
+    *count = ctx->stamp_buf ? (int64_t)ctx->stamp_count : 0;
+    const size_t take = (size_t)std::min<int64_t>(*count, cap);
+    if (take == 0) return COVGRAM_OK;
+    CG_DEVICE(ctx);
+    CG_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    CG_CHECK_HIP(hipMemcpy(out, ctx->stamp_buf, take * 4 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return COVGRAM_OK;
 }
 
 int covgram_ctx_kernel_time(covgram_ctx* ctx, double* total_ms, int64_t* launches, int32_t reset) {

@@ -273,7 +273,9 @@ struct covgram_ctx {
     size_t tickets_cap = 0;
     int64_t mfma_sym = -1;       // matrix-core EQ path on gramian(k, x): evaluate the upper triangle once (-1 auto, 0 never, 1 always)
     int64_t mfma_lds = -1;       // matrix-core EQ path: 4 waves share the column tiles through LDS (-1 auto, 0 never, 1 always)
-    int64_t mfma_stamp = 0;      // 1: the general matrix-core EQ kernel runs its clock-stamping diagnostic build (info key "last_clock_khz")
+    int64_t mfma_graded = -1;    // general matrix-core EQ kernel: graded column split, shorter chunks towards the end of the grid (-1 auto: the LDS-shared form from two rounds of resident workgroups on, 0 never, 1 wherever the shape admits one; >= 100: measurements, dense_mfma.hip)
+    int64_t last_mfma_graded = 0; // chunks of the last general matrix-core EQ MVM when it ran the graded split, else 0
+    int64_t mfma_stamp = 0;     // 1: the general matrix-core EQ kernel runs its clock-stamping diagnostic build (info key "last_clock_khz")
     void* stamp_buf = nullptr;   // [workgroup][4]: s_memtime / s_memrealtime before and after the column loop
     size_t stamp_cap = 0, stamp_count = 0;
     int64_t matrix_variant = 0;     // Matrix(G): 0 = rows in registers + 64-column strips (d <= 64), 1 = the generic entry-by-entry kernel
@@ -410,6 +412,9 @@ grad_launch_fn grad_launcher(int family);
 // ~1.7e-7 P per entry.  The bound is on EACH side, not on the product: the partial sums of |x~|^2 + |y~|^2 - 2 x~.y~ reach
 // the larger norm, and a far X cluster over a compact Y would otherwise pass.
 constexpr int MFMA_LDS_MIN_TILES = 64;
+// the graded column split of the general EQ kernel (dense_mfma.hip: mvm_eq_mfma): the columns cut into shorter chunks at the end of the grid, in half
+// rounds of the instance's resident workgroups (measured at C2, profiles/c2_graded_split.txt)
+constexpr int MFMA_GRADED_TAIL_HALFROUNDS = 1;
 // gramian(k, x) takes the symmetric (upper triangle once) kernels from these sizes on; below, the general kernel is as fast — the
 // symmetric launch has a floor of ~33 us (EQ) / ~90 us (MaternP) from its panel structure.  tools/sym_threshold_sweep.py, all
 // entries / symmetric in us: EQ d = 3: n = 16384 38.8 / 40.0, 20000 55.9 / 51.5; EQ d = 8: 16384 48.9 / 47.0, 20000 70.7 / 60.0;

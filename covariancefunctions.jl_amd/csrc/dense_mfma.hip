@@ -55,6 +55,7 @@
 #include "dense_mfma_eq.hpp"
 
 namespace covgram {
+static_assert(GRADED_MAX_CHUNKS == MFMA_MAX_CHUNKS, "the planner's table and the kernel argument hold the same number of chunks");
 
 // ---- The points handle's radii: max |x|^2 and max |x - c|^2 about a sampled centre, computed once at handle creation (covgram_points_create, --------------------
 // api.hip), and the gate quantity the rules below derive from them
@@ -411,10 +412,20 @@ static int mfma_blocks_per_cu() {
 // the one place that spells dense_mfma_eq_kernel's argument list; a.grid counts WAVES (x: row blocks of 32 RT rows)
 template <int K2, int RT, int WPB, int LDS, int STAMP, int FMT>
 static void eq_launch(covgram_ctx* ctx, const MfmaArgs& a, dim3* launched) {
-    ctx->last_mfma_instance = (int64_t)K2 * 100000 + RT * 10000 + WPB * 1000 + LDS * 100 + STAMP * 10 + FMT;
     *launched = dim3((a.grid.x + WPB - 1) / WPB, a.grid.y);
+    if (a.occupancy) {   // the graded plan's question: how many workgroups of THIS instance a CU holds (asked once per instance), and its waves per workgroup
+        static int cached = 0;
+        if (!cached) {
+            int nb = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, dense_mfma_eq_kernel<K2, RT, WPB, LDS, STAMP, FMT>, 64 * WPB, 0) != hipSuccess || nb <= 0) nb = std::max(1, 16 / WPB);
+            cached = nb;
+        }
+        a.occupancy[0] = cached; a.occupancy[1] = WPB;
+        return;
+    }
+    ctx->last_mfma_instance = (int64_t)K2 * 100000 + RT * 10000 + WPB * 1000 + LDS * 100 + STAMP * 10 + FMT;
     hipLaunchKernelGGL((dense_mfma_eq_kernel<K2, RT, WPB, LDS, STAMP, FMT>), *launched, dim3(64 * WPB), 0, a.stream, a.X, a.n, a.d, a.PB, a.W, a.ntile, a.out,
-                       a.npad, a.tchunk, a.g, a.alpha, a.beta, a.final_store, a.Cn, STAMP ? a.stamps : nullptr, a.tickets, a.yfinal, a.EF, a.mcols);
+                       a.npad, a.tchunk, a.g, a.alpha, a.beta, a.final_store, a.Cn, STAMP ? a.stamps : nullptr, a.tickets, a.yfinal, a.EF, a.mcols, a.chunks);
 }
 // the instance of (K2, split) for this plan: row tiles per wave a.RT, the LDS-shared form (a.lds), the diagnostic build (a.stamps)
 template <int K2, int FMT>
@@ -521,7 +532,8 @@ int mvm_eq_mfma(covgram_ctx* ctx, const HostKernel& hk, const covgram_points* X,
     // row tiles per wave: two share every B fragment while the state fits (d <= 8); option "rows_per_lane" = 1 / 2 forces it
     int rt = ctx->rows_per_lane == 1 ? 1 : (ctx->rows_per_lane == 2 ? 2 : (K2 <= MFMA_NARROW_MAXK2 ? 2 : 1));
     if (K2 > 8) rt = 1;
-    // grid = a whole number (4) of rounds of resident waves: a fractional last round costs up to one round of idle SIMDs
+    // the uniform plan aims at 4 rounds of resident one-wave workgroups (nb per CU); where the LDS-shared form then runs at least two rounds of ITS resident
+    // workgroups, the end of the column range is cut finer below ("graded split"): equal workgroups do not finish together, and the chip drains in their length
     int nb = 16;
     mfma_for_k2(K2, [&](auto k) {
         constexpr int K = decltype(k)::value;
@@ -548,10 +560,52 @@ int mvm_eq_mfma(covgram_ctx* ctx, const HostKernel& hk, const covgram_points* X,
         const Plan p4 = plan_for(4);
         if (p4.lds4) pl = p4;
     }
-    const ColumnPlan& col = pl.col;
+    ColumnPlan col = pl.col;
     ma.RT = pl.rt; ma.lds = pl.lds4 ? 1 : 0;
-    ma.npad = col.npad; ma.tchunk = col.tchunk; ma.final_store = col.js == 1 ? 1 : 0;
     ma.grid = dim3((unsigned)col.rowtiles, (unsigned)col.js);
+    // The graded split (mfma_plan.hpp: plan_columns_graded).  Equal chunks fill the resident slots in whole rounds only on paper: the workgroups of a
+    // round do not finish together, a slot that is done with its last one has nothing left to take, and the chip drains at the granularity of a
+    // workgroup's life — C2's 8 x 256 workgroups on 512 slots live a quarter of the kernel each (tools/c2_drain_probe.py, profiles/c2_graded_split.txt).
+    // The last half round's worth of columns is cut into chunks that halve down to MFMA_LDS_MIN_TILES, dispatched last: the slots that free up first
+    // take them.  Automatic only where it can pay — shapes of the LDS-shared form, at least two rounds of the instance's resident workgroups, chunks at or above
+    // the LDS form's minimum —; a forced "jsplit" / "target_wgs" and the GP-sized shapes under plan_columns' stop / floor clamps keep the uniform split.
+    // Option "mfma_graded": -1 this rule, 0 never, 1 wherever the shape admits a graded table (tests), 100 h + f = 1 with a tail of h half rounds and a
+    // floor of 16 * 2^f tiles (measurements: tools/c2_graded_ab.py).  The slab keeps one row per chunk, summed in chunk order: deterministic, as before.
+    ctx->last_mfma_graded = 0;
+    if (ctx->mfma_graded != 0 && ctx->jsplit <= 0 && ctx->target_wgs <= 0 && col.js > 1) {
+        // The rule looks at the SHAPE — would the automatic "mfma_lds" share its column tiles through LDS? — and plans for that LDS-shared instance
+        // even when option "mfma_lds" = 0 / 1 picks the form by hand: the table, and with it every bit of the result, is the same for both forms
+        // (tests/test_gpu_parity.py compares them bit for bit)
+        const bool lds_shape = ((pl.rt >= 2 && K2 <= MFMA_NARROW_MAXK2) || (pl.rt == 1 && K2 > MFMA_NARROW_MAXK2)) && col.tchunk >= MFMA_LDS_MIN_TILES &&
+                               col.rowtiles >= 64;
+        int occ[2] = {0, 1};                                             // resident workgroups per CU and waves per workgroup of the instance planned for
+        dim3 unused;
+        MfmaArgs q = ma;
+        q.lds = lds_shape ? 1 : ma.lds; q.occupancy = occ;
+        mfma_for_k2(K2, [&](auto k) {
+            constexpr int K = decltype(k)::value;
+            if (!fmt) eq_launch_instance<K, 0>(ctx, q, &unused);
+            else if constexpr (K <= 8) eq_launch_instance<K, 1>(ctx, q, &unused);
+        });
+        const bool force = ctx->mfma_graded > 0;
+        const int64_t wpb = occ[1], rblocks = (col.rowtiles + wpb - 1) / wpb, slots = (int64_t)ctx->num_cus * occ[0];
+        // (GP-sized shapes: the split plan_columns' stop / floor clamps changed stays as measured there)
+        const bool clamped = plan_columns(n, ntile, 32 * pl.rt, (int64_t)ctx->num_cus * nb * 4, 0, 8).js != col.js;
+        // the floor: the LDS form's minimum; forced on a shape whose chunks are shorter than two of those, a wave's minimum of 8 tiles
+        int64_t floor_tiles = col.tchunk >= 2 * MFMA_LDS_MIN_TILES ? MFMA_LDS_MIN_TILES : 8, halfrounds = MFMA_GRADED_TAIL_HALFROUNDS;
+        if (ctx->mfma_graded >= 100) { halfrounds = ctx->mfma_graded / 100; floor_tiles = (int64_t)16 << (ctx->mfma_graded % 10); }   // (measurements)
+        if (force || (lds_shape && !clamped)) {
+            const GradedPlan gp = plan_columns_graded(col, ntile, rblocks, slots, q.lds ? wpb : 2 /* (that loop walks tile pairs) */, floor_tiles, force, halfrounds);
+            if (gp.graded) {
+                col.js = gp.js;
+                ma.chunks.n = (int32_t)gp.js;
+                for (int c = 0; c <= GRADED_MAX_CHUNKS; ++c) ma.chunks.start[c] = gp.start[c];
+                ma.grid.y = (unsigned)gp.js;
+                ctx->last_mfma_graded = gp.js;
+            }
+        }
+    }
+    ma.npad = col.npad; ma.tchunk = col.tchunk; ma.final_store = col.js == 1 ? 1 : 0;
     rc = split_out(ctx, col, 1, y, &ma.out);
     if (rc) return rc;
     // option "mfma_stamp": the clock-stamping diagnostic build of the two LDS-shared instances (C2's and C3's kernels)

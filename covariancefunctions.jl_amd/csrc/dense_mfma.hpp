@@ -1043,6 +1043,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 #include "dense_mfma_sym2.hpp"
 namespace covgram {
 
+// chunk boundaries of a graded column split (mfma_plan.hpp: plan_columns_graded), passed to dense_mfma_eq_kernel BY VALUE in its kernel arguments — no
+// memory of its own, nothing to keep alive under stream capture: chunk c walks the column tiles [start[c], start[c + 1]).  n == 0: the uniform split by tchunk
+constexpr int MFMA_MAX_CHUNKS = 64;
+struct ChunkTable { int32_t n = 0; int32_t start[MFMA_MAX_CHUNKS + 1] = {}; };
+
 struct MfmaArgs {
     const float* X; int64_t n; int32_t d;
     const uint4* PB; const float* W; int64_t ntile;
@@ -1066,6 +1071,8 @@ struct MfmaArgs {
     // W holds packed weights) and the column count, the arrival counters and final output of the in-kernel slab sum, the diagnostic clock stamps
     float g = 0.0f; const float* EF = nullptr; int64_t mcols = 0;
     unsigned* tickets = nullptr; float* yfinal = nullptr; unsigned long long* stamps = nullptr;
+    ChunkTable chunks;           // dense_mfma_eq_kernel: the graded column split (n == 0: uniform, by tchunk)
+    int* occupancy = nullptr;    // dense_mfma_eq_kernel: not nullptr = launch nothing, report the resident workgroups per CU of the instance that would run
 };
 
 // ---- one function per kernel family spells its argument list ---------------------------------------------------------------------------------

@@ -90,7 +90,8 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(LDS ==
                                                            float* __restrict__ out, int64_t npad, int64_t tchunk, float g,
                                                            float alpha, float beta, int32_t final_store, const float* __restrict__ Cn,
                                                            unsigned long long* __restrict__ stamps, unsigned* __restrict__ tickets,
-                                                           float* __restrict__ yfinal, const float* __restrict__ EF, int64_t mcols) {
+                                                           float* __restrict__ yfinal, const float* __restrict__ EF, int64_t mcols,
+                                                           const ChunkTable chunks) {
     // WPB waves per workgroup take consecutive row tiles and walk the SAME column tiles at the same pace (no barrier,
     // nothing shared explicitly): their fragment loads coalesce in the CU's vector L1 instead of each going to L2
     const int l = threadIdx.x & 63, t = l & 31, h = l >> 5;
@@ -107,8 +108,11 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(LDS ==
 
     unsigned long long st_c0 = 0, st_r0 = 0;
     if constexpr (STAMP) { st_c0 = __builtin_amdgcn_s_memtime(); st_r0 = __builtin_amdgcn_s_memrealtime(); }
-    const int64_t T0 = (int64_t)blockIdx.y * tchunk;
-    const int64_t T1 = (T0 + tchunk < ntile) ? (T0 + tchunk) : ntile;
+    // this workgroup's column tiles [T0, T1): equal steps of tchunk, or the boundaries of a graded split (chunks.n > 0: shorter chunks towards the end of
+    // the grid, mfma_plan.hpp) — two scalar loads from the kernel arguments
+    int64_t T0 = (int64_t)blockIdx.y * tchunk;
+    int64_t T1 = (T0 + tchunk < ntile) ? (T0 + tchunk) : ntile;
+    if (chunks.n > 0) { T0 = chunks.start[blockIdx.y]; T1 = chunks.start[blockIdx.y + 1]; }
     // the accumulators live as register PAIRS: with one or two MFMAs per tile the weighted sums are v_pk_fma_f32 (two fmas per instruction — nearly twice
     // the rate while no MFMA executes, slower than two v_fma_f32 beside one: tools/pkfma_probe.hip; C2-shaped 1.44 -> 1.33 ms, four MFMAs per tile +2-3 %)
     typedef float f32x2 __attribute__((ext_vector_type(2)));

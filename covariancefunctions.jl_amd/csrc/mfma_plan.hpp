@@ -33,6 +33,57 @@ inline ColumnPlan plan_columns(int64_t n, int64_t ntile, int rows, int64_t targe
     return pl;
 }
 
+// ---- graded column split (dense_mfma_eq_kernel) --------------------------------------------------------------------------------------------
+// A uniform split hands the chip equal workgroups: a slot that finishes its last one early finds nothing left to take, and the kernel drains at
+// the granularity of one workgroup's life (C2: a quarter of the kernel).  The graded split keeps plan_columns' chunk length for the body and cuts
+// the LAST portion of the column range — `tail_halfrounds` half rounds of the `slots` resident workgroups, at most half of the chunks — into shorter
+// chunks of non-increasing length: each level takes half of what is left in chunks half as long as the level before, down to `floor_tiles`,
+// which takes the rest.  Every graded chunk is a multiple of `stage` tiles (what a workgroup of the LDS-shared form fetches at once) except
+// possibly the last one, the remainder.  The grid is dispatched chunk-major, so the short chunks start last and fill the slots that free up first.
+//   start[0 .. js]: tile offsets of the chunk boundaries (chunk c walks [start[c], start[c + 1])), js <= GRADED_MAX_CHUNKS
+//   graded == false: the shape does not admit it (too few chunks or rounds, chunks under the floor, more than 64 chunks) — the uniform plan `base`
+//   stands, js = base.js, and start[] holds its equal steps where they fit the table
+constexpr int GRADED_MAX_CHUNKS = 64;
+struct GradedPlan { bool graded; int64_t js; int32_t start[GRADED_MAX_CHUNKS + 1]; };
+
+// base: the uniform plan; rblocks: workgroups along the rows (grid x); slots: resident workgroups of the instance that will launch, whole chip;
+// force: skip the "pays only from two rounds of resident workgroups on" condition (option "mfma_graded" = 1)
+inline GradedPlan plan_columns_graded(const ColumnPlan& base, int64_t ntile, int64_t rblocks, int64_t slots, int64_t stage, int64_t floor_tiles,
+                                      bool force, int64_t tail_halfrounds = 2) {
+    GradedPlan g;
+    g.graded = false; g.js = base.js;
+    for (int64_t c = 0; c <= GRADED_MAX_CHUNKS; ++c) g.start[c] = (int32_t)std::min<int64_t>(c * base.tchunk, ntile);
+    if (base.js < 2 || rblocks < 1 || slots < 1 || stage < 1 || ntile > INT32_MAX) return g;
+    if (!force && (rblocks * base.js < 2 * slots || base.tchunk < floor_tiles)) return g;
+    const int64_t tail_chunks = std::max<int64_t>(1, std::min<int64_t>((tail_halfrounds * slots + rblocks) / (2 * rblocks), base.js / 2));
+    const int64_t body = base.js - tail_chunks;
+    for (int64_t floor = (std::max<int64_t>(floor_tiles, 1) + stage - 1) / stage * stage;; floor *= 2) {
+        int64_t len = base.tchunk / 2 / stage * stage;
+        if (len < floor || body > GRADED_MAX_CHUNKS) return g;        // nothing to grade: the first level would fall under the floor
+        int64_t js = body, at = body * base.tchunk, left = ntile - at;
+        int32_t start[GRADED_MAX_CHUNKS + 1];
+        for (int64_t c = 0; c <= body; ++c) start[c] = (int32_t)(c * base.tchunk);
+        bool fits = true;
+        while (left > 0 && fits) {
+            // chunks of this level: half of what is left (at least one), everything at the floor; the remainder under a chunk goes last
+            int64_t k = len > floor ? std::min<int64_t>((left / 2 + len - 1) / len, left / len) : left / len;
+            if (len == floor && k == 0) k = 1;
+            for (; k > 0 && fits; --k) {
+                const int64_t take = std::min(len, left);
+                if (js >= GRADED_MAX_CHUNKS) { fits = false; break; }
+                at += take; left -= take; start[++js] = (int32_t)at;
+            }
+            if (len > floor) len = std::max(floor, len / 2 / stage * stage);
+            else if (left > 0 && left < len) len = left;               // (the remainder: one last, shorter chunk)
+        }
+        if (!fits) continue;                                           // more than 64 chunks: a coarser floor
+        g.graded = true; g.js = js;
+        for (int64_t c = 0; c <= js; ++c) g.start[c] = start[c];
+        for (int64_t c = js + 1; c <= GRADED_MAX_CHUNKS; ++c) g.start[c] = (int32_t)ntile;
+        return g;
+    }
+}
+
 // ---- work list of the symmetric kernels ----------------------------------------------------------------------------------------------------
 // A panel = tpp row tiles; this call owns the panels pfirst, pfirst + pstride, ... (local numbers 0, 1, ...).  Workgroup (lp, c) walks the column
 // tiles [max(c tchunk, first tile of its panel), min((c + 1) tchunk, ntile)): chunks sit at absolute multiples of tchunk, a panel's first one is

@@ -208,6 +208,10 @@ int covgram_ctx_get_stream(covgram_ctx* ctx, void** hip_stream);
  * 2.5e-5 (fp16) at the edge and scales with the gate: 40 holds 1e-5 row-wise on it.  Clouds outside run the direct-difference kernels),
  * "mfma_fuse_w" (the general matrix-core EQ kernel's column weights a_j exp2(f_j): -1 / 1 = formed inside the kernel, 0 = by a pack launch in front of
  * it — bit-identical results),
+ * "mfma_graded" (the general matrix-core EQ kernel's column split: -1 = graded — the last half round's worth of columns cut into chunks that halve down to 64
+ * tiles, so that the chip drains in short workgroups — on the LDS-shared form from two rounds of resident workgroups on, 0 = always equal chunks, 1 = graded
+ * wherever the shape admits it (tests), 100 h + f = 1 with a tail of h half rounds and a floor of 16 * 2^f tiles: measurements only, tools/c2_graded_ab.py.  A forced "jsplit" or "target_wgs" keeps equal
+ * chunks.  Results differ between the two splits by the fp32 summation order of the chunks' partial sums; each is deterministic),
  * "mfma_stamp" (1 = the general matrix-core EQ kernel runs its clock-stamping DIAGNOSTIC build — s_memtime / s_memrealtime
  * around every workgroup's column loop, for bench.py's sustained-clock figure; never set in production). */
 int covgram_ctx_set_option(covgram_ctx* ctx, const char* key, int64_t value);
@@ -216,13 +220,17 @@ int covgram_ctx_set_option(covgram_ctx* ctx, const char* key, int64_t value);
  * ran: 0 none yet or n m == 0, otherwise route + 10 DM + 1000 VR with route 1 = generic single profile, 2 = generic composite,
  * 3 = registers single profile, 4 = registers composite; DM the compiled dimension bucket, 0 for the generic kernels; VR rows per
  * thread, 1 where not applicable), "last_mfma_lds" (1: that matrix-core MVM shared its column tiles through LDS), "last_mfma_sym" (1: the last dense
- * MVM ran the symmetric upper-triangle kernel), "last_dense_sym" (1: it ran a direct-difference symmetric kernel, fp64 or fp32), "last_inkernel_reduce" (1: the last dense kernel summed its own split-J slab), "last_grad_expand" (1: the last gradient MVM ran the expanded form), "last_grad_bcast" (waves per workgroup of the broadcast kernel if the last gradient MVM ran it, else 0), "last_grad_path" (which kernels the last gradient or value-gradient MVM ran, as bits: 1 = the lane-per-row kernel, 2 = its two-column pass, 4 = the panel path (grad_wide), 8 = more than one panel, 16 = the panel path split over z slices with the separate reduce, 32 = the lane-per-row kernel with a column split > 1 and the slab reduce; 0 = no block kernel (n = 0 or m = 0); a Sum split term by term reports its last term), "last_grad_jsplit" (the column split of the last gradient MVM's lane-per-row launch, 0 if it did not run one), "last_hess_path" (0 = no Hessian MVM yet or one without rows / columns, 1 = the last covgram_hess_mvm ran its block kernel, csrc/hess_mvm.hpp), "last_block_matrix_path" (0 = no covgram_block_matrix yet or an empty product, otherwise (kind + 1) + 10 VR, VR = scalars per store instruction of the launch that ran: 1, or 2 for fp64 / 4 for fp32 on the 16-byte route), "last_sum_fused" (1: the last covgram_mvm ran a Sum on the one-pass kernels), "last_mfma_instance" (which instance of the matrix-core EQ kernels the last launch was: the template arguments of dense_mfma_eq_kernel as K2 1e5 + RT 1e4 + WPB 1e3 + LDS 100 + STAMP 10 + FMT, -(K2 10 + FMT) for the symmetric kernel, 0 otherwise — bench.py checks its recorded PMC pass against it), "last_dense_bcast" (1: the last fp64 dense MVM ran a register-broadcast kernel), "last_mfma_f16" (1: the last general matrix-core EQ MVM ran the fp16 two-way split), "last_jsplit" (the column split of the last lane-per-row dense launch), "last_kron_path" (which kernels the last covgram_kron_mvm ran, as bits: 1 = the fused last-two-modes pass, 2 = the single-mode kernel, 4 = the last-mode kernel, 8 = a rocBLAS GEMM (a factor side >= 1024, >= 256 with >= 2 GFLOP, or a shape the kernels refuse), 16 = two small trailing factors multiplied out first), "num_cus", "last_clock_khz" (median shader clock over the workgroups of the last
+ * MVM ran the symmetric upper-triangle kernel), "last_dense_sym" (1: it ran a direct-difference symmetric kernel, fp64 or fp32), "last_inkernel_reduce" (1: the last dense kernel summed its own split-J slab), "last_grad_expand" (1: the last gradient MVM ran the expanded form), "last_grad_bcast" (waves per workgroup of the broadcast kernel if the last gradient MVM ran it, else 0), "last_grad_path" (which kernels the last gradient or value-gradient MVM ran, as bits: 1 = the lane-per-row kernel, 2 = its two-column pass, 4 = the panel path (grad_wide), 8 = more than one panel, 16 = the panel path split over z slices with the separate reduce, 32 = the lane-per-row kernel with a column split > 1 and the slab reduce; 0 = no block kernel (n = 0 or m = 0); a Sum split term by term reports its last term), "last_grad_jsplit" (the column split of the last gradient MVM's lane-per-row launch, 0 if it did not run one), "last_hess_path" (0 = no Hessian MVM yet or one without rows / columns, 1 = the last covgram_hess_mvm ran its block kernel, csrc/hess_mvm.hpp), "last_block_matrix_path" (0 = no covgram_block_matrix yet or an empty product, otherwise (kind + 1) + 10 VR, VR = scalars per store instruction of the launch that ran: 1, or 2 for fp64 / 4 for fp32 on the 16-byte route), "last_sum_fused" (1: the last covgram_mvm ran a Sum on the one-pass kernels), "last_mfma_instance" (which instance of the matrix-core EQ kernels the last launch was: the template arguments of dense_mfma_eq_kernel as K2 1e5 + RT 1e4 + WPB 1e3 + LDS 100 + STAMP 10 + FMT, -(K2 10 + FMT) for the symmetric kernel, 0 otherwise — bench.py checks its recorded PMC pass against it), "last_dense_bcast" (1: the last fp64 dense MVM ran a register-broadcast kernel), "last_mfma_graded" (the number of column chunks if the last general matrix-core EQ MVM ran the graded split of "mfma_graded", else 0), "last_mfma_f16" (1: the last general matrix-core EQ MVM ran the fp16 two-way split), "last_jsplit" (the column split of the last lane-per-row dense launch), "last_kron_path" (which kernels the last covgram_kron_mvm ran, as bits: 1 = the fused last-two-modes pass, 2 = the single-mode kernel, 4 = the last-mode kernel, 8 = a rocBLAS GEMM (a factor side >= 1024, >= 256 with >= 2 GFLOP, or a shape the kernels refuse), 16 = two small trailing factors multiplied out first), "num_cus", "last_clock_khz" (median shader clock over the workgroups of the last
  * launch made with "mfma_stamp" = 1; synchronises the stream; 0 = no stamped launch yet). */
 int covgram_ctx_get_info(covgram_ctx* ctx, const char* key, int64_t* value);
 int covgram_sync(covgram_ctx* ctx);
 /* With option "time_kernels" = 1 every dense / gradient MVM brackets its dominant kernel with HIP events on the
  * ctx stream; this returns the summed device time and the number of launches since the last reset. */
 int covgram_ctx_kernel_time(covgram_ctx* ctx, double* total_ms, int64_t* launches, int32_t reset);
+/* The clock stamps of the last launch made with "mfma_stamp" = 1 (diagnostics: tools/c2_drain_probe.py): *count = its workgroups (0: none
+ * yet), and up to cap of them are copied to out as four values each — shader clock and 100 MHz counter at the start of the workgroup's column
+ * loop, the same two at its end — in launch order (chunk-major: workgroup = chunk * row blocks + row block).  Synchronises the stream. */
+int covgram_ctx_read_stamps(covgram_ctx* ctx, uint64_t* out, int64_t cap, int64_t* count);
 
 /* x: n points of dimension d, point-major.  loc == HOST: copied to the device; loc == DEVICE: borrowed
  * (the caller keeps it alive and unchanged while the handle lives: creation caches a sample mean c of the set as the
