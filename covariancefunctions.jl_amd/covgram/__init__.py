@@ -24,12 +24,12 @@ from .gramian import (Gramian, BlockGramian, HessianGramian, ValueGradientHessia
                       SeparableGramian, LazyMatrixProduct, LazyMatrixSum, ScaledOperator, LinearMapBlockGramian, CosineBlockGramian, PointJacobianBlockGramian, Fill, LazyOperator, LazyGrid, StepRangeLen,
                       srange, gramian, mul_, get_ctx, set_option, get_info, kernel_time, SparseGramian, sparse, decay_radius,
                       BarnesHutFactorization, require_barneshut_spec, SpectralMixtureGramian, bilinear_gradient, bilinear_chain_rules,
-                      bilinear_input_gradient, spectral_mixture_gradient)
+                      bilinear_input_gradient, spectral_mixture_gradient, spectral_mixture_input_gradient)
 from .dist import ShardedGramian, shard_bounds
 from .solve import (cg, mbcg, cg_tridiagonals, lanczos_quadrature, logdet, inv_quad_logdet, inv_quad_logdet_gradient, minres, solve, toeplitz_solve, durbin, levinson,
                     trench)
 from .factorize import (cholesky, factorize, diagonal, CholeskyFactor, PivotedCholesky, pivoted_cholesky, PivotedCholeskyPreconditioner,
                         preconditioner)
-from .autograd import gram_product
+from .autograd import gram_product, spectral_mixture_product
 
 __all__ = [n for n in dir() if not n.startswith("_")]

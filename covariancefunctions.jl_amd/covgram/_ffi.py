@@ -157,6 +157,7 @@ PROTOTYPES = {
     "covgram_sm_matrix": (C.c_int, [_P, _P, _P, _P, _I64, _I32]),
     "covgram_sm_destroy": (C.c_int, [_P]),
     "covgram_bilinear_grad_sm": (C.c_int, [_P, _P, _P, _P, _I64, _P, _I64, _I32, C.POINTER(_D), _I32]),
+    "covgram_bilinear_input_grad_sm": (C.c_int, [_P, _P, _P, _P, _I64, _P, _I64, _I32, C.POINTER(_D), _I32]),
     "covgram_bilinear_grad": (C.c_int, [_P, _KP, _P, _P, _P, _I64, _P, _I64, _I32, _I32, C.POINTER(_D), _I32]),
     "covgram_bilinear_input_grad": (C.c_int, [_P, _KP, _P, _P, _P, _I64, _P, _I64, _I32, C.POINTER(_D), _I32]),
     "covgram_debug_kernel_params": (C.c_int, [_KP, _I32, _I32, C.POINTER(_D)]),

@@ -688,17 +688,10 @@ class SpectralMixtureGramian(_OwnsHandle, _PointPairGramian):
         _ffi.check(_ffi.lib().covgram_sm_matrix(self.handle, self._px.handle, self._py.handle, out, ldo, _ffi.DEVICE))
 
 
-def spectral_mixture_gradient(G, U, A):
-    """(value, grad) of the bilinear form Σ_t U[:, t]ᵀ G A[:, t] = Σ_ij W_ij k(x_i, y_j), W = U Aᵀ, with respect to the weights,
-    frequencies and lengthscales of the spectral mixture G was built from, in ONE fused pass over the pairs (csrc/sm_grad.hip,
-    covgram_bilinear_grad_sm): all Q(1 + 2d) derivatives at once, W formed per pair in registers, nothing of size n × m exists.
-    `G` is a SpectralMixtureGramian; U is (n,) or (n, nvec), A (m,) or (m, nvec).  `value` is a float64 0-dim CPU tensor, `grad` a
-    float64 CPU tensor in hyperparameters(G.k) order; the chain rules from the device's numbers to the leaves of the kernel tree are
-    kernels.spectral_mixture_chain_rules.  More than 32 columns run in chunks of 32 summed in fp64.  The parameters are those the
-    handle holds: rounded once to the points' dtype.  Anything but a SpectralMixtureGramian of a tree spectral_mixture_spec accepts
-    raises UnsupportedKernel by name before any device call.  Gradients with respect to the points and autograd through the product
-    of a mixture are out of scope: bilinear_input_gradient and gram_product refuse mixtures."""
-    fn = "spectral_mixture_gradient"
+def _sm_setup(fn, G, U, A):
+    """What spectral_mixture_gradient and spectral_mixture_input_gradient (`fn`: the name in the messages) share: the refusals, before any
+    device call, and the weights as the device wants them.  Returns (U, A, Ut, At): U (n, nvec) and A (m, nvec) in the Gramian's dtype
+    on its device and their transposes (nvec, n) / (nvec, m), row-major == column-major n × nvec / m × nvec."""
     if type(G) is not SpectralMixtureGramian:
         raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"{fn}: {type(G).__name__} is not supported (the SpectralMixtureGramian of gramian(k, x[, y]) only)")
     n, m = G.shape
@@ -711,7 +704,23 @@ def spectral_mixture_gradient(G, U, A):
     A = A[:, None] if A.dim() == 1 else A
     if U.dim() != 2 or A.dim() != 2 or U.shape[1] != A.shape[1] or U.shape[1] < 1:
         raise _ffi.DimensionMismatch(_ffi.EINVAL, f"DimensionMismatch: U has shape {tuple(U.shape)}, A {tuple(A.shape)}: equal column counts expected")
-    Ut, At = U.t().contiguous(), A.t().contiguous()            # (nvec, n) row-major == column-major n × nvec
+    return U, A, U.t().contiguous(), A.t().contiguous()
+
+
+def spectral_mixture_gradient(G, U, A):
+    """(value, grad) of the bilinear form Σ_t U[:, t]ᵀ G A[:, t] = Σ_ij W_ij k(x_i, y_j), W = U Aᵀ, with respect to the weights,
+    frequencies and lengthscales of the spectral mixture G was built from, in ONE fused pass over the pairs (csrc/sm_grad.hip,
+    covgram_bilinear_grad_sm): all Q(1 + 2d) derivatives at once, W formed per pair in registers, nothing of size n × m exists.
+    `G` is a SpectralMixtureGramian; U is (n,) or (n, nvec), A (m,) or (m, nvec).  `value` is a float64 0-dim CPU tensor, `grad` a
+    float64 CPU tensor in hyperparameters(G.k) order; the chain rules from the device's numbers to the leaves of the kernel tree are
+    kernels.spectral_mixture_chain_rules.  More than 32 columns run in chunks of 32 summed in fp64.  The parameters are those the
+    handle holds: rounded once to the points' dtype.  Anything but a SpectralMixtureGramian of a tree spectral_mixture_spec accepts
+    raises UnsupportedKernel by name before any device call.  The gradients with respect to the points are
+    spectral_mixture_input_gradient, and autograd through the product of a mixture is spectral_mixture_product
+    (bilinear_input_gradient and gram_product themselves refuse mixtures)."""
+    U, A, Ut, At = _sm_setup("spectral_mixture_gradient", G, U, A)
+    n, m = G.shape
+    d = G.x.shape[1]
     nvec = U.shape[1]
     nout = int(G.w.shape[0]) * (1 + 2 * d)
     lib = _ffi.lib()
@@ -726,6 +735,45 @@ def spectral_mixture_gradient(G, U, A):
         acc += o.cpu()
     value, grad = K.spectral_mixture_chain_rules(G.k, acc.numpy(), d)
     return torch.tensor(value, dtype=torch.float64), torch.tensor(grad, dtype=torch.float64)
+
+
+def _sm_input_grad_device(G, px, py, Ut, At, rows, cols, d):
+    """covgram_bilinear_input_grad_sm with G's handle for the row points `px` against the column points `py` (None: the row points
+    themselves) as a float64 (rows, d) tensor on G's device: chunks of at most 32 of the columns of Ut (nvec, rows) and At (nvec, cols),
+    summed in fp64 on the device."""
+    lib = _ffi.lib()
+    px.ctx.bind_stream()
+    total = None
+    for c0 in range(0, Ut.shape[0], BILINEAR_MAX_NVEC):
+        nv = min(BILINEAR_MAX_NVEC, Ut.shape[0] - c0)
+        o = torch.empty((rows, d), dtype=torch.float64, device=G.device)
+        _ffi.check(lib.covgram_bilinear_input_grad_sm(G.handle, px.handle, None if py is None else py.handle, _ffi._P(Ut[c0:].data_ptr()), max(rows, 1),
+                                                      _ffi._P(At[c0:].data_ptr()), max(cols, 1), nv, C.cast(o.data_ptr(), C.POINTER(C.c_double)),
+                                                      _ffi.DEVICE))
+        total = o if total is None else total.add_(o)
+    return total
+
+
+def spectral_mixture_input_gradient(G, U, A):
+    """(dX, dY): the gradients of the bilinear form F = Σ_t U[:, t]ᵀ G A[:, t] = Σ_ij W_ij k(x_i, y_j), W = U Aᵀ, of a spectral mixture
+    with respect to the points of G, as float64 tensors (n, d) and (m, d) on G's device, in ONE fused pass over the pairs per side
+    (csrc/sm_input_grad.hip, covgram_bilinear_input_grad_sm): with r = x_i − y_j, φ_q = 2π μ_q·r and e_q = exp(−½ Σ_k (r_k / l_qk)²)
+        dX[i, c] = Σ_j W_ij Σ_q w_q e_q (−2π μ_qc sin φ_q − r_c cos φ_q / l_qc²)
+    dY is the same device call with the roles swapped, (Y, X, A, U): the mixture is symmetric in its arguments.  When G was built from
+    one point set (G.y is G.x) ONE array is returned and dY is None: dX = call(X, U, A) + call(X, A, U); when U and A are the same tensor
+    (same storage, shape and strides) that is one call, doubled (exact: both routes agree bit for bit).  A pair at distance 0 adds
+    exactly 0.  `G` is a SpectralMixtureGramian; U is (n,) or (n, nvec), A (m,) or (m, nvec); more than 32 columns run in chunks of 32
+    summed in fp64 on the device.  The parameters are those the handle holds: rounded once to the points' dtype.  Anything but a
+    SpectralMixtureGramian of a tree spectral_mixture_spec accepts raises UnsupportedKernel by name before any device call, as
+    spectral_mixture_gradient does.  The gradients are with respect to the points the Gramian HOLDS, G.x and G.y."""
+    same_weights = _same_tensor(U, A)
+    U, A, Ut, At = _sm_setup("spectral_mixture_input_gradient", G, U, A)
+    n, m = G.shape
+    d = G.x.shape[1]
+    if G._py is G._px:
+        t = _sm_input_grad_device(G, G._px, None, Ut, At, n, n, d)
+        return (2.0 * t if same_weights else t + _sm_input_grad_device(G, G._px, None, At, Ut, n, n, d)), None
+    return _sm_input_grad_device(G, G._px, G._py, Ut, At, n, m, d), _sm_input_grad_device(G, G._py, G._px, At, Ut, m, n, d)
 
 
 BLOCK_MATRIX_MAX_D = 64     # covgram_block_matrix, gradient kinds: rows in registers (include/covgram.h)

@@ -325,9 +325,10 @@ int covgram_sm_create(covgram_ctx* ctx, covgram_sm** out, int32_t ncomp, int32_t
     const bool f32 = dtype == COVGRAM_F32;
     auto rnd = [f32](double v) { return f32 ? (double)(float)v : v; };
     const int nch = (ncomp + SM_QC - 1) / SM_QC, qpad = nch * SM_QC;
-    const size_t count = (size_t)qpad + (size_t)qpad * d + (size_t)qpad * SM_CST + qpad;
+    const size_t count = sm_prm_count(qpad, d);
     std::vector<double> h(count, 0.0);
     double* hw = h.data(); double* hmu = hw + qpad; double* hc = hmu + (size_t)qpad * d; double* hi = hc + (size_t)qpad * SM_CST;
+    double* hgs = hi + qpad; double* hgc = hgs + (size_t)qpad * SM_CST; double* hgi = hgc + (size_t)qpad * SM_CST;
     bool iso = true;
     for (int q = 0; q < ncomp; ++q) {
         hw[q] = rnd(w[q]);
@@ -335,9 +336,12 @@ int covgram_sm_create(covgram_ctx* ctx, covgram_sm** out, int32_t ncomp, int32_t
             hmu[q * d + k] = rnd(mu[q * d + k]);
             const double il = rnd(inv_l[q * d + k]);
             hc[q * SM_CST + k] = rnd(0.72134752044448170368 * il * il);
+            hgs[q * SM_CST + k] = rnd(-6.283185307179586476925 * hw[q] * hmu[q * d + k]);
+            hgc[q * SM_CST + k] = rnd(hw[q] * il * il);
             if (il != rnd(inv_l[q * d])) iso = false;
         }
         hi[q] = hc[q * SM_CST];
+        hgi[q] = hgc[q * SM_CST];
     }
     CG_DEVICE(ctx);
     covgram_sm* S = new covgram_sm();

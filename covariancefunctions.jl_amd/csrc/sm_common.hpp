@@ -1,5 +1,5 @@
 // sm_common.hpp — what the units behind the covgram_sm handle share: sm.hip (product and Matrix(G)) and sm_grad.hip
-// (hyper-parameter gradients of a bilinear form).  The handle, the chunking of the components, the per-point phase kernel
+// (hyper-parameter gradients of a bilinear form) and sm_input_grad.hip (its gradients in the row points).  The handle, the chunking of the components, the per-point phase kernel
 // and the check of the points against the handle.
 #pragma once
 #include <cmath>
@@ -9,13 +9,16 @@
 struct covgram_sm {
     covgram_ctx* ctx = nullptr;
     int32_t ncomp = 0, d = 0, dtype = 0, isotropic = 0, nch = 0;
-    void* prm = nullptr;   // device, scalars of dtype: w [qpad] | mu [qpad d] | coef [qpad SM_CST] | ciso [qpad]
+    // device, scalars of dtype: w [qpad] | mu [qpad d] | coef [qpad SM_CST] | ciso [qpad] | gsin [qpad SM_CST] | gcos [qpad SM_CST] | gciso [qpad]
+    // (the last three: the input gradient's coefficients -2 pi w_q mu_qk and w_q inv_l_qk^2, formed in fp64 from the rounded parameters)
+    void* prm = nullptr;
 };
 
 namespace covgram {
 
 constexpr int SM_QC = 4;       // components per chunk
 constexpr int SM_CST = COVGRAM_SM_MAX_D;   // stride of a component's coefficient row
+inline size_t sm_prm_count(int qpad, int d) { return (size_t)qpad * (2 + d) + (size_t)qpad * SM_CST + (size_t)qpad * (2 * SM_CST + 1); }
 
 // phases of both point sets: thread = (point, component slot)
 template <typename T>

@@ -830,4 +830,14 @@ function bilinear_input_grad(G::Gramian{T}, U::StridedVecOrMat{T}, A::StridedVec
     return dX
 end
 
+# --- the same for a spectral mixture (covgram_bilinear_input_grad_sm): column i is Σ_j W_ij Σ_q w_q e_q (−2π μ_q sin φ_q − invl_q² ∘ r cos φ_q),
+#     r = x_i − y_j, the column side held fixed (also for one point set: add the call with U and A swapped)
+function bilinear_input_grad(S::DeviceSpectralMixture{T}, U::StridedVecOrMat{T}, A::StridedVecOrMat{T}) where {T <: DevFloat}
+    size(U, 1) == S.n && size(A, 1) == S.m && size(U, 2) == size(A, 2) || throw(DimensionMismatch("bilinear_input_grad: U is n × nvec, A is m × nvec"))
+    dX = Matrix{Float64}(undef, size(S.μ, 1), S.n)
+    check(ccall((:covgram_bilinear_input_grad_sm, libcovgram), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int32, Ptr{Float64}, Int32),
+                S.handle, S.X.handle, S.Y.handle, U, max(stride(U, 2), S.n), A, max(stride(A, 2), S.m), size(U, 2), dX, HOST))
+    return dX
+end
+
 end # module

@@ -74,7 +74,8 @@ extern "C" {
                                the covgram_sm_* handle (SpectralMixture Gramians: one fused product and Matrix(G));
                                covgram_bilinear_grad (hyper-parameter gradients of bilinear forms in one pass);
                                covgram_bilinear_input_grad (their gradients with respect to the row points in one pass);
-                               covgram_bilinear_grad_sm (the hyper-parameter gradients of a SpectralMixture Gramian's bilinear forms).
+                               covgram_bilinear_grad_sm (the hyper-parameter gradients of a SpectralMixture Gramian's bilinear forms);
+                               covgram_bilinear_input_grad_sm (their gradients with respect to the row points in one pass).
                                A binding checks covgram_version() against the header it mirrors at load time */
 
 typedef enum covgram_status {
@@ -682,6 +683,27 @@ int covgram_bilinear_input_grad(covgram_ctx* ctx, const covgram_kernel* k, const
  *   and never synchronises.  Option "time_kernels" brackets the phase kernels, the pair kernel and its reduction. */
 int covgram_bilinear_grad_sm(covgram_sm* S, const covgram_points* X, const covgram_points* Y, const void* U, int64_t ldu, const void* A,
                              int64_t lda, int32_t nvec, double* out, int32_t loc);
+
+/* ---- Gradients of the bilinear forms sum_t u_t' G a_t of a SpectralMixture Gramian with respect to the ROW points in ONE pass over the
+ * pairs (csrc/sm_input_grad.hip), W = U A', r, phi_q and e_q as in covgram_bilinear_grad_sm:
+ *     dX[i d + c] = sum_j W_ij sum_q w_q e_q (-2 pi mu_qc sin phi_q - inv_l_qc^2 r_c cos phi_q)        i < n, c < d
+ * the partial derivative of F(X, Y) = sum_ij W_ij sum_q w_q cos phi_q e_q in x_ic with the column side held FIXED, also when Y == NULL
+ *   (Y = X): the mixture is symmetric in its arguments (cos is even), so the derivative in the column points is the call with
+ *   (Y, X, A, U), and the full derivative of the one-point-set case is call(X, NULL, U, A) + call(X, NULL, A, U) — the conventions of
+ *   covgram_bilinear_input_grad.
+ * `dX` holds n d DOUBLES, point-major like the points, whatever the points' dtype; nothing outside them is written.  U is n x nvec
+ *   (ldu >= n), A is m x nvec (lda >= m), column-major, in the points' dtype; `loc` applies to U, A and dX.  w, mu and inv_l are the
+ *   handle's parameters as covgram_sm_create rounded them, once, to the points' dtype.
+ * X, Y and S must agree in ctx, dtype and d (COVGRAM_EINVAL, as covgram_sm_mvm); nvec outside 1 .. 32 or a NULL dX: COVGRAM_EINVAL.
+ * The phases mu_q . x_i and mu_q . y_j are formed per point and reduced in fp64; the pair loop has no trigonometric instruction
+ *   (cos phi = cu cv + su sv, sin phi = su cv - cu sv).  A pair with sum_k r_k^2 == 0 (with Y == NULL the whole diagonal) adds exactly 0
+ *   to every output: sin phi is replaced by 0 there by a select, next to cos phi := 1.  Rows and columns beyond the sets add exactly 0.
+ * A lane owns a row: it adds at most 128 pairs in the points' precision before the sum continues in fp64; the four waves' totals and the
+ *   column chunks are added in a fixed order, no atomics: two calls with the same arguments agree bit for bit.  m == 0 gives zeros,
+ *   n == 0 returns at once.  With loc == DEVICE the call is stream-ordered, never synchronises, uses the ctx workspace and allocates
+ *   nothing after the first call of a shape.  Option "time_kernels" brackets the phase kernels, the pair kernel and its reduction. */
+int covgram_bilinear_input_grad_sm(covgram_sm* S, const covgram_points* X, const covgram_points* Y, const void* U, int64_t ldu, const void* A,
+                                   int64_t lda, int32_t nvec, double* dX, int32_t loc);
 
 /* Test hook: the double-precision parameter block handed to the device kernels for `k`
  * (out45[0..8] = gamma, gamma^2, scale, param, c0, 2p+1, Taylor bound, d1, d2; then the MaternP tables
