@@ -877,6 +877,28 @@ class BlockGramian(LazyOperator):
             _ffi.DEVICE)))
 
 
+class MixedBlockGramian(BlockGramian):
+    """Gramian of GradientKernel(k) / ValueGradientKernel(k) for a Sum / Product / Power whose factors do not share one input trait
+    (the reference's gradient algebra, src/gradient_algebra.jl:6-89, e.g. MaternP(2) + Dot()**2 + NeuralNetwork()): ONE fused pass of
+    covgram_grad_mvm_mixed, every factor a function of (x·y, |x|², |y|²).  Matrix(G), block() and [] are the product applied to
+    identity columns on the sliced point sets."""
+
+    def _lower(self):
+        return K.require_mixed_gradient_spec(self.g.k)
+
+    def _dense(self, inner):
+        sub = self if inner is self.inner else type(self)(self.g, inner.x, None if inner.y is inner.x else inner.y)
+        return LazyOperator.to_dense(sub)
+
+    def mul_(self, y, a, alpha=1.0, beta=0.0):
+        spec = self._lower()
+        a = _rhs(self, y, a)
+        ctx = self.inner._px.ctx.bind_stream()
+        return _staged(y, a, beta, lambda ap, lda, yp, ldy, nrhs: _ffi.check(_ffi.lib().covgram_grad_mvm_mixed(
+            ctx, C.byref(spec), self.inner._px.handle, self.inner._py.handle, _ffi._P(ap), lda, _ffi._P(yp), ldy, nrhs, float(alpha), float(beta),
+            1 if self.value else 0, _ffi.DEVICE)))
+
+
 class HessianGramian(BlockGramian):
     """Gramian of a HessianKernel: the lazy (n d²)×(m d²) BlockFactorization whose blocks are ∂⁴k / ∂x∂x∂y∂y (src/hessian.jl:33-41),
     applied in O(d²) per pair by covgram_hess_mvm.  Block vectors are point-major, entry i d² + a + b d."""
@@ -1586,6 +1608,8 @@ def gramian(k, x=None, y=None, trait: Optional[K.InputTrait] = None):
         return CosineBlockGramian(torch.as_tensor(k.k.c, dtype=px.dtype, device=px.device), _cosine_lowrank(k.k, px, py, same))
 
     if isinstance(k, (K.GradientKernel, K.ValueGradientKernel)):   # src/gramian.jl:120-123
+        if isinstance(k.k, K.AbstractKernel) and K.device_spec(k.k) is None and K.mixed_gradient_spec(k.k) is not None:
+            return MixedBlockGramian(k, x, None if same else y)     # factors of different traits: src/gradient_algebra.jl
         return BlockGramian(k, x, None if same else y)
     if isinstance(k, K.HessianKernel):
         return HessianGramian(k, x, None if same else y)

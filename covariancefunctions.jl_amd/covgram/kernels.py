@@ -763,6 +763,122 @@ def require_device_spec(k):
 
 
 # ----------------------------------------------------------------------------------------------
+# gradient kernels of mixed-trait composites (src/gradient_algebra.jl): the composite of covgram_grad_mvm_mixed
+# ----------------------------------------------------------------------------------------------
+class _MixedRefusal(Exception):
+    pass
+
+
+def _mixed_leaf_refusal(k):
+    """Why the leaf `k` has no jet in the mixed gradient kernels, or None."""
+    if isinstance(k, CosineKernel):
+        return f"{type(k).__name__} belongs with the gradient kernels of spectral mixtures"
+    return None
+
+
+def _mixed_expand(k, budget=64):
+    """_expand for the mixed gradient kernels: the same sum-of-products normal form, with NeuralNetwork(σ) as a leaf of its own
+    (family NEURALNETWORK, trait 0, σ in param) and the leaves without a jet refused by name (_MixedRefusal)."""
+    if isinstance(k, Constant):
+        return [(k.c, [])]
+    if isinstance(k, NeuralNetwork):
+        s = _ffi.covgram_kernel()
+        s.family, s.trait, s.p, s.power = _ffi.NEURALNETWORK, 0, 0, 1
+        s.param, s.lengthscale, s.scale = k.sigma, 1.0, 1.0
+        return [(1.0, [s])]
+    s = _simple_spec(k)
+    if s is not None:
+        leaf = k
+        while isinstance(leaf, (Product, Power, Lengthscale)):
+            leaf = [a for a in leaf.args if not isinstance(a, Constant)][0] if isinstance(leaf, Product) else leaf.k
+        name = type(leaf).__name__                           # (a half-integer Matern has lowered to MaternP: judged as such)
+        if s.family in (_ffi.EXP, _ffi.GAMMAEXP) or (s.family == _ffi.MATERNP and s.p == 0):
+            raise _MixedRefusal(f"{name}{'(0)' if isinstance(leaf, MaternP) else ''} is singular at zero distance")
+        if s.family == _ffi.MATERN:
+            raise _MixedRefusal(f"{name}(ν = {leaf.nu}) has no closed-form jet here (MaternP does)")
+        c, s.scale = s.scale, 1.0
+        return [(c, [s])]
+    if isinstance(k, Sum):
+        out = []
+        for a in k.args:
+            out += _mixed_expand(a, budget)
+        if len(out) > budget:
+            raise _MixedRefusal(f"the expression multiplies out to more than {budget} terms")
+        return out
+    if isinstance(k, Product) or (isinstance(k, Power) and k.p >= 1):
+        parts = k.args if isinstance(k, Product) else (k.k,) * k.p
+        out = [(1.0, [])]
+        for a in parts:
+            e = _mixed_expand(a, budget)
+            out = [(c1 * c2, f1 + f2) for (c1, f1) in out for (c2, f2) in e]
+            if len(out) > budget:
+                raise _MixedRefusal(f"the expression multiplies out to more than {budget} terms")
+        return out
+    why = _mixed_leaf_refusal(k)
+    raise _MixedRefusal(why if why is not None else f"{type(k).__name__} is not a Sum / Product / Power / Constant / Lengthscale over the supported leaves")
+
+
+def _mixed_lower(k):
+    """(composite, None) or (None, reason)."""
+    try:
+        terms = _mixed_expand(k)
+    except _MixedRefusal as e:
+        return None, str(e)
+    key_of = lambda f: (f.family, f.p, f.param, f.lengthscale)
+    merged = {}
+    for c, fs in terms:
+        byleaf = {}
+        for f in fs:                                          # identical leaves of a term multiply into one factor: φ^a φ^b = φ^(a+b)
+            if key_of(f) in byleaf:
+                byleaf[key_of(f)].power += f.power
+            else:
+                g = _ffi.covgram_kernel(); _copy_spec(g, f); byleaf[key_of(f)] = g
+        fs = sorted(byleaf.values(), key=lambda f: key_of(f) + (f.power,))
+        key = tuple(key_of(f) + (f.power,) for f in fs)
+        merged[key] = (merged[key][0] + c if key in merged else c, fs)
+    terms = [(c, fs) for key, (c, fs) in merged.items() if c != 0.0]
+    if not terms:
+        terms = [(0.0, [])]
+    nfac = sum(max(len(fs), 1) for _, fs in terms)
+    if len(terms) > _ffi.COMPOSITE_MAX_TERMS or nfac > _ffi.COMPOSITE_MAX_FACTORS:
+        return None, (f"the normal form has {len(terms)} terms and {nfac} factors; the composite holds {_ffi.COMPOSITE_MAX_TERMS} terms "
+                      f"and {_ffi.COMPOSITE_MAX_FACTORS} factors")
+    comp = _ffi.covgram_kernel_composite()
+    comp.head.family, comp.head.trait, comp.head.p, comp.head.power = _ffi.COMPOSITE, 0, 0, 1
+    comp.head.param, comp.head.lengthscale, comp.head.scale = 0.0, 1.0, 1.0
+    comp.nterms = len(terms)
+    fi = 0
+    for t, (c, fs) in enumerate(terms):
+        if not fs:
+            comp.nfactors[t] = 1
+            comp.factors[fi].family, comp.factors[fi].trait, comp.factors[fi].power = _ffi.CONSTANT, 0, 1
+            comp.factors[fi].lengthscale, comp.factors[fi].scale = 1.0, c
+            fi += 1
+            continue
+        comp.nfactors[t] = len(fs)
+        for q, f in enumerate(fs):
+            _copy_spec(comp.factors[fi], f)
+            comp.factors[fi].scale = c if q == 0 else 1.0     # the term's coefficient rides on its first factor
+            fi += 1
+    return comp, None
+
+
+def mixed_gradient_spec(k):
+    """The covgram_kernel_composite that covgram_grad_mvm_mixed runs for GradientKernel(k) / ValueGradientKernel(k), or None: Sum /
+    Product / Power / Constant / Lengthscale over the leaves with a jet in (x·y, |x|², |y|²) — the isotropic profiles that are smooth
+    at zero distance (EQ, RQ, Cauchy, InverseMultiQuadratic, MaternP(p ≥ 1)), Dot, ExponentialDot, AsinDot and NeuralNetwork(σ) — in
+    the normal form of device_spec, EVERY FACTOR WITH ITS OWN TRAIT (the head's is 0), within the same limits (8 terms, 8 factors)."""
+    return _mixed_lower(k)[0] if isinstance(k, AbstractKernel) else None
+
+
+def require_mixed_gradient_spec(k):
+    spec, why = _mixed_lower(k) if isinstance(k, AbstractKernel) else (None, f"{type(k).__name__} is not a kernel expression")
+    if spec is None:
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"gradient kernel of a mixed-trait composite ({type(k).__name__}): {why}")
+    return spec
+
+
+# ----------------------------------------------------------------------------------------------
 # hyper-parameters: the ordered leaves of a kernel expression (the role of parameters / Base.similar in src/parameters.jl)
 # ----------------------------------------------------------------------------------------------
 _OWN_PARAMETER = {RationalQuadratic: "alpha", GammaExponential: "gamma", InverseMultiQuadratic: "c"}

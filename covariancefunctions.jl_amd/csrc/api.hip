@@ -708,12 +708,13 @@ static const CtxField kOptions[] = {
     CG_FIELD(mfma_gate_pct), CG_FIELD(mfma_fuse_w), CG_FIELD(toeplitz_real_spectrum), CG_FIELD(rows_per_lane), CG_FIELD(jsplit), CG_FIELD(target_wgs),
     CG_FIELD(grad_keep_r), CG_FIELD(grad_expand), CG_FIELD(grad_bcast), CG_FIELD(mfma_lds), CG_FIELD(mfma_sym), CG_FIELD(dense_sym), CG_FIELD(dense_bcast),
     CG_FIELD(mfma_stamp), CG_FIELD(mfma_graded), CG_FIELD(inkernel_reduce), CG_FIELD(matrix_variant), CG_FIELD(mfma_mrhs), CG_FIELD(composite_termwise), CG_FIELD(sum_fused),
-    CG_FIELD(lowrank_reverse), CG_FIELD(mfma_sym_rt), CG_FIELD(mfma_sym_st), CG_FIELD(lowrank_wgs), CG_FIELD(time_kernels)};
+    CG_FIELD(lowrank_reverse), CG_FIELD(mfma_sym_rt), CG_FIELD(mfma_sym_st), CG_FIELD(lowrank_wgs), CG_FIELD(grad_mixed_panel), CG_FIELD(time_kernels)};
 static const CtxField kInfo[] = {
     CG_FIELD(last_dense_path), CG_FIELD(last_jsplit), CG_FIELD(last_kron_path), CG_FIELD(last_mfma_lds), CG_FIELD(last_mfma_sym), CG_FIELD(last_dense_sym),
     CG_FIELD(last_dense_bcast), CG_FIELD(last_mfma_f16), CG_FIELD(last_inkernel_reduce), CG_FIELD(last_grad_expand), CG_FIELD(last_grad_bcast),
     CG_FIELD(last_grad_path), CG_FIELD(last_grad_jsplit), CG_FIELD(last_hess_path), CG_FIELD(last_vgh_path), CG_FIELD(last_matrix_path),
-    CG_FIELD(last_block_matrix_path), CG_FIELD(last_sum_fused), CG_FIELD(last_mfma_instance), CG_FIELD(last_mfma_graded), CG_FIELD(last_mfma_sym_rt), CG_FIELD(num_cus)};
+    CG_FIELD(last_block_matrix_path), CG_FIELD(last_sum_fused), CG_FIELD(last_mfma_instance), CG_FIELD(last_mfma_graded), CG_FIELD(last_mfma_sym_rt), CG_FIELD(last_grad_mixed_path),
+    CG_FIELD(last_grad_mixed_jsplit), CG_FIELD(num_cus)};
 #undef CG_FIELD
 
 int covgram_ctx_set_option(covgram_ctx* ctx, const char* key, int64_t value) {

@@ -310,6 +310,9 @@ struct covgram_ctx {
     int64_t last_vgh_path = 0;    // 1: the last covgram_valgradhess_mvm ran hess_mvm_kernel<VGH = true> (0: none yet, or no columns / rows)
     int64_t last_block_matrix_path = 0; // covgram_block_matrix: (kind + 1) + 10 VR (include/covgram.h, "last_block_matrix_path"); 0: none yet, or an empty product
     int64_t last_mfma_lds = 0;   // the last matrix-core EQ MVM shared its column tiles through LDS
+    int64_t grad_mixed_panel = 0;       // covgram_grad_mvm_mixed, panel route: cap on the columns of a panel (0 = the 256 MB rule of the coefficient slabs)
+    int64_t last_grad_mixed_path = 0;   // kernels of the last covgram_grad_mvm_mixed, bits: 1 lane-per-row, 2 panel route, 4 more than one panel, 8 z slices + reduce, 16 column split + slab reduce
+    int64_t last_grad_mixed_jsplit = 0; // column split of its lane-per-row launch (0: it did not run one)
     // optional HIP-event bracketing of the dominant kernel of each MVM (bench.py's live roofline measurement)
     int64_t time_kernels = 0;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> timers;

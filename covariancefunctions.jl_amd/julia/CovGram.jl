@@ -245,11 +245,47 @@ function device_blockmul!(sym::Symbol, y::StridedVecOrMat{T}, G::Gramian, a::Str
     end
     return y
 end
+
+# --- src/gradient_algebra.jl:6-89: GradientKernel / ValueGradientKernel of a Sum / Product whose factors do NOT share one trait
+# (input_trait = GenericInput, e.g. MaternP(2) + Dot()^2 + NN()) -> covgram_grad_mvm_mixed, the entry that reads every factor's own
+# trait.  Leaves: the profiles of `lower` that are smooth at zero distance, and NeuralNetwork(σ) as family 102 with σ in param.
+# (covgram/kernels.py::mixed_gradient_spec is the executed version of this flattening, including Power over sums.)
+const F_NEURALNETWORK = Int32(102)
+lower_mixed_leaf(k) = (f = lower(k); (f === nothing || f.family in (F_EXP, F_GAMMAEXP) || (f.family == F_MATERNP && f.p == 0)) ? nothing : f)
+lower_mixed_leaf(k::CovarianceFunctions.NeuralNetwork) = CKernel(F_NEURALNETWORK, Int32(0), Int32(0), Int32(1), Float64(k.σ), 1.0, 1.0)
+lower_mixed_leaf(k::Constant) = CKernel(F_CONSTANT, Int32(0), Int32(0), Int32(1), 0.0, 1.0, Float64(k.c))
+function lower_mixed(k)
+    terms = k isa Sum ? collect(k.args) : [k]
+    length(terms) ≤ COMPOSITE_MAX_TERMS || return nothing
+    nfac = zeros(Int32, COMPOSITE_MAX_TERMS); facs = CKernel[]
+    for (t, term) in enumerate(terms)
+        for part in (term isa Product ? collect(term.args) : [term])
+            f = lower_mixed_leaf(part)
+            f === nothing && return nothing
+            push!(facs, f); nfac[t] += 1
+        end
+    end
+    length(facs) ≤ COMPOSITE_MAX_FACTORS || return nothing
+    while length(facs) < COMPOSITE_MAX_FACTORS; push!(facs, NOKERNEL); end
+    CComposite(CKernel(F_COMPOSITE, Int32(0), Int32(0), Int32(1), 0.0, 1.0, 1.0), Int32(length(terms)), Tuple(nfac), Tuple(facs))
+end
+# the hook of the block mul! methods below: the mixed composite where the kernel has one, else the reference's own blockmul!
+function mixed_or(G::Gramian, value::Integer, y::StridedVecOrMat{T}, a::StridedVecOrMat{T}, α, β, fallback) where {T <: DevFloat}
+    spec = ENABLED[] && input_trait(G.k.k) isa GenericInput ? lower_mixed(G.k.k) : nothing
+    spec === nothing && return fallback()
+    X = points(G.x, T); Y = G.x === G.y ? X : points(G.y, T)
+    size(y, 2) == size(a, 2) || throw(DimensionMismatch("mul!: y has $(size(y, 2)) columns, a has $(size(a, 2))"))
+    check(ccall((:covgram_grad_mvm_mixed, libcovgram), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int32, Float64, Float64, Int32, Int32),
+                ctx(), Ref(spec), X.handle, Y.handle, a, max(stride(a, 2), size(a, 1)), y, max(stride(y, 2), size(y, 1)), Int32(size(a, 2)),
+                Float64(α), Float64(β), Int32(value), HOST))
+    return y
+end
 function LinearAlgebra.mul!(y::StridedVector{T}, B::BlockFactorizations.BlockFactorization{T, <:Gramian{<:Any, <:GradientKernel}},
                             a::StridedVector{T}, α::Real = 1, β::Real = 0) where {T <: DevFloat}
     G = B.A
     spec = device_kernel_for(G.k.k)
-    spec === nothing ? invoke(mul!, Tuple{AbstractVector, BlockFactorizations.BlockFactorization, AbstractVector, Real, Real}, y, B, a, α, β) :
+    spec === nothing ? mixed_or(G, 0, y, a, α, β, () -> invoke(mul!, Tuple{AbstractVector, BlockFactorizations.BlockFactorization, AbstractVector, Real, Real}, y, B, a, α, β)) :
                        device_blockmul!(:grad, y, G, a, α, β, spec)
 end
 # matrix right-hand sides (src/gramian.jl:241-257: AbstractVecOfVecOrMat): one library call for all columns
@@ -257,21 +293,21 @@ function LinearAlgebra.mul!(Y::StridedMatrix{T}, B::BlockFactorizations.BlockFac
                             A::StridedMatrix{T}, α::Real = 1, β::Real = 0) where {T <: DevFloat}
     G = B.A
     spec = device_kernel_for(G.k.k)
-    spec === nothing ? invoke(mul!, Tuple{AbstractMatrix, BlockFactorizations.BlockFactorization, AbstractMatrix, Real, Real}, Y, B, A, α, β) :
+    spec === nothing ? mixed_or(G, 0, Y, A, α, β, () -> invoke(mul!, Tuple{AbstractMatrix, BlockFactorizations.BlockFactorization, AbstractMatrix, Real, Real}, Y, B, A, α, β)) :
                        device_blockmul!(:grad, Y, G, A, α, β, spec)
 end
 function LinearAlgebra.mul!(y::StridedVector{T}, B::BlockFactorizations.BlockFactorization{T, <:Gramian{<:Any, <:ValueGradientKernel}},
                             a::StridedVector{T}, α::Real = 1, β::Real = 0) where {T <: DevFloat}
     G = B.A
     spec = device_kernel_for(G.k.k)
-    spec === nothing ? invoke(mul!, Tuple{AbstractVector, BlockFactorizations.BlockFactorization, AbstractVector, Real, Real}, y, B, a, α, β) :
+    spec === nothing ? mixed_or(G, 1, y, a, α, β, () -> invoke(mul!, Tuple{AbstractVector, BlockFactorizations.BlockFactorization, AbstractVector, Real, Real}, y, B, a, α, β)) :
                        device_blockmul!(:valgrad, y, G, a, α, β, spec)
 end
 function LinearAlgebra.mul!(Y::StridedMatrix{T}, B::BlockFactorizations.BlockFactorization{T, <:Gramian{<:Any, <:ValueGradientKernel}},
                             A::StridedMatrix{T}, α::Real = 1, β::Real = 0) where {T <: DevFloat}
     G = B.A
     spec = device_kernel_for(G.k.k)
-    spec === nothing ? invoke(mul!, Tuple{AbstractMatrix, BlockFactorizations.BlockFactorization, AbstractMatrix, Real, Real}, Y, B, A, α, β) :
+    spec === nothing ? mixed_or(G, 1, Y, A, α, β, () -> invoke(mul!, Tuple{AbstractMatrix, BlockFactorizations.BlockFactorization, AbstractMatrix, Real, Real}, Y, B, A, α, β)) :
                        device_blockmul!(:valgrad, Y, G, A, α, β, spec)
 end
 

@@ -75,7 +75,9 @@ extern "C" {
                                covgram_bilinear_grad (hyper-parameter gradients of bilinear forms in one pass);
                                covgram_bilinear_input_grad (their gradients with respect to the row points in one pass);
                                covgram_bilinear_grad_sm (the hyper-parameter gradients of a SpectralMixture Gramian's bilinear forms);
-                               covgram_bilinear_input_grad_sm (their gradients with respect to the row points in one pass).
+                               covgram_bilinear_input_grad_sm (their gradients with respect to the row points in one pass);
+                               covgram_grad_mvm_mixed, the factor family COVGRAM_NEURALNETWORK, the option "grad_mixed_panel" and the
+                               info keys "last_grad_mixed_path" / "last_grad_mixed_jsplit" (gradient Gramians of mixed-trait composites).
                                A binding checks covgram_version() against the header it mirrors at load time */
 
 typedef enum covgram_status {
@@ -105,7 +107,10 @@ typedef enum covgram_family {
     COVGRAM_NFAMILY = 11,
     /* only inside / as the head of a covgram_kernel_composite: */
     COVGRAM_CONSTANT = 100, /* factor: the constant `scale`            src/stationary.jl:27-34   */
-    COVGRAM_COMPOSITE = 101 /* head of a covgram_kernel_composite      src/algebra.jl:5-63       */
+    COVGRAM_COMPOSITE = 101, /* head of a covgram_kernel_composite      src/algebra.jl:5-63       */
+    /* only as a factor of the composite passed to covgram_grad_mvm_mixed: */
+    COVGRAM_NEURALNETWORK = 102 /* factor: NeuralNetwork(sigma) on the RAW points, (2/pi) asin((x.y + sigma) / sqrt((1 + |x|^2 + sigma)
+                                   (1 + |y|^2 + sigma))); param = sigma >= 0, trait = 0 (neither trait), lengthscale = 1   src/mercer.jl:73-85 */
 } covgram_family;
 
 /* input_trait(k), src/properties.jl:31-45.  Only the two traits with a device path are encoded;
@@ -328,6 +333,31 @@ int covgram_grad_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram_po
  * Aliasing (covgram_grad_mvm and covgram_valgrad_mvm): a and y may overlap in any way; a is then read from a private copy. */
 int covgram_valgrad_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, const void* a,
                         int64_t lda, void* y, int64_t ldy, int32_t nrhs, double alpha, double beta, int32_t loc);
+
+/* The same two block Gramians for a Sum / Product / Power whose factors do NOT share one input trait — GenericInput in the reference's
+ * terms, its gradient algebra of src/gradient_algebra.jl:6-36 (Sum) and :47-89 (Product) — in ONE fused pass over the pairs.
+ * value = 0: the blocks and vectors of covgram_grad_mvm; value = 1: those of covgram_valgrad_mvm (blocks of d + 1, the value first).
+ * k is the composite of covgram_kernel_composite, k(x, y) = head.scale sum_t prod_f factor(x, y); this entry is the one that reads the
+ * `trait` of every factor instead of the head's (head.trait is not read; head.power = 1 and head.lengthscale = 1 as everywhere).
+ * Factors: COVGRAM_CONSTANT; the isotropic profiles that are smooth at zero distance — EQ, RQ, Cauchy, IMQ, MaternP(p >= 1) —, each
+ * with its own lengthscale, on |x - y|^2 formed by direct differences of the stored coordinates (no centring, no expanded form); the
+ * dot-product profiles Dot, ExponentialDot, AsinDot on x.y; COVGRAM_NEURALNETWORK (param = sigma) on the raw points; every one with
+ * its own power >= 1 and scale.  Exponential, GammaExponential, MaternP(0) (singular at zero distance) and Matern(nu) are
+ * COVGRAM_EUNSUPPORTED with a message that names the leaf.  Every factor is a function F(p, q, s) of p = x.y, q = |x|^2, s = |y|^2; the
+ * composite's first and second partial derivatives follow from the factors' by the sum and Leibniz rules, and block (i, j) applied to
+ * a_j costs O(d):  b_i += F_p a_j + (F_pp t + 2 F_ps w) y_j + 2 (F_qp t + 2 F_qs w) x_i,  t = x_i.a_j, w = y_j.a_j.  A product that is
+ * zero at a pair is an ordinary number here (the reference throws DomainError there, src/gradient_algebra.jl:74-76).
+ * Routes (info key "last_grad_mixed_path", bits: 1 = lane per block row, padded d <= 32; 2 = the two-kernel panel route for wider
+ * points; 4 = more than one panel; 8 = the panel's column blocks split over z slices with a fixed-order reduce; 16 = the lane-per-row
+ * launch split over the columns with the slab reduce — "last_grad_mixed_jsplit" is that split, 0 if the route did not run; 0 = no block
+ * kernel ran: n = 0 or m = 0).  Option "grad_mixed_panel" (0 = automatic: the coefficient slabs within 256 MB) caps the columns of a
+ * panel, rounded up to whole column blocks; options "jsplit" and "target_wgs" act on the lane-per-row route as on covgram_grad_mvm.
+ * y <- alpha G a + beta y; beta == 0 never reads y; m = 0 gives beta y; nrhs columns run one after the other.  Option "time_kernels"
+ * brackets the lane-per-row kernel and the panel route's two kernels.
+ * Aliasing: a and y may overlap in any way; a is then read from a private copy. */
+int covgram_grad_mvm_mixed(covgram_ctx* ctx, const covgram_kernel_composite* k, const covgram_points* X, const covgram_points* Y,
+                           const void* a, int64_t lda, void* y, int64_t ldy, int32_t nrhs, double alpha, double beta, int32_t value,
+                           int32_t loc);
 
 /* Hessian-kernel Gramian (n d^2 × m d^2), src/hessian.jl:33-41: block (i,j) is the d^2 × d^2 matrix
  *     T[(a,b),(c,e)] = d^4 k(x_i, y_j) / dx_a dx_b dy_c dy_e,
