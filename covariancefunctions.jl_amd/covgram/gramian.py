@@ -866,15 +866,18 @@ class BlockGramian(LazyOperator):
         sub = self.block(slice(p0, p1), slice(q0, q1))
         return sub[ri][..., rj]
 
+    def _mvm(self, ctx, spec, px, py, ap, lda, yp, ldy, nrhs, alpha, beta):
+        """The library call of mul_ on device-resident a and y."""
+        return self._entry()(ctx, _ffi.kref(spec), px, py, ap, lda, yp, ldy, nrhs, alpha, beta, _ffi.DEVICE)
+
     def mul_(self, y, a, alpha=1.0, beta=0.0):
         """Matrix right-hand sides (block solvers; src/gramian.jl:241-257 takes vectors of matrices) go down in ONE library call: the
         library shares the pair evaluations between two columns at a time where its kernel holds two accumulators."""
         spec = self._lower()
         a = _rhs(self, y, a)
         ctx = self.inner._px.ctx.bind_stream()
-        return _staged(y, a, beta, lambda ap, lda, yp, ldy, nrhs: _ffi.check(self._entry()(
-            ctx, _ffi.kref(spec), self.inner._px.handle, self.inner._py.handle, _ffi._P(ap), lda, _ffi._P(yp), ldy, nrhs, float(alpha), float(beta),
-            _ffi.DEVICE)))
+        return _staged(y, a, beta, lambda ap, lda, yp, ldy, nrhs: _ffi.check(self._mvm(
+            ctx, spec, self.inner._px.handle, self.inner._py.handle, _ffi._P(ap), lda, _ffi._P(yp), ldy, nrhs, float(alpha), float(beta))))
 
 
 class MixedBlockGramian(BlockGramian):
@@ -890,13 +893,8 @@ class MixedBlockGramian(BlockGramian):
         sub = self if inner is self.inner else type(self)(self.g, inner.x, None if inner.y is inner.x else inner.y)
         return LazyOperator.to_dense(sub)
 
-    def mul_(self, y, a, alpha=1.0, beta=0.0):
-        spec = self._lower()
-        a = _rhs(self, y, a)
-        ctx = self.inner._px.ctx.bind_stream()
-        return _staged(y, a, beta, lambda ap, lda, yp, ldy, nrhs: _ffi.check(_ffi.lib().covgram_grad_mvm_mixed(
-            ctx, C.byref(spec), self.inner._px.handle, self.inner._py.handle, _ffi._P(ap), lda, _ffi._P(yp), ldy, nrhs, float(alpha), float(beta),
-            1 if self.value else 0, _ffi.DEVICE)))
+    def _mvm(self, ctx, spec, px, py, ap, lda, yp, ldy, nrhs, alpha, beta):
+        return _ffi.lib().covgram_grad_mvm_mixed(ctx, C.byref(spec), px, py, ap, lda, yp, ldy, nrhs, alpha, beta, 1 if self.value else 0, _ffi.DEVICE)
 
 
 class HessianGramian(BlockGramian):

@@ -652,37 +652,36 @@ def _simple_spec(k) -> Optional[_ffi.covgram_kernel]:
     return spec
 
 
-def _expand(k, budget=64):
-    """Sum-of-products normal form of a kernel expression: list of (coefficient, [simple specs]), or None.
+class _Refusal(Exception):
+    """An expression without a normal form; the message says why."""
 
-    Sum concatenates, Product distributes over sums, Power of a composite multiplies out; a Constant is a bare
-    coefficient.  Anything without a compiled profile (closures, Matern(ν), FiniteBasis, ...) gives None."""
+
+def _normal_form(k, leaf, budget=64):
+    """Sum-of-products normal form of a kernel expression: list of (coefficient, [leaf specs]).
+
+    Sum concatenates, Product distributes over sums, Power of a composite multiplies out; a Constant is a bare coefficient.
+    `leaf(k)` is the covgram_kernel of a leaf (its scale moves into the coefficient), None where k is none, or raises _Refusal
+    for a leaf it will not take.  Anything else — and more than `budget` terms — raises _Refusal."""
     if isinstance(k, Constant):
         return [(k.c, [])]
-    s = _simple_spec(k)
+    s = leaf(k)
     if s is not None:
         c, s.scale = s.scale, 1.0
         return [(c, [s])]
     if isinstance(k, Sum):
-        out = []
-        for a in k.args:
-            e = _expand(a, budget)
-            if e is None:
-                return None
-            out += e
-        return out if len(out) <= budget else None
-    if isinstance(k, Product) or (isinstance(k, Power) and k.p >= 1):
-        parts = k.args if isinstance(k, Product) else (k.k,) * k.p
+        out = [term for a in k.args for term in _normal_form(a, leaf, budget)]
+    elif isinstance(k, Product) or (isinstance(k, Power) and k.p >= 1):
         out = [(1.0, [])]
-        for a in parts:
-            e = _expand(a, budget)
-            if e is None:
-                return None
+        for a in (k.args if isinstance(k, Product) else (k.k,) * k.p):
+            e = _normal_form(a, leaf, budget)
             out = [(c1 * c2, f1 + f2) for (c1, f1) in out for (c2, f2) in e]
             if len(out) > budget:
-                return None
-        return out
-    return None
+                break
+    else:
+        raise _Refusal(f"{type(k).__name__} is not a Sum / Product / Power / Constant / Lengthscale over the supported leaves")
+    if len(out) > budget:
+        raise _Refusal(f"the expression multiplies out to more than {budget} terms")
+    return out
 
 
 def _copy_spec(dst, src):
@@ -690,58 +689,41 @@ def _copy_spec(dst, src):
         setattr(dst, name, getattr(src, name))
 
 
-def device_spec(k):
-    """What the device runs for `k`: a covgram_kernel (single profile), a covgram_kernel_composite (Sum / Product /
-    Power of kernels sharing one input trait, src/algebra.jl:5-63 with the trait rule of src/properties.jl:47-63),
-    or None if k is GenericInput in the reference's terms or exceeds the composite limits (4 terms, 6 factors)."""
-    s = _simple_spec(k)
-    if s is not None:
-        return s
-    terms = _expand(k)
-    if not terms:
-        return None
-    # within a term, identical profiles multiply into one factor with a higher Power: phi^a phi^b = phi^(a+b)
-    def _pow_merge(fs):
-        out = {}
-        for f in fs:
-            key = (f.family, f.p, f.param, f.lengthscale)
-            if key in out:
-                out[key].power += f.power
-            else:
-                g = _ffi.covgram_kernel(); _copy_spec(g, f); out[key] = g
-        return list(out.values())
-    terms = [(c, _pow_merge(fs)) for c, fs in terms]
-    # merge like terms (pure constants included), drop zero terms
+def _merge_leaf_powers(fs):
+    """Within a term, identical leaves multiply into one factor with a higher Power: φ^a φ^b = φ^(a+b)."""
+    out = {}
+    for f in fs:
+        key = (f.family, f.p, f.param, f.lengthscale)
+        if key in out:
+            out[key].power += f.power
+        else:
+            g = _ffi.covgram_kernel(); _copy_spec(g, f); out[key] = g
+    return list(out.values())
+
+
+def _merge_like_terms(terms, key_of):
+    """{factor keys: (coefficient, factors)}: like leaves merged, each term's factors sorted by `key_of`, like terms (pure
+    constants included, under the key ()) added up where the first of them stood."""
     merged = {}
     for c, fs in terms:
-        fs = sorted(fs, key=lambda f: (f.family, f.p, f.power, f.param, f.lengthscale))
-        key = tuple((f.family, f.p, f.power, f.param, f.lengthscale) for f in fs)
-        if key in merged:
-            merged[key] = (merged[key][0] + c, fs)
-        else:
-            merged[key] = (c, fs)
-    terms = [(c, fs) for key, (c, fs) in merged.items() if key and c != 0.0]
-    if () in merged and merged[()][0] != 0.0:
-        terms.append((merged[()][0], []))
-    traits = {f.trait for _, fs in terms for f in fs}
-    if len(traits) != 1:
-        return None                                           # mixed traits: GenericInput (src/properties.jl:56-62)
-    nfac = sum(max(len(fs), 1) for _, fs in terms)
-    if not (1 <= len(terms) <= _ffi.COMPOSITE_MAX_TERMS) or nfac > _ffi.COMPOSITE_MAX_FACTORS:
-        return None
+        fs = sorted(_merge_leaf_powers(fs), key=key_of)
+        key = tuple(key_of(f) for f in fs)
+        merged[key] = (merged[key][0] + c if key in merged else c, fs)
+    return merged
+
+
+def _composite(terms, trait):
+    """The covgram_kernel_composite of (coefficient, factors) terms under the head trait `trait`; the caller has checked the limits."""
     comp = _ffi.covgram_kernel_composite()
-    comp.head.family = _ffi.COMPOSITE
-    comp.head.trait = traits.pop()
-    comp.head.p, comp.head.power = 0, 1
+    comp.head.family, comp.head.trait, comp.head.p, comp.head.power = _ffi.COMPOSITE, trait, 0, 1
     comp.head.param, comp.head.lengthscale, comp.head.scale = 0.0, 1.0, 1.0
     comp.nterms = len(terms)
     fi = 0
     for t, (c, fs) in enumerate(terms):
         if not fs:
             comp.nfactors[t] = 1
-            comp.factors[fi].family = _ffi.CONSTANT
-            comp.factors[fi].trait = comp.head.trait
-            comp.factors[fi].power, comp.factors[fi].lengthscale, comp.factors[fi].scale = 1, 1.0, c
+            comp.factors[fi].family, comp.factors[fi].trait, comp.factors[fi].power = _ffi.CONSTANT, trait, 1
+            comp.factors[fi].lengthscale, comp.factors[fi].scale = 1.0, c
             fi += 1
             continue
         comp.nfactors[t] = len(fs)
@@ -750,6 +732,35 @@ def device_spec(k):
             comp.factors[fi].scale = c if q == 0 else 1.0     # the term's coefficient rides on its first factor
             fi += 1
     return comp
+
+
+def _within_limits(terms):
+    nfac = sum(max(len(fs), 1) for _, fs in terms)
+    return len(terms) <= _ffi.COMPOSITE_MAX_TERMS and nfac <= _ffi.COMPOSITE_MAX_FACTORS, nfac
+
+
+def device_spec(k):
+    """What the device runs for `k`: a covgram_kernel (single profile), a covgram_kernel_composite (Sum / Product /
+    Power of kernels sharing one input trait, src/algebra.jl:5-63 with the trait rule of src/properties.jl:47-63),
+    or None if k is GenericInput in the reference's terms or exceeds the composite limits (8 terms, 8 factors)."""
+    s = _simple_spec(k)
+    if s is not None:
+        return s
+    try:                                                      # leaves: the compiled profiles (no closures, FiniteBasis, ...)
+        terms = _normal_form(k, _simple_spec)
+    except _Refusal:
+        return None
+    merged = _merge_like_terms(terms, lambda f: (f.family, f.p, f.power, f.param, f.lengthscale))
+    # zero terms drop out; the pure constant goes last
+    terms = [(c, fs) for key, (c, fs) in merged.items() if key and c != 0.0]
+    if () in merged and merged[()][0] != 0.0:
+        terms.append(merged[()])
+    traits = {f.trait for _, fs in terms for f in fs}
+    if len(traits) != 1:
+        return None                                           # mixed traits: GenericInput (src/properties.jl:56-62)
+    if not _within_limits(terms)[0]:
+        return None
+    return _composite(terms, traits.pop())
 
 
 def require_device_spec(k):
@@ -765,102 +776,41 @@ def require_device_spec(k):
 # ----------------------------------------------------------------------------------------------
 # gradient kernels of mixed-trait composites (src/gradient_algebra.jl): the composite of covgram_grad_mvm_mixed
 # ----------------------------------------------------------------------------------------------
-class _MixedRefusal(Exception):
-    pass
-
-
-def _mixed_leaf_refusal(k):
-    """Why the leaf `k` has no jet in the mixed gradient kernels, or None."""
-    if isinstance(k, CosineKernel):
-        return f"{type(k).__name__} belongs with the gradient kernels of spectral mixtures"
-    return None
-
-
-def _mixed_expand(k, budget=64):
-    """_expand for the mixed gradient kernels: the same sum-of-products normal form, with NeuralNetwork(σ) as a leaf of its own
-    (family NEURALNETWORK, trait 0, σ in param) and the leaves without a jet refused by name (_MixedRefusal)."""
-    if isinstance(k, Constant):
-        return [(k.c, [])]
+def _mixed_leaf(k):
+    """The leaf hook of the mixed gradient kernels: the compiled profiles, NeuralNetwork(σ) as a leaf of its own (family NEURALNETWORK,
+    trait 0, σ in param), and the leaves without a jet refused by name."""
     if isinstance(k, NeuralNetwork):
         s = _ffi.covgram_kernel()
         s.family, s.trait, s.p, s.power = _ffi.NEURALNETWORK, 0, 0, 1
         s.param, s.lengthscale, s.scale = k.sigma, 1.0, 1.0
-        return [(1.0, [s])]
+        return s
+    if isinstance(k, CosineKernel):
+        raise _Refusal(f"{type(k).__name__} belongs with the gradient kernels of spectral mixtures")
     s = _simple_spec(k)
-    if s is not None:
-        leaf = k
-        while isinstance(leaf, (Product, Power, Lengthscale)):
-            leaf = [a for a in leaf.args if not isinstance(a, Constant)][0] if isinstance(leaf, Product) else leaf.k
-        name = type(leaf).__name__                           # (a half-integer Matern has lowered to MaternP: judged as such)
-        if s.family in (_ffi.EXP, _ffi.GAMMAEXP) or (s.family == _ffi.MATERNP and s.p == 0):
-            raise _MixedRefusal(f"{name}{'(0)' if isinstance(leaf, MaternP) else ''} is singular at zero distance")
-        if s.family == _ffi.MATERN:
-            raise _MixedRefusal(f"{name}(ν = {leaf.nu}) has no closed-form jet here (MaternP does)")
-        c, s.scale = s.scale, 1.0
-        return [(c, [s])]
-    if isinstance(k, Sum):
-        out = []
-        for a in k.args:
-            out += _mixed_expand(a, budget)
-        if len(out) > budget:
-            raise _MixedRefusal(f"the expression multiplies out to more than {budget} terms")
-        return out
-    if isinstance(k, Product) or (isinstance(k, Power) and k.p >= 1):
-        parts = k.args if isinstance(k, Product) else (k.k,) * k.p
-        out = [(1.0, [])]
-        for a in parts:
-            e = _mixed_expand(a, budget)
-            out = [(c1 * c2, f1 + f2) for (c1, f1) in out for (c2, f2) in e]
-            if len(out) > budget:
-                raise _MixedRefusal(f"the expression multiplies out to more than {budget} terms")
-        return out
-    why = _mixed_leaf_refusal(k)
-    raise _MixedRefusal(why if why is not None else f"{type(k).__name__} is not a Sum / Product / Power / Constant / Lengthscale over the supported leaves")
+    if s is None:
+        return None
+    leaf = k
+    while isinstance(leaf, (Product, Power, Lengthscale)):
+        leaf = [a for a in leaf.args if not isinstance(a, Constant)][0] if isinstance(leaf, Product) else leaf.k
+    name = type(leaf).__name__                               # (a half-integer Matern has lowered to MaternP: judged as such)
+    if s.family in (_ffi.EXP, _ffi.GAMMAEXP) or (s.family == _ffi.MATERNP and s.p == 0):
+        raise _Refusal(f"{name}{'(0)' if isinstance(leaf, MaternP) else ''} is singular at zero distance")
+    if s.family == _ffi.MATERN:
+        raise _Refusal(f"{name}(ν = {leaf.nu}) has no closed-form jet here (MaternP does)")
+    return s
 
 
 def _mixed_lower(k):
-    """(composite, None) or (None, reason)."""
-    try:
-        terms = _mixed_expand(k)
-    except _MixedRefusal as e:
-        return None, str(e)
-    key_of = lambda f: (f.family, f.p, f.param, f.lengthscale)
-    merged = {}
-    for c, fs in terms:
-        byleaf = {}
-        for f in fs:                                          # identical leaves of a term multiply into one factor: φ^a φ^b = φ^(a+b)
-            if key_of(f) in byleaf:
-                byleaf[key_of(f)].power += f.power
-            else:
-                g = _ffi.covgram_kernel(); _copy_spec(g, f); byleaf[key_of(f)] = g
-        fs = sorted(byleaf.values(), key=lambda f: key_of(f) + (f.power,))
-        key = tuple(key_of(f) + (f.power,) for f in fs)
-        merged[key] = (merged[key][0] + c if key in merged else c, fs)
-    terms = [(c, fs) for key, (c, fs) in merged.items() if c != 0.0]
-    if not terms:
-        terms = [(0.0, [])]
-    nfac = sum(max(len(fs), 1) for _, fs in terms)
-    if len(terms) > _ffi.COMPOSITE_MAX_TERMS or nfac > _ffi.COMPOSITE_MAX_FACTORS:
-        return None, (f"the normal form has {len(terms)} terms and {nfac} factors; the composite holds {_ffi.COMPOSITE_MAX_TERMS} terms "
-                      f"and {_ffi.COMPOSITE_MAX_FACTORS} factors")
-    comp = _ffi.covgram_kernel_composite()
-    comp.head.family, comp.head.trait, comp.head.p, comp.head.power = _ffi.COMPOSITE, 0, 0, 1
-    comp.head.param, comp.head.lengthscale, comp.head.scale = 0.0, 1.0, 1.0
-    comp.nterms = len(terms)
-    fi = 0
-    for t, (c, fs) in enumerate(terms):
-        if not fs:
-            comp.nfactors[t] = 1
-            comp.factors[fi].family, comp.factors[fi].trait, comp.factors[fi].power = _ffi.CONSTANT, 0, 1
-            comp.factors[fi].lengthscale, comp.factors[fi].scale = 1.0, c
-            fi += 1
-            continue
-        comp.nfactors[t] = len(fs)
-        for q, f in enumerate(fs):
-            _copy_spec(comp.factors[fi], f)
-            comp.factors[fi].scale = c if q == 0 else 1.0     # the term's coefficient rides on its first factor
-            fi += 1
-    return comp, None
+    """The mixed composite of `k`, or _Refusal: the normal form of device_spec with every factor on its own trait (the head's is 0), a
+    term's factors sorted with the power last, the constant term where it first appeared, and an expression that cancels lowered to
+    the one term 0."""
+    merged = _merge_like_terms(_normal_form(k, _mixed_leaf), lambda f: (f.family, f.p, f.param, f.lengthscale, f.power))
+    terms = [term for term in merged.values() if term[0] != 0.0] or [(0.0, [])]
+    ok, nfac = _within_limits(terms)
+    if not ok:
+        raise _Refusal(f"the normal form has {len(terms)} terms and {nfac} factors; the composite holds {_ffi.COMPOSITE_MAX_TERMS} terms "
+                       f"and {_ffi.COMPOSITE_MAX_FACTORS} factors")
+    return _composite(terms, 0)
 
 
 def mixed_gradient_spec(k):
@@ -868,14 +818,19 @@ def mixed_gradient_spec(k):
     Product / Power / Constant / Lengthscale over the leaves with a jet in (x·y, |x|², |y|²) — the isotropic profiles that are smooth
     at zero distance (EQ, RQ, Cauchy, InverseMultiQuadratic, MaternP(p ≥ 1)), Dot, ExponentialDot, AsinDot and NeuralNetwork(σ) — in
     the normal form of device_spec, EVERY FACTOR WITH ITS OWN TRAIT (the head's is 0), within the same limits (8 terms, 8 factors)."""
-    return _mixed_lower(k)[0] if isinstance(k, AbstractKernel) else None
+    try:
+        return require_mixed_gradient_spec(k)
+    except _ffi.UnsupportedKernel:
+        return None
 
 
 def require_mixed_gradient_spec(k):
-    spec, why = _mixed_lower(k) if isinstance(k, AbstractKernel) else (None, f"{type(k).__name__} is not a kernel expression")
-    if spec is None:
-        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"gradient kernel of a mixed-trait composite ({type(k).__name__}): {why}")
-    return spec
+    try:
+        if not isinstance(k, AbstractKernel):
+            raise _Refusal(f"{type(k).__name__} is not a kernel expression")
+        return _mixed_lower(k)
+    except _Refusal as why:
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"gradient kernel of a mixed-trait composite ({type(k).__name__}): {why}") from None
 
 
 # ----------------------------------------------------------------------------------------------

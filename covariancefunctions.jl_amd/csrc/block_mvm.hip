@@ -1,14 +1,13 @@
 // block_mvm.hip — the block MVM drivers of the derivative kernels: covgram_grad_mvm / covgram_valgrad_mvm (grad_mvm.hpp, grad_bcast.hpp,
-// grad_wide.hpp) and covgram_hess_mvm / covgram_valgradhess_mvm (hess_mvm.hpp).
+// grad_wide.hpp; the column split, the panel plan and the reductions: grad_driver.hpp, shared with grad_mixed.hip) and covgram_hess_mvm /
+// covgram_valgradhess_mvm (hess_mvm.hpp).
 #include <math.h>
 
 #include <algorithm>
 
-#include "driver.hpp"
+#include "grad_driver.hpp"
 #include "dense_mvm.hpp"
-#include "grad_mvm.hpp"
 #include "grad_bcast.hpp"
-#include "grad_wide.hpp"
 #include "hess_mvm.hpp"
 
 using namespace covgram;
@@ -60,7 +59,7 @@ static int grad_mvm_device(covgram_ctx* ctx, const covgram_kernel* k, const Host
     // fp32 (round 5): the same form inside GRAD_EXPAND_GATE_F32 — there the absolute error of s is a few fp32 roundings of R^2, what the fp32
     // matrix-core dense kernels carry inside their gate of the same size (dense_mfma.hip), measured at the gate in tests/test_gpu_grad_expand32.py
     const double expand_gate = dtype == COVGRAM_F64 ? GRAD_EXPAND_GATE : GRAD_EXPAND_GATE_F32;
-    const bool expd_ok = !wide && m > 0 && iso && hk.tu_family < COVGRAM_NFAMILY && ctx->grad_keep_r != 1 && !(dtype == COVGRAM_F32 && hk.k.power != 1) &&
+    const bool expd = !wide && m > 0 && iso && hk.tu_family < COVGRAM_NFAMILY && ctx->grad_keep_r != 1 && !(dtype == COVGRAM_F32 && hk.k.power != 1) &&
                           (ctx->grad_expand == 1 ||
                            // measured (tools/c4_expand_ab.py, profiles/r02_c4_expand_ab.txt): pays from d = 8 (C4 0.86x, d = 8 0.95x,
                            // d = 3 +4 %); MaternP(p >= 1) 0.89x since its exp(-r) is the library's own (it was +3 % with the
@@ -77,148 +76,89 @@ static int grad_mvm_device(covgram_ctx* ctx, const covgram_kernel* k, const Host
     // round 4: the expanded form with the column records in VGPRs (grad_bcast.hpp; option "grad_bcast": -1 auto, 0 never, 1 / 4 = with
     // that many waves per workgroup).  One right-hand side per pass: where it applies, matrix right-hand sides run column by column on it
     // (C4 shape: 2 x 1.36 ms against 3.30 ms for the scalar-stream kernel's two-column pass)
-    int bcast_sel = 0;
-    if (expd_ok && dtype == COVGRAM_F64 && hk.k.power == 1 && grad_bcast_ok(D) && hk.tu_family != COVGRAM_MATERN && ctx->grad_bcast != 0)
-        bcast_sel = ctx->grad_bcast == 1 ? 1 : (ctx->grad_bcast == 4 ? 4 : GRAD_BCAST_AUTO(D));
+    int bcast = 0;
+    if (expd && dtype == COVGRAM_F64 && hk.k.power == 1 && grad_bcast_ok(D) && hk.tu_family != COVGRAM_MATERN && ctx->grad_bcast != 0)
+        bcast = ctx->grad_bcast == 1 ? 1 : (ctx->grad_bcast == 4 ? 4 : GRAD_BCAST_AUTO(D));
     for (int c0 = 0; c0 < nrhs;) {
-    const int nr = (two_ok && !bcast_sel && c0 + 1 < nrhs) ? 2 : 1;
-    const void* a_dev = (const char*)a_all + (size_t)c0 * lda_d * ts;
-    void* y_dev = (char*)y_all + (size_t)c0 * ldy_d * ts;
-    const dim3 rgrid((unsigned)((n + 255) / 256), (unsigned)bd, (unsigned)nr);
-
-    if (m == 0) {
-        by_dtype(dtype, [&](auto t) {
-            using T = decltype(t);
-            hipLaunchKernelGGL(grad_reduce_kernel<T>, rgrid, dim3(256), 0, ctx->stream, (const T*)nullptr, npad, D, 0, (T*)y_dev, n, d, (T)0, (T)beta, vg, (T)0);
-        });
-    } else if (wide) {
-        const int PKN = (dtype == COVGRAM_F32) ? 2 : 1;
-        const int64_t BC = (int64_t)GJG * PKN;
-        const int64_t mpad = ((m + BC - 1) / BC) * BC;
-        const int64_t npad64 = ((n + 63) / 64) * 64;
-        int64_t panel = (((int64_t)256 << 20) / (npad64 * 2 * (int64_t)ts)) / BC * BC;   // coefficient slab <= 256 MB
-        panel = std::max<int64_t>(BC, std::min<int64_t>(panel, mpad));
-        grad_wide_launch_fn wlaunch = grad_wide_launcher(hk.tu_family);
-        // (row blocks x dimension chunks) waves may not fill the chip: split each panel's column blocks over z slices that
-        // accumulate raw sums into their own output slabs, reduced in fixed order after the last panel
-        const int64_t waves = (npad64 / 64) * (D / 32);
-        int zs = (int)std::min<int64_t>(16, std::max<int64_t>(1, ((int64_t)ctx->num_cus * 16 + waves - 1) / waves));
-        zs = (int)std::min<int64_t>(zs, std::max<int64_t>(1, panel / BC));
-        void* zslab = nullptr;
-        const int64_t total = n * (int64_t)bd;
-        if (zs > 1) { rc = ws_reserve(ctx, 4, (size_t)zs * total * ts, &zslab); if (rc) return rc; }
-        ctx->last_grad_path |= 4 | (mpad > panel ? 8 : 0) | (zs > 1 ? 16 : 0);
-        for (int64_t col0 = 0; col0 < mpad; col0 += panel) {
-            const int64_t pc = std::min<int64_t>(panel, mpad - col0);
-            void *P, *C;
-            // stream + (value-gradient) the columns' value weights; coefficient slabs C1, C2 + the value row's block partials C0
-            rc = ws_reserve(ctx, 0, (size_t)pc * (D * 2 + vg) * ts, &P); if (rc) return rc;
-            rc = ws_reserve(ctx, 1, ((size_t)pc * 2 + (vg ? (size_t)(pc / BC) : 0)) * npad64 * ts, &C); if (rc) return rc;
-            void* A0P = vg ? (void*)((char*)P + (size_t)pc * D * 2 * ts) : nullptr;
-            void* C0 = vg ? (void*)((char*)C + (size_t)pc * 2 * npad64 * ts) : nullptr;
-            const int64_t pe = pc * (int64_t)D;
-            by_dtype(dtype, [&](auto t) {
-                using T = decltype(t);
-                hipLaunchKernelGGL(grad_wide_pack_kernel<T>, dim3((unsigned)((pe + 255) / 256)), dim3(256), 0, ctx->stream, (const T*)Y->dptr, m, d, D,
-                                   (const T*)a_dev, col0, pc, (T*)P, PKN, (T)hk.kp.gamma, vg, (T*)A0P, (const T*)Cn);
+        const int nr = (two_ok && !bcast && c0 + 1 < nrhs) ? 2 : 1;
+        const void* a_dev = (const char*)a_all + (size_t)c0 * lda_d * ts;
+        void* y_dev = (char*)y_all + (size_t)c0 * ldy_d * ts;
+        if (m == 0) {                                           // no columns: y <- beta y
+            grad_reduce(ctx, dtype, nullptr, npad, D, 0, y_dev, n, d, vg, nr, 0, 0.0, 0.0, beta);
+        } else if (wide) {
+            GradPanelPlan pp;
+            rc = grad_panel_plan(ctx, dtype, n, m, D, bd, 0, &pp); if (rc) return rc;
+            grad_wide_launch_fn wlaunch = grad_wide_launcher(hk.tu_family);
+            ctx->last_grad_path |= 4 | (pp.several() ? 8 : 0) | (pp.zs > 1 ? 16 : 0);
+            rc = grad_panel_route(ctx, pp, dtype, n, bd, vg, y_dev, alpha_eff, alpha0, beta, [&](int64_t col0, int64_t pc, int accumulate) -> int {
+                const int64_t npad64 = pp.npad64;
+                void *P, *C;
+                // stream + (value-gradient) the columns' value weights; coefficient slabs C1, C2 + the value row's block partials C0
+                int prc = ws_reserve(ctx, 0, (size_t)pc * (D * 2 + vg) * ts, &P); if (prc) return prc;
+                prc = ws_reserve(ctx, 1, ((size_t)pc * 2 + (vg ? (size_t)(pc / pp.BC) : 0)) * npad64 * ts, &C); if (prc) return prc;
+                void* A0P = vg ? (void*)((char*)P + (size_t)pc * D * 2 * ts) : nullptr;
+                void* C0 = vg ? (void*)((char*)C + (size_t)pc * 2 * npad64 * ts) : nullptr;
+                const int64_t pe = pc * (int64_t)D;
+                by_dtype(dtype, [&](auto t) {
+                    using T = decltype(t);
+                    hipLaunchKernelGGL(grad_wide_pack_kernel<T>, dim3((unsigned)((pe + 255) / 256)), dim3(256), 0, ctx->stream, (const T*)Y->dptr, m, d, D,
+                                       (const T*)a_dev, col0, pc, (T*)P, pp.PKN, (T)hk.kp.gamma, vg, (T*)A0P, (const T*)Cn);
+                });
+                GradWideArgs wa;
+                wa.Cn = Cn;
+                wa.vg = vg; wa.A0P = A0P; wa.C0 = C0; wa.alpha0 = pp.zs > 1 ? 1.0 : alpha0;
+                wa.vg_c = (iso ? -1.0 : 1.0) / hk.kp.gamma; wa.vg_b = iso ? -2.0 * hk.kp.gamma : hk.kp.gamma;
+                wa.X = X->dptr; wa.n = n; wa.d = d; wa.dpad = D; wa.P = P; wa.C1 = C; wa.C2 = (char*)C + (size_t)pc * npad64 * ts;
+                wa.npad = npad64; wa.nblocks = pc / pp.BC; wa.y = y_dev; wa.alpha = alpha_eff; wa.beta = beta; wa.accumulate = accumulate;
+                if (pp.zs > 1) { wa.zs = pp.zs; wa.zstride = pp.total; wa.y = pp.zslab; wa.alpha = 1.0; wa.beta = 0.0; }
+                wa.hk = &hk; wa.stream = ctx->stream;
+                TimerScope tm(ctx);
+                return wlaunch(wa, dtype);
             });
-            GradWideArgs wa;
-            wa.Cn = Cn;
-            wa.vg = vg; wa.A0P = A0P; wa.C0 = C0; wa.alpha0 = zs > 1 ? 1.0 : alpha0;
-            wa.vg_c = (iso ? -1.0 : 1.0) / hk.kp.gamma; wa.vg_b = iso ? -2.0 * hk.kp.gamma : hk.kp.gamma;
-            wa.X = X->dptr; wa.n = n; wa.d = d; wa.dpad = D; wa.P = P; wa.C1 = C; wa.C2 = (char*)C + (size_t)pc * npad64 * ts;
-            wa.npad = npad64; wa.nblocks = pc / BC; wa.y = y_dev; wa.alpha = alpha_eff; wa.beta = beta; wa.accumulate = col0 > 0 ? 1 : 0;
-            if (zs > 1) { wa.zs = zs; wa.zstride = total; wa.y = zslab; wa.alpha = 1.0; wa.beta = 0.0; }
-            wa.hk = &hk; wa.stream = ctx->stream;
-            { TimerScope tm(ctx); rc = wlaunch(wa, dtype); }
             if (rc) return rc;
-        }
-        if (zs > 1) {
-            const dim3 zg((unsigned)((n + 255) / 256), (unsigned)bd);
+        } else {
+            void* P;
+            // + 1 prefetch-only record; the value weights A0[0..m] of the value-gradient variant follow the stream
+            rc = ws_reserve(ctx, 0, (size_t)(m + 1) * ((1 + nr) * D + nr * vg + (expd ? 1 + nr : 0)) * ts, &P); if (rc) return rc;
+            void* A0 = vg ? (void*)((char*)P + (size_t)(m + 1) * (1 + nr) * D * ts) : nullptr;
+            void* Ex = expd ? (void*)((char*)P + (size_t)(m + 1) * ((1 + nr) * D + nr * vg) * ts) : nullptr;
+            const int64_t pe = (m + 1) * (int64_t)D;
             by_dtype(dtype, [&](auto t) {
                 using T = decltype(t);
-                hipLaunchKernelGGL(grad_wide_reduce_kernel<T>, zg, dim3(256), 0, ctx->stream, (const T*)zslab, zs, total, n, (T*)y_dev, (T)alpha_eff, (T)beta,
-                                   vg, bd, (T)alpha0);
-            });
-        }
-    } else {
-        void* P;
-        // + 1 prefetch-only record; the value weights A0[0..m] of the value-gradient variant follow the stream
-        // expanded form (grad_mvm.hpp): fp64 isotropic simple profiles whose pre-scaled clouds lie within the radius gate
-        const bool expd = expd_ok;
-        rc = ws_reserve(ctx, 0, (size_t)(m + 1) * ((1 + nr) * D + nr * vg + (expd ? 1 + nr : 0)) * ts, &P); if (rc) return rc;
-        void* A0 = vg ? (void*)((char*)P + (size_t)(m + 1) * (1 + nr) * D * ts) : nullptr;
-        void* Ex = expd ? (void*)((char*)P + (size_t)(m + 1) * ((1 + nr) * D + nr * vg) * ts) : nullptr;
-        const int64_t pe = (m + 1) * (int64_t)D;
-        by_dtype(dtype, [&](auto t) {
-            using T = decltype(t);
-            hipLaunchKernelGGL(grad_pack_kernel<T>, dim3((unsigned)((pe + 255) / 256)), dim3(256), 0, ctx->stream, (const T*)Y->dptr, m, d, (const T*)a_dev, (T*)P,
-                               D, (T)hk.kp.gamma, vg, (T*)A0, (const T*)Cn, nr, lda_d);
-            if (!expd) return;
+                hipLaunchKernelGGL(grad_pack_kernel<T>, dim3((unsigned)((pe + 255) / 256)), dim3(256), 0, ctx->stream, (const T*)Y->dptr, m, d, (const T*)a_dev, (T*)P,
+                                   D, (T)hk.kp.gamma, vg, (T*)A0, (const T*)Cn, nr, lda_d);
+                if (!expd) return;
 #define CG_PEL(DLV) hipLaunchKernelGGL((grad_pack_extra_lanes_kernel<T, DLV>), dim3((unsigned)(((m + 1) * DLV + 255) / 256)), dim3(256), 0, ctx->stream, (const T*)Y->dptr, m, \
                                        (const T*)a_dev, (T)hk.kp.gamma, vg, (const T*)Cn, (T*)Ex, nr, lda_d)
-            if (d == 8) CG_PEL(8); else if (d == 16) CG_PEL(16); else if (d == 32) CG_PEL(32); else if (d == 64) CG_PEL(64);
-            else hipLaunchKernelGGL(grad_pack_extra_kernel<T>, dim3((unsigned)((m + 256) / 256)), dim3(256), 0, ctx->stream, (const T*)Y->dptr, m, d,
-                                    (const T*)a_dev, (T)hk.kp.gamma, vg, (const T*)Cn, (T*)Ex, nr, lda_d);
+                if (d == 8) CG_PEL(8); else if (d == 16) CG_PEL(16); else if (d == 32) CG_PEL(32); else if (d == 64) CG_PEL(64);
+                else hipLaunchKernelGGL(grad_pack_extra_kernel<T>, dim3((unsigned)((m + 256) / 256)), dim3(256), 0, ctx->stream, (const T*)Y->dptr, m, d,
+                                        (const T*)a_dev, (T)hk.kp.gamma, vg, (const T*)Cn, (T*)Ex, nr, lda_d);
 #undef CG_PEL
-        });
-        int64_t jchunk; int jsplit;
-        // partial slabs cost jsplit * n * d * sizeof(T) bytes, but several rounds of workgroups balance the tail
-        // (C4: 2.47 ms at CUs*8, 2.08 at CUs*32, 2.01 at CUs*64, 2.05 at CUs*96, 2.15 at CUs*128 — interleaved A/B, tools/c4_ab.py)
-        // round 4: the expanded form with the column records in VGPRs (grad_bcast.hpp; option "grad_bcast": -1 auto, 0 never, 1 / 4 = with
-        // that many waves per workgroup)
-        const int bcast = bcast_sel;
-        ctx->last_grad_bcast = bcast;
-        const int bwaves = std::max(1, std::min(4, 512 / (4 * D + 4 * ((2 * D + 15) / 16) + 44)));   // grad_bcast_waves<D>()
-        const int gthreads = bcast ? 64 * bcast : grad_block_threads((int)ts, D, hk.tu_family);          // 64 or 256 threads per workgroup (grad_mvm.hpp)
-        // Column split: about 64 waves per CU over the launch (round 1's sweep), then (round 2, tools/c4_jsplit_sweep.py)
-        //  * capped so that the partial slabs (split x n x d results, written here and read back by the reduction) stay inside the
-        //    256 MB Infinity Cache — C4 at 64 splits writes 268 MB, d = 48 403 MB: 3.86 ms against 3.61 at 48 splits —
-        //  * and, when that cap binds, snapped DOWN to a whole number of rounds of resident workgroups if one lies within reach (the
-        //    waves of the EQ kernel all take the same time, so a ragged last round idles most of the chip: C4 at 64 row workgroups x
-        //    {36, 42, 48, 54, 60} splits = {3.0, 3.5, 4.0, 4.5, 5.0} rounds: 1.744, 1.853, 1.748, 1.809, 1.770 ms).
-        //  Old and new library alternating on one box: C4 1.79 -> 1.77 ms, value-gradient -2 %, d = 48 3.85 -> 3.65; the heavier
-        //  profiles at the C4 shape lose 1.5 % (MaternP(2) 2.33 -> 2.37, RQ 3.60 -> 3.66): their slab is the same 268 MB but a
-        //  smaller share of a longer kernel.
-        const int64_t growwgs = (n + gthreads - 1) / gthreads;
-        const int64_t gslots = (int64_t)ctx->num_cus * 4 * (bcast ? bwaves : grad_waves_per_simd((int)ts, D, hk.tu_family)) / (gthreads / 64);
-        int64_t gsplit = std::max<int64_t>(1, ((int64_t)ctx->num_cus * 64 * 64 / gthreads + growwgs - 1) / growwgs);
-        gsplit = std::min(gsplit, std::max<int64_t>(1, m / 64));   // >= 64 columns per workgroup: below that its prologue and slab rows dominate
-                                                                    // (tools/c4_jsplit_sweep.py small: n = 4096, d = 8: 16-column chunks 0.109 ms, 64-column 0.059)
-        const int64_t gcap = std::max<int64_t>(1, (int64_t)(256.0e6 / ((double)npad * (D + vg) * nr * ts)));
-        if (ctx->jsplit <= 0 && ctx->target_wgs <= 0 && gsplit > gcap) {
-            gsplit = gcap;
-            for (int64_t js = gsplit; js >= std::max<int64_t>(1, gsplit / 2); --js) {
-                const double rounds = (double)(js * growwgs) / (double)gslots;
-                const double ragged = std::ceil(rounds) - rounds;
-                if (rounds >= 1.0 && ragged <= 0.04) { gsplit = js; break; }
-            }
-        }
-        choose_split(ctx, growwgs, m, 8, &jchunk, &jsplit, gsplit * growwgs);
-        GradArgs ga;
-        ga.C = Cn;
-        ga.X = X->dptr; ga.n = n; ga.d = d; ga.P = P; ga.m = m; ga.npad = npad; ga.Dpad = D; ga.jchunk = jchunk; ga.jsplit = jsplit; ga.keep_r = (int)ctx->grad_keep_r;
-        ga.alpha = alpha_eff; ga.beta = beta; ga.hk = &hk; ga.stream = ctx->stream;
-        ga.vg = vg; ga.A0 = A0; ga.alpha0 = alpha0;
-        ga.expd = expd ? 1 : 0; ga.Ex = Ex; ga.bcast = bcast;
-        ga.nr = nr; ga.ldy = ldy_d;
-        ctx->last_grad_expand = ga.expd;
-        ctx->last_grad_jsplit = jsplit;
-        ctx->last_grad_path |= 1 | (nr == 2 ? 2 : 0) | (jsplit > 1 ? 32 : 0);
-        ga.vg_c = (iso ? -1.0 : 1.0) / hk.kp.gamma;
-        ga.vg_b = iso ? -2.0 * hk.kp.gamma : hk.kp.gamma;
-        if (jsplit == 1) ga.out = y_dev;
-        else { rc = ws_reserve(ctx, 1, (size_t)jsplit * nr * (D + vg) * npad * ts, &ga.out); if (rc) return rc; }
-        { TimerScope tm(ctx); rc = launch(ga, dtype); }
-        if (rc) return rc;
-        if (jsplit > 1)
-            by_dtype(dtype, [&](auto t) {
-                using T = decltype(t);
-                hipLaunchKernelGGL(grad_reduce_kernel<T>, rgrid, dim3(256), 0, ctx->stream, (const T*)ga.out, npad, D, jsplit, (T*)y_dev, n, d, (T)alpha_eff,
-                                   (T)beta, vg, (T)alpha0, ldy_d);
             });
-    }
-    c0 += nr;
+            ctx->last_grad_bcast = bcast;
+            const int bwaves = std::max(1, std::min(4, 512 / (4 * D + 4 * ((2 * D + 15) / 16) + 44)));   // grad_bcast_waves<D>()
+            const int gthreads = bcast ? 64 * bcast : grad_block_threads((int)ts, D, hk.tu_family);          // 64 or 256 threads per workgroup (grad_mvm.hpp)
+            // the workgroups resident at once: where the slab cap binds, the column split snaps to whole rounds of them (grad_driver.hpp)
+            const int64_t gslots = (int64_t)ctx->num_cus * 4 * (bcast ? bwaves : grad_waves_per_simd((int)ts, D, hk.tu_family)) / (gthreads / 64);
+            rc = grad_lane_route(ctx, dtype, n, m, d, D, vg, nr, gthreads, gslots, npad, y_dev, ldy_d, alpha_eff, alpha0, beta, [&](int64_t jchunk, int jsplit, void* out) -> int {
+                GradArgs ga;
+                ga.C = Cn;
+                ga.X = X->dptr; ga.n = n; ga.d = d; ga.P = P; ga.m = m; ga.npad = npad; ga.Dpad = D; ga.jchunk = jchunk; ga.jsplit = jsplit; ga.keep_r = (int)ctx->grad_keep_r;
+                ga.alpha = alpha_eff; ga.beta = beta; ga.hk = &hk; ga.stream = ctx->stream; ga.out = out;
+                ga.vg = vg; ga.A0 = A0; ga.alpha0 = alpha0;
+                ga.expd = expd ? 1 : 0; ga.Ex = Ex; ga.bcast = bcast;
+                ga.nr = nr; ga.ldy = ldy_d;
+                ctx->last_grad_expand = ga.expd;
+                ctx->last_grad_jsplit = jsplit;
+                ctx->last_grad_path |= 1 | (nr == 2 ? 2 : 0) | (jsplit > 1 ? 32 : 0);
+                ga.vg_c = (iso ? -1.0 : 1.0) / hk.kp.gamma;
+                ga.vg_b = iso ? -2.0 * hk.kp.gamma : hk.kp.gamma;
+                TimerScope tm(ctx);
+                return launch(ga, dtype);
+            });
+            if (rc) return rc;
+        }
+        c0 += nr;
     }   // right-hand sides
     return COVGRAM_OK;
 }
@@ -228,39 +168,32 @@ static int grad_mvm_device(covgram_ctx* ctx, const covgram_kernel* k, const Host
 // vectors OF MATRICES too, and the block mul! of src/gradient.jl:86-92 broadcasts over their columns)
 static int grad_mvm_impl(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, const void* a, int64_t lda,
                          void* y, int64_t ldy, int32_t nrhs, double alpha, double beta, int32_t loc, int vg) {
-    int rc = check_pair(ctx, X, Y);
-    if (rc) return rc;
-    CG_REQUIRE(nrhs >= 1, COVGRAM_EINVAL, "nrhs must be >= 1");
-    const int64_t ma = Y->n * (int64_t)(Y->d + vg), ny = X->n * (int64_t)(X->d + vg);
-    CG_REQUIRE(lda >= ma && ldy >= ny, COVGRAM_EINVAL, "lda / ldy smaller than the block vectors (%lld, %lld)", (long long)ma, (long long)ny);
-    CG_REQUIRE((a != nullptr || ma == 0) && (y != nullptr || ny == 0), COVGRAM_EINVAL, "a or y is NULL");
     // derivatives are linear in the kernel: a Sum runs term by term as well
     // (always split: the one-pass Sum kernels of covgram_mvm (dense_mfma.hip: sum_fused_applies) are value kernels only — there is no
     //  one-pass gradient form, and the unsplit Sum would run the composite interpreter instead of each term's own kernel)
     SumSplit split;
-    const bool sum = composite_sum_terms(ctx, k, loc, &split);
+    bool sum = false;
     HostKernel hk;
-    rc = make_host_kernel(k, X->dtype, true, &hk);     // (a split Sum: the composite's own validation still applies)
-    if (rc) return rc;
-    CG_DEVICE(ctx);
-    Staged st;
-    rc = st.begin(ctx, loc, dtype_size(X->dtype), a, lda, ma, y, ldy, ny, nrhs, beta);
-    if (rc) return rc;
-    if (!sum) rc = grad_mvm_device(ctx, k, hk, X, Y, st.a, st.lda, st.y, st.ldy, nrhs, alpha, beta, vg);
-    else
-        rc = sum_split_run(
-            split, beta,
-            [&](const covgram_kernel* tk, double tbeta) {
-                HostKernel thk;
-                const int trc = make_host_kernel(tk, X->dtype, true, &thk);
-                return trc ? trc : grad_mvm_device(ctx, tk, thk, X, Y, st.a, st.lda, st.y, st.ldy, nrhs, alpha, tbeta, vg);
-            },
-            [&] {   // a constant has zero derivatives: only the value-value entry of the value-gradient blocks sees it
-                return vg ? constant_term_mvm(ctx, X->dtype, st.a, Y->n, st.lda, X->d + 1, st.y, X->n, st.ldy, X->d + 1, nrhs, alpha * split.constant) : COVGRAM_OK;
-            });
-    if (rc) return rc;
-    CG_CHECK_HIP(hipGetLastError());
-    return st.finish();
+    return block_mvm_entry(
+        ctx, X, Y, a, lda, y, ldy, nrhs, beta, loc, true,
+        [&](int d, int64_t* B) -> int { *B = d + vg; return COVGRAM_OK; },
+        [&]() -> int {
+            sum = composite_sum_terms(ctx, k, loc, &split);
+            return make_host_kernel(k, X->dtype, true, &hk);     // (a split Sum: the composite's own validation still applies)
+        },
+        [&](const Staged& st) -> int {
+            if (!sum) return grad_mvm_device(ctx, k, hk, X, Y, st.a, st.lda, st.y, st.ldy, nrhs, alpha, beta, vg);
+            return sum_split_run(
+                split, beta,
+                [&](const covgram_kernel* tk, double tbeta) {
+                    HostKernel thk;
+                    const int trc = make_host_kernel(tk, X->dtype, true, &thk);
+                    return trc ? trc : grad_mvm_device(ctx, tk, thk, X, Y, st.a, st.lda, st.y, st.ldy, nrhs, alpha, tbeta, vg);
+                },
+                [&] {   // a constant has zero derivatives: only the value-value entry of the value-gradient blocks sees it
+                    return vg ? constant_term_mvm(ctx, X->dtype, st.a, Y->n, st.lda, X->d + 1, st.y, X->n, st.ldy, X->d + 1, nrhs, alpha * split.constant) : COVGRAM_OK;
+                });
+        });
 }
 
 int covgram_grad_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, const void* a, int64_t lda,

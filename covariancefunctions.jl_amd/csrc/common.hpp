@@ -149,6 +149,9 @@ struct HostKernel {
 
 // Validates `k` and fills the parameter block.  `for_gradient` keeps gamma = 1/l (no log2e fold).
 int make_host_kernel(const covgram_kernel* k, int dtype, bool for_gradient, HostKernel* out);
+// The composite behind make_host_kernel (mixed = false: one trait over the head and every factor), or the mixed-trait composite of
+// covgram_grad_mvm_mixed (mixed = true: every factor on its own trait, NeuralNetwork factors, tu_family = FAM_EXPR_DOT).
+int make_composite_kernel(const covgram_kernel_composite* c, int dtype, bool mixed, HostKernel* out);
 
 template <typename T>
 inline KParams<T> cast_params(const KParams<double>& s) {

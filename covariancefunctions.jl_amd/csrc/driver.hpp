@@ -1,5 +1,6 @@
-// driver.hpp — what the C-ABI drivers share: staging of host pointers, dtype dispatch, the timer bracket, the Sum split.  Served units: the
-// point-pair entries (api.hip, matrix.hip, block_mvm.hip, sm.hip, sparse.hip, bilin_grad.hip, input_grad.hip, dense_mfma.hip, pivchol.hip) and the
+// driver.hpp — what the C-ABI drivers share: staging of host pointers, dtype dispatch, the timer bracket, the bracket of a block MVM entry, the
+// Sum split.  Served units: the point-pair entries (api.hip, matrix.hip, block_mvm.hip, grad_mixed.hip — these two through grad_driver.hpp —,
+// sm.hip, sparse.hip, bilin_grad.hip, input_grad.hip, dense_mfma.hip, pivchol.hip), kernel_params.hip (the family names of its refusals) and the
 // structured operators (toeplitz.hip, toeplitz_direct.hip, kron.hip, lowrank.hip, barneshut.hip).  Host code only; the per-family kernel units
 // include common.hpp, not this.
 #pragma once
@@ -73,6 +74,36 @@ inline int stage_operand(covgram_ctx* ctx, int loc, size_t ts, char*& cur, const
 }
 
 int check_pair(const covgram_ctx* ctx, const covgram_points* X, const covgram_points* Y);
+
+// The bracket of a block MVM entry, y <- alpha G a + beta y on block vectors with B entries per point (a: m B x nrhs, y: n B x nrhs,
+// column-major): the argument checks, the ctx's device, the staging of a and y around run(st), which enqueues the product on st.a / st.y.
+//   block(d, &B): the entry's own checks that come first, and its block size;
+//   lower():      the kernel's validation, host work only — nothing has touched the device before it returns COVGRAM_OK;
+//   stage_empty:  whether a product without rows (n = 0) is still staged and run, or returns at once.
+template <typename Block, typename Lower, typename Run>
+inline int block_mvm_entry(covgram_ctx* ctx, const covgram_points* X, const covgram_points* Y, const void* a, int64_t lda, void* y, int64_t ldy, int32_t nrhs,
+                           double beta, int32_t loc, bool stage_empty, Block block, Lower lower, Run run) {
+    int rc = check_pair(ctx, X, Y);
+    if (rc) return rc;
+    int64_t B = 0;
+    rc = block(X->d, &B);
+    if (rc) return rc;
+    CG_REQUIRE(nrhs >= 1, COVGRAM_EINVAL, "nrhs must be >= 1");
+    const int64_t ma = Y->n * B, ny = X->n * B;
+    CG_REQUIRE(lda >= ma && ldy >= ny, COVGRAM_EINVAL, "lda / ldy smaller than the block vectors (%lld, %lld)", (long long)ma, (long long)ny);
+    CG_REQUIRE((a != nullptr || ma == 0) && (y != nullptr || ny == 0), COVGRAM_EINVAL, "a or y is NULL");
+    rc = lower();
+    if (rc) return rc;
+    CG_DEVICE(ctx);
+    if (X->n == 0 && !stage_empty) return COVGRAM_OK;
+    Staged st;
+    rc = st.begin(ctx, loc, dtype_size(X->dtype), a, lda, ma, y, ldy, ny, nrhs, beta);
+    if (rc) return rc;
+    rc = run(st);
+    if (rc) return rc;
+    CG_CHECK_HIP(hipGetLastError());
+    return st.finish();
+}
 
 // choose the J split: enough workgroups to fill the chip, chunks aligned to the inner accumulation block
 void choose_split(const covgram_ctx* ctx, int64_t rowblocks, int64_t m, int64_t align, int64_t* jchunk, int* jsplit, int64_t default_target = 0);

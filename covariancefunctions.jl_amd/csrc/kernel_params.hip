@@ -2,7 +2,7 @@
 // master copy of the parameter block every device kernel receives.
 #include <algorithm>
 
-#include "common.hpp"
+#include "driver.hpp"
 
 namespace covgram {
 
@@ -43,16 +43,19 @@ static void maternp_derivs0(int p, long double* d /* d[1..p] */) {
 static int make_simple_kernel(const covgram_kernel* k, int dtype, bool for_gradient, HostKernel* out);
 
 // Composite: every factor keeps its own parameter block with gamma = 1/l (unfolded EQ); rows and columns stay unscaled.
-static int make_composite_kernel(const covgram_kernel_composite* c, int dtype, HostKernel* out) {
+// mixed (the composite of covgram_grad_mvm_mixed, grad_mixed.hpp): the head's trait binds nobody, every factor is validated on its OWN
+// trait, a NeuralNetwork factor keeps sigma in fkp.param, and the leaves without a jet in (x.y, |x|^2, |y|^2) are refused.
+int make_composite_kernel(const covgram_kernel_composite* c, int dtype, bool mixed, HostKernel* out) {
     const covgram_kernel& h = c->head;
-    CG_REQUIRE(h.trait == COVGRAM_ISOTROPIC || h.trait == COVGRAM_DOTPRODUCT, COVGRAM_EINVAL, "composite: bad trait %d", h.trait);
+    if (mixed) CG_REQUIRE(h.family == COVGRAM_COMPOSITE, COVGRAM_EINVAL, "covgram_grad_mvm_mixed takes a covgram_kernel_composite (head.family = %d)", h.family);
+    else CG_REQUIRE(h.trait == COVGRAM_ISOTROPIC || h.trait == COVGRAM_DOTPRODUCT, COVGRAM_EINVAL, "composite: bad trait %d", h.trait);
     CG_REQUIRE(h.power == 1 && h.lengthscale == 1.0, COVGRAM_EINVAL, "composite head must have power == 1 and lengthscale == 1");
     CG_REQUIRE(c->nterms >= 1 && c->nterms <= EXPR_MAXT, COVGRAM_EUNSUPPORTED, "composite: %d terms (1..%d supported)", c->nterms, EXPR_MAXT);
     memset(out, 0, sizeof(*out));
     out->k = h;
     out->kp.gamma = 1.0; out->kp.gamma2 = 1.0; out->kp.scale = h.scale; out->kp.power = 1;
     out->eq_folded = false;
-    out->tu_family = (h.trait == COVGRAM_ISOTROPIC) ? FAM_EXPR_ISO : FAM_EXPR_DOT;
+    out->tu_family = (!mixed && h.trait == COVGRAM_ISOTROPIC) ? FAM_EXPR_ISO : FAM_EXPR_DOT;
     out->nterms = c->nterms;
     int nin = 0, nf = 0;   // factors consumed from the descriptor / profile factors kept for the device
     for (int t = 0; t < c->nterms; ++t) {
@@ -66,16 +69,32 @@ static int make_composite_kernel(const covgram_kernel_composite* c, int dtype, H
                 out->coef[t] *= fk.scale;
                 continue;
             }
-            CG_REQUIRE(fk.trait == h.trait, COVGRAM_EINVAL, "composite: factor %d has trait %d, head has %d (GenericInput is not a device path)",
-                       nin, fk.trait, h.trait);
-            HostKernel one;
-            int rc = make_simple_kernel(&fk, dtype, true, &one);
-            if (rc) return rc;
-            double sc = fk.scale;                  // (scale * phi)^1 only: a factor's scale multiplies the term once
-            out->coef[t] *= sc;
+            KParams<double>& kp = out->fkp[nf];
+            if (mixed && fk.family == COVGRAM_NEURALNETWORK) {
+                CG_REQUIRE(fk.param >= 0, COVGRAM_EINVAL, "DomainError: NeuralNetwork sigma = %g is negative", fk.param);
+                CG_REQUIRE(fk.power >= 1, COVGRAM_EINVAL, "Power exponent must be >= 1 (got %d)", fk.power);
+                CG_REQUIRE(fk.lengthscale == 1.0, COVGRAM_EINVAL, "Lengthscale applies to isotropic kernels only");
+                kp.gamma = 1.0; kp.gamma2 = 1.0; kp.param = fk.param; kp.power = fk.power;
+            } else {
+                if (mixed) {
+                    CG_REQUIRE(fk.family >= 0 && fk.family < COVGRAM_NFAMILY, COVGRAM_EUNSUPPORTED, "unknown kernel family %d", fk.family);
+                    const char* name = kFamilyNames[fk.family];
+                    CG_REQUIRE(fk.family != COVGRAM_EXP && fk.family != COVGRAM_GAMMAEXP && !(fk.family == COVGRAM_MATERNP && fk.p == 0), COVGRAM_EUNSUPPORTED,
+                               "mixed gradient kernel: the leaf %s%s is singular at zero distance and has no device path here", name,
+                               fk.family == COVGRAM_MATERNP ? "(0)" : "");
+                    CG_REQUIRE(fk.family != COVGRAM_MATERN, COVGRAM_EUNSUPPORTED, "mixed gradient kernel: the leaf %s(nu) has no device path here (MaternP does)", name);
+                } else {
+                    CG_REQUIRE(fk.trait == h.trait, COVGRAM_EINVAL, "composite: factor %d has trait %d, head has %d (GenericInput is not a device path)",
+                               nin, fk.trait, h.trait);
+                }
+                HostKernel one;
+                int rc = make_simple_kernel(&fk, dtype, true, &one);   // the factor's own trait against its family, its parameters
+                if (rc) return rc;
+                kp = one.kp;
+            }
+            kp.scale = 1.0;
+            out->coef[t] *= fk.scale;              // (scale * phi)^1 only: a factor's scale multiplies the term once
             out->ffam[nf] = fk.family;
-            out->fkp[nf] = one.kp;
-            out->fkp[nf].scale = 1.0;
             ++out->nfac[t]; ++nf;
         }
     }
@@ -84,7 +103,7 @@ static int make_composite_kernel(const covgram_kernel_composite* c, int dtype, H
 
 int make_host_kernel(const covgram_kernel* k, int dtype, bool for_gradient, HostKernel* out) {
     CG_REQUIRE(k != nullptr, COVGRAM_EINVAL, "kernel is NULL");
-    if (k->family == COVGRAM_COMPOSITE) return make_composite_kernel((const covgram_kernel_composite*)k, dtype, out);
+    if (k->family == COVGRAM_COMPOSITE) return make_composite_kernel((const covgram_kernel_composite*)k, dtype, false, out);
     return make_simple_kernel(k, dtype, for_gradient, out);
 }
 

@@ -134,6 +134,38 @@ def test_lowering_constants_and_power_folding(cg):
     assert [(q.family, q.power) for q in term] == [(f.DOT, 2)]
 
 
+def test_the_two_normal_forms_differ_where_the_device_reads_them(cg):
+    """device_spec and mixed_gradient_spec share one walker and one composite writer; the order of terms and factors decides the order of
+    the floating-point products on the device, so what differs between the two forms is pinned with literal orders."""
+    f = cg._ffi
+    shape = lambda c: [[(q.family, q.param, q.power) for q in t] for t in _factors(c)]
+    # a constant in the middle of a Sum: last in the common-trait form, where it stood in the mixed form
+    k = cg.EQ() + 2.0 + cg.RQ(2.0)
+    c = cg.device_spec(k)
+    assert c.head.trait == f.ISOTROPIC and shape(c) == [[(f.EQ, 0.0, 1)], [(f.RQ, 2.0, 1)], [(f.CONSTANT, 0.0, 1)]]
+    assert [t[0].scale for t in _factors(c)] == [1.0, 1.0, 2.0] and _factors(c)[2][0].trait == f.ISOTROPIC
+    c = cg.mixed_gradient_spec(k)
+    assert c.head.trait == 0 and shape(c) == [[(f.EQ, 0.0, 1)], [(f.CONSTANT, 0.0, 1)], [(f.RQ, 2.0, 1)]]
+    assert [t[0].scale for t in _factors(c)] == [1.0, 2.0, 1.0] and _factors(c)[1][0].trait == 0
+    c = cg.mixed_gradient_spec(cg.EQ() + 2.0 + cg.Dot())
+    assert shape(c) == [[(f.EQ, 0.0, 1)], [(f.CONSTANT, 0.0, 1)], [(f.DOT, 0.0, 1)]]
+    # a term's factors: (family, p, power, param, lengthscale) against (family, p, param, lengthscale, power)
+    k = cg.RQ(2.0) ** 3 * cg.RQ(3.0) ** 2
+    assert shape(cg.device_spec(k)) == [[(f.RQ, 3.0, 2), (f.RQ, 2.0, 3)]]
+    assert shape(cg.mixed_gradient_spec(k)) == [[(f.RQ, 2.0, 3), (f.RQ, 3.0, 2)]]
+    # like terms meet whatever order their factors were written in, coefficient on the first factor
+    c = cg.mixed_gradient_spec(2.0 * k + cg.RQ(3.0) ** 2 * cg.RQ(2.0) ** 3)
+    assert shape(c) == [[(f.RQ, 2.0, 3), (f.RQ, 3.0, 2)]] and [q.scale for q in _factors(c)[0]] == [3.0, 1.0]
+    # an expression that cancels: nothing left in one form, the single term 0 in the other
+    k = cg.EQ() + cg.Constant(-1.0, False) * cg.EQ()
+    assert cg.device_spec(k) is None
+    c = cg.mixed_gradient_spec(k)
+    assert shape(c) == [[(f.CONSTANT, 0.0, 1)]] and _factors(c)[0][0].scale == 0.0
+    # a single profile stays a plain covgram_kernel in one form and becomes a one-term composite in the other
+    assert type(cg.device_spec(cg.EQ())) is f.covgram_kernel
+    assert type(cg.mixed_gradient_spec(cg.EQ())) is f.covgram_kernel_composite
+
+
 def test_lowering_limits_and_refusals_by_name(cg):
     f = cg._ffi
     many = cg.EQ()
