@@ -714,7 +714,7 @@ static const CtxField kInfo[] = {
     CG_FIELD(last_dense_bcast), CG_FIELD(last_mfma_f16), CG_FIELD(last_inkernel_reduce), CG_FIELD(last_grad_expand), CG_FIELD(last_grad_bcast),
     CG_FIELD(last_grad_path), CG_FIELD(last_grad_jsplit), CG_FIELD(last_hess_path), CG_FIELD(last_vgh_path), CG_FIELD(last_matrix_path),
     CG_FIELD(last_block_matrix_path), CG_FIELD(last_sum_fused), CG_FIELD(last_mfma_instance), CG_FIELD(last_mfma_graded), CG_FIELD(last_mfma_sym_rt), CG_FIELD(last_grad_mixed_path),
-    CG_FIELD(last_grad_mixed_jsplit), CG_FIELD(num_cus)};
+    CG_FIELD(last_grad_mixed_jsplit), CG_FIELD(last_kron_arms), CG_FIELD(num_cus)};
 #undef CG_FIELD
 
 int covgram_ctx_set_option(covgram_ctx* ctx, const char* key, int64_t value) {

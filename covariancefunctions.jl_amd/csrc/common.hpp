@@ -300,6 +300,7 @@ struct covgram_ctx {
     int live_handles = 0;
     int64_t last_dense_path = 0; // 1 lane-per-row, 2 matrix cores, 3 wide rows, 4 factored dot product X (Y' a)
     int64_t last_kron_path = 0;  // kernels of the last Kronecker MVM, bits: 1 fused last-two-modes pass, 2 single-mode kernel, 4 last-mode kernel, 8 rocBLAS GEMM, 16 two small trailing factors multiplied out
+    int64_t last_kron_arms = 0;  // template arms its kernels were launched with, one bit each (kron_kernels.hpp arm_bit_*): pair 0-7, mode 8-19, last-mode 20-27; cleared with last_kron_path
     int64_t last_jsplit = 0;     // column split of the last lane-per-row dense launch (tools)
     int32_t* sym_map = nullptr;  // symmetric kernel: device list of its (local panel, chunk) workgroups, keyed by sym_key
     size_t sym_map_cap = 0, sym_map_len = 0;

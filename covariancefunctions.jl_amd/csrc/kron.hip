@@ -109,7 +109,7 @@ static int kron_run(covgram_ctx* ctx, const void* const* factors, const int64_t*
                     const T* a_dev, T* y_dev, T alpha, T beta, T* bufA, T* bufB, T* merged) {
     int64_t cur[16];
     for (int i = 0; i < q; ++i) cur[i] = cols[i];
-    if (merged != nullptr) ctx->last_kron_path = 0;      // (the outer call; the recursion below keeps what it has)
+    if (merged != nullptr) ctx->last_kron_path = ctx->last_kron_arms = 0;      // (the outer call; the recursion below keeps what it has)
     const T* src = a_dev;
     T* dst = bufA;
     auto next_out = [&](bool final) -> T* { return final ? y_dev : dst; };

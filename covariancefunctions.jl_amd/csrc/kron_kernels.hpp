@@ -578,6 +578,14 @@ static inline int pick_nw(int strips, int64_t units, int num_cus, int minnw, int
     return nw;
 }
 
+// info key "last_kron_arms": one bit per template arm a launcher below chose (the tests compare it with their own restatement of the rules)
+//   pair  <NB1, NB2, VEC>   bit      4 [NB1 == 8] + 2 [NB2 == 8] + VEC
+//   mode  <NBP, NW, VEC>    bit  8 + 4 log2(NBP / 2) + 2 [NW == 8] + VEC
+//   modet <NBB, NW, VEC>    bit 20 + 4 [NBB == 8] + 2 [NW == 8] + VEC
+static inline int64_t arm_bit_pair(int nb1, int nb2, bool vec) { return (int64_t)1 << ((nb1 == 8 ? 4 : 0) + (nb2 == 8 ? 2 : 0) + (vec ? 1 : 0)); }
+static inline int64_t arm_bit_mode(int nbp, int nw, bool vec) { return (int64_t)1 << (8 + (nbp == 8 ? 8 : nbp == 4 ? 4 : 0) + (nw == 8 ? 2 : 0) + (vec ? 1 : 0)); }
+static inline int64_t arm_bit_modet(int nbb, int nw, bool vec) { return (int64_t)1 << (20 + (nbb == 8 ? 4 : 0) + (nw == 8 ? 2 : 0) + (vec ? 1 : 0)); }
+
 template <typename T, int NB1, int NB2>
 static void launch_pair(const PairArgs<T>& a, bool vec, dim3 grid, hipStream_t st) {
     if (vec) hipLaunchKernelGGL((kron_pair_kernel<T, NB1, NB2, true>), grid, dim3(512), 0, st, a);
@@ -611,6 +619,7 @@ int run_pair(covgram_ctx* ctx, const T* in, T* out, const T* F2, int64_t ld2, in
 #endif
     const int nb1 = (int)((K2 + 15) / 16);
     const bool wide = N2 > 64;      // output chunks of 128 columns, 64 for narrow last factors
+    ctx->last_kron_arms |= arm_bit_pair(nb1 <= 4 ? 4 : 8, wide ? 8 : 4, vec);
     if (nb1 <= 4) { if (wide) launch_pair<T, 4, 8>(a, vec, grid, ctx->stream); else launch_pair<T, 4, 4>(a, vec, grid, ctx->stream); }
     else { if (wide) launch_pair<T, 8, 8>(a, vec, grid, ctx->stream); else launch_pair<T, 8, 4>(a, vec, grid, ctx->stream); }
 #ifdef KRON_DIAG
@@ -657,6 +666,7 @@ int run_mode(covgram_ctx* ctx, const T* in, T* out, const T* F, int64_t ld, int6
     const int64_t nblocks = pre * ntiles * a.groups;
     CG_REQUIRE(nblocks < ((int64_t)1 << 31) && ntiles < ((int64_t)1 << 31), COVGRAM_EUNSUPPORTED, "kron: tensor too large for one launch");
     const dim3 grid((unsigned)nblocks);
+    ctx->last_kron_arms |= arm_bit_mode(nbp, nw, vec);
     if (nbp == 2) launch_mode<T, 2>(a, nw, vec, grid, ctx->stream);
     else if (nbp == 4) launch_mode<T, 4>(a, nw, vec, grid, ctx->stream);
     else launch_mode<T, 8>(a, nw, vec, grid, ctx->stream);
@@ -693,6 +703,7 @@ int run_modet(covgram_ctx* ctx, const T* in, T* out, const T* F, int64_t ld, int
     const int64_t nblocks = ntiles * a.groups;
     CG_REQUIRE(nblocks < ((int64_t)1 << 31), COVGRAM_EUNSUPPORTED, "kron: tensor too large for one launch");
     const dim3 grid((unsigned)nblocks);
+    ctx->last_kron_arms |= arm_bit_modet(nbb, nw, vec);
     if (nbb == 2) launch_modet<T, 2>(a, nw, vec, grid, ctx->stream);
     else launch_modet<T, 8>(a, nw, vec, grid, ctx->stream);
     return COVGRAM_OK;

@@ -77,7 +77,8 @@ extern "C" {
                                covgram_bilinear_grad_sm (the hyper-parameter gradients of a SpectralMixture Gramian's bilinear forms);
                                covgram_bilinear_input_grad_sm (their gradients with respect to the row points in one pass);
                                covgram_grad_mvm_mixed, the factor family COVGRAM_NEURALNETWORK, the option "grad_mixed_panel" and the
-                               info keys "last_grad_mixed_path" / "last_grad_mixed_jsplit" (gradient Gramians of mixed-trait composites).
+                               info keys "last_grad_mixed_path" / "last_grad_mixed_jsplit" (gradient Gramians of mixed-trait composites);
+                               the info key "last_kron_arms" (template arms of the last covgram_kron_mvm's kernels).
                                A binding checks covgram_version() against the header it mirrors at load time */
 
 typedef enum covgram_status {
@@ -226,7 +227,7 @@ int covgram_ctx_set_option(covgram_ctx* ctx, const char* key, int64_t value);
  * ran: 0 none yet or n m == 0, otherwise route + 10 DM + 1000 VR with route 1 = generic single profile, 2 = generic composite,
  * 3 = registers single profile, 4 = registers composite; DM the compiled dimension bucket, 0 for the generic kernels; VR rows per
  * thread, 1 where not applicable), "last_mfma_lds" (1: that matrix-core MVM shared its column tiles through LDS), "last_mfma_sym" (1: the last dense
- * MVM ran the symmetric upper-triangle kernel), "last_dense_sym" (1: it ran a direct-difference symmetric kernel, fp64 or fp32), "last_inkernel_reduce" (1: the last dense kernel summed its own split-J slab), "last_grad_expand" (1: the last gradient MVM ran the expanded form), "last_grad_bcast" (waves per workgroup of the broadcast kernel if the last gradient MVM ran it, else 0), "last_grad_path" (which kernels the last gradient or value-gradient MVM ran, as bits: 1 = the lane-per-row kernel, 2 = its two-column pass, 4 = the panel path (grad_wide), 8 = more than one panel, 16 = the panel path split over z slices with the separate reduce, 32 = the lane-per-row kernel with a column split > 1 and the slab reduce; 0 = no block kernel (n = 0 or m = 0); a Sum split term by term reports its last term), "last_grad_jsplit" (the column split of the last gradient MVM's lane-per-row launch, 0 if it did not run one), "last_hess_path" (0 = no Hessian MVM yet or one without rows / columns, 1 = the last covgram_hess_mvm ran its block kernel, csrc/hess_mvm.hpp), "last_block_matrix_path" (0 = no covgram_block_matrix yet or an empty product, otherwise (kind + 1) + 10 VR, VR = scalars per store instruction of the launch that ran: 1, or 2 for fp64 / 4 for fp32 on the 16-byte route), "last_sum_fused" (1: the last covgram_mvm ran a Sum on the one-pass kernels), "last_mfma_instance" (which instance of the matrix-core EQ kernels the last launch was: the template arguments of dense_mfma_eq_kernel as K2 1e5 + RT 1e4 + WPB 1e3 + LDS 100 + STAMP 10 + FMT, -(K2 10 + FMT) for the symmetric kernel, 0 otherwise — bench.py checks its recorded PMC pass against it), "last_dense_bcast" (1: the last fp64 dense MVM ran a register-broadcast kernel), "last_mfma_graded" (the number of column chunks if the last general matrix-core EQ MVM ran the graded split of "mfma_graded", else 0), "last_mfma_f16" (1: the last general matrix-core EQ MVM ran the fp16 two-way split), "last_jsplit" (the column split of the last lane-per-row dense launch), "last_kron_path" (which kernels the last covgram_kron_mvm ran, as bits: 1 = the fused last-two-modes pass, 2 = the single-mode kernel, 4 = the last-mode kernel, 8 = a rocBLAS GEMM (a factor side >= 1024, >= 256 with >= 2 GFLOP, or a shape the kernels refuse), 16 = two small trailing factors multiplied out first), "num_cus", "last_clock_khz" (median shader clock over the workgroups of the last
+ * MVM ran the symmetric upper-triangle kernel), "last_dense_sym" (1: it ran a direct-difference symmetric kernel, fp64 or fp32), "last_inkernel_reduce" (1: the last dense kernel summed its own split-J slab), "last_grad_expand" (1: the last gradient MVM ran the expanded form), "last_grad_bcast" (waves per workgroup of the broadcast kernel if the last gradient MVM ran it, else 0), "last_grad_path" (which kernels the last gradient or value-gradient MVM ran, as bits: 1 = the lane-per-row kernel, 2 = its two-column pass, 4 = the panel path (grad_wide), 8 = more than one panel, 16 = the panel path split over z slices with the separate reduce, 32 = the lane-per-row kernel with a column split > 1 and the slab reduce; 0 = no block kernel (n = 0 or m = 0); a Sum split term by term reports its last term), "last_grad_jsplit" (the column split of the last gradient MVM's lane-per-row launch, 0 if it did not run one), "last_hess_path" (0 = no Hessian MVM yet or one without rows / columns, 1 = the last covgram_hess_mvm ran its block kernel, csrc/hess_mvm.hpp), "last_block_matrix_path" (0 = no covgram_block_matrix yet or an empty product, otherwise (kind + 1) + 10 VR, VR = scalars per store instruction of the launch that ran: 1, or 2 for fp64 / 4 for fp32 on the 16-byte route), "last_sum_fused" (1: the last covgram_mvm ran a Sum on the one-pass kernels), "last_mfma_instance" (which instance of the matrix-core EQ kernels the last launch was: the template arguments of dense_mfma_eq_kernel as K2 1e5 + RT 1e4 + WPB 1e3 + LDS 100 + STAMP 10 + FMT, -(K2 10 + FMT) for the symmetric kernel, 0 otherwise — bench.py checks its recorded PMC pass against it), "last_dense_bcast" (1: the last fp64 dense MVM ran a register-broadcast kernel), "last_mfma_graded" (the number of column chunks if the last general matrix-core EQ MVM ran the graded split of "mfma_graded", else 0), "last_mfma_f16" (1: the last general matrix-core EQ MVM ran the fp16 two-way split), "last_jsplit" (the column split of the last lane-per-row dense launch), "last_kron_path" (which kernels the last covgram_kron_mvm ran, as bits: 1 = the fused last-two-modes pass, 2 = the single-mode kernel, 4 = the last-mode kernel, 8 = a rocBLAS GEMM (a factor side >= 1024, >= 256 with >= 2 GFLOP, or a shape the kernels refuse), 16 = two small trailing factors multiplied out first), "last_kron_arms" (which template arms of those kernels it launched, one bit each, cleared together with "last_kron_path": the fused pass <NB1, NB2, VEC> is bit 4 [NB1 == 8] + 2 [NB2 == 8] + VEC, the single-mode kernel <NBP, NW, VEC> bit 8 + 4 log2(NBP / 2) + 2 [NW == 8] + VEC, the last-mode kernel <NBB, NW, VEC> bit 20 + 4 [NBB == 8] + 2 [NW == 8] + VEC; a rocBLAS mode sets none), "num_cus", "last_clock_khz" (median shader clock over the workgroups of the last
  * launch made with "mfma_stamp" = 1; synchronises the stream; 0 = no stamped launch yet). */
 int covgram_ctx_get_info(covgram_ctx* ctx, const char* key, int64_t* value);
 int covgram_sync(covgram_ctx* ctx);
