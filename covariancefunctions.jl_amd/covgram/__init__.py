@@ -19,8 +19,8 @@ from .kernels import (AbstractKernel, MercerKernel, StationaryKernel, IsotropicK
                       GenericInput, IsotropicInput, DotProductInput, StationaryInput, StationaryLinearFunctionalInput,
                       PeriodicInput, input_trait, register_input_trait, ismercer, isstationary, isisotropic, isdot,
                       device_spec, Spectral, SpectralMixture, SM, spectral_mixture_spec, require_sm_spec, require_hessian_spec, require_vgh_spec, require_pivchol_spec, DomainError,
-                      hyperparameters, with_hyperparameters, spectral_mixture_chain_rules, mixed_gradient_spec, require_mixed_gradient_spec)
-from .gramian import (Gramian, BlockGramian, MixedBlockGramian, HessianGramian, ValueGradientHessianGramian, SymmetricToeplitz, Toeplitz, Circulant, KroneckerProduct, kronecker,
+                      hyperparameters, with_hyperparameters, spectral_mixture_chain_rules, mixed_gradient_spec, require_mixed_gradient_spec, mixed_spec, require_mixed_spec)
+from .gramian import (Gramian, MixedGramian, BlockGramian, MixedBlockGramian, HessianGramian, ValueGradientHessianGramian, SymmetricToeplitz, Toeplitz, Circulant, KroneckerProduct, kronecker,
                       SeparableGramian, LazyMatrixProduct, LazyMatrixSum, ScaledOperator, LinearMapBlockGramian, CosineBlockGramian, PointJacobianBlockGramian, Fill, LazyOperator, LazyGrid, StepRangeLen,
                       srange, gramian, mul_, get_ctx, set_option, get_info, kernel_time, SparseGramian, sparse, decay_radius,
                       BarnesHutFactorization, require_barneshut_spec, SpectralMixtureGramian, bilinear_gradient, bilinear_chain_rules,

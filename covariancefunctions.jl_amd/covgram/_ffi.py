@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("COVGRAM_LIB") or os.path.normpath(os.path.join(_HERE,
 # enums (include/covgram.h)
 EQ, EXP, RQ, GAMMAEXP, CAUCHY, IMQ, MATERNP, DOT, EXPDOT, MATERN, ASINDOT = range(11)
 CONSTANT, COMPOSITE = 100, 101
-NEURALNETWORK = 102   # COVGRAM_NEURALNETWORK: a factor of the composite of covgram_grad_mvm_mixed only (param = sigma, trait 0)
+NEURALNETWORK = 102   # COVGRAM_NEURALNETWORK: a factor of the mixed-trait composites only (covgram_grad_mvm_mixed, covgram_mvm_mixed; param = sigma, trait 0)
 COMPOSITE_MAX_TERMS, COMPOSITE_MAX_FACTORS = 8, 8
 ISOTROPIC, DOTPRODUCT = 1, 2
 F32, F64 = 0, 1
@@ -109,6 +109,8 @@ PROTOTYPES = {
     "covgram_grad_mvm": (C.c_int, [_P, _KP, _P, _P, _P, _I64, _P, _I64, _I32, _D, _D, _I32]),
     "covgram_valgrad_mvm": (C.c_int, [_P, _KP, _P, _P, _P, _I64, _P, _I64, _I32, _D, _D, _I32]),
     "covgram_grad_mvm_mixed": (C.c_int, [_P, C.POINTER(covgram_kernel_composite), _P, _P, _P, _I64, _P, _I64, _I32, _D, _D, _I32, _I32]),
+    "covgram_mvm_mixed": (C.c_int, [_P, C.POINTER(covgram_kernel_composite), _P, _P, _P, _I64, _P, _I64, _I32, _D, _D, _I32]),
+    "covgram_matrix_mixed": (C.c_int, [_P, C.POINTER(covgram_kernel_composite), _P, _P, _P, _I64, _I32]),
     "covgram_hess_mvm": (C.c_int, [_P, _KP, _P, _P, _P, _I64, _P, _I64, _I32, _D, _D, _I32]),
     "covgram_valgradhess_mvm": (C.c_int, [_P, _KP, _P, _P, _P, _I64, _P, _I64, _I32, _D, _D, _I32]),
     "covgram_block_matrix": (C.c_int, [_P, _I32, _KP, _P, _P, _P, _I64, _I32]),

@@ -46,6 +46,8 @@ class _GramProduct(torch.autograd.Function):
                 k = K.with_hyperparameters(k, theta.detach().cpu().numpy())
             if structural:                                      # what can be refused before anything is built
                 inner = k.k if isinstance(k, K.ScaledInputKernel) and k.diagonal else k
+                if isinstance(inner, K.AbstractKernel) and K.device_spec(inner) is None and K.spectral_mixture_spec(inner) is None and K.mixed_spec(inner) is not None:
+                    raise _refuse("MixedGramian")               # what gramian() would build: no gradient passes exist for it
                 _bilinear_plan(inner, "gram_product")
                 for p in (x, y):
                     if p is not None and not isinstance(p, torch.Tensor):

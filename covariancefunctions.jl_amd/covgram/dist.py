@@ -139,6 +139,11 @@ class ShardedGramian:
         """block: entries per point of the flat vectors — 1 for scalar kernels, d for GradientKernel, d + 1 for
         ValueGradientKernel Gramians (inferred from the kernel when not given): rank g then owns the rows
         [lo_g * block, hi_g * block) of the flat output and the all-gather moves ceil(n/P) * block entries per rank."""
+        if local_factory is None:                               # a mixed-trait composite has no sharded form (no covgram_kernel encoding for the C-ABI route)
+            from . import kernels as _K
+            if isinstance(k, _K.AbstractKernel) and _K.device_spec(k) is None and _K.spectral_mixture_spec(k) is None and _K.mixed_spec(k) is not None:
+                from ._ffi import UnsupportedKernel, EUNSUPPORTED
+                raise UnsupportedKernel(EUNSUPPORTED, f"ShardedGramian: MixedGramian (the Gramian of {type(k).__name__} with factors of different input traits) has no sharded form")
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0

@@ -21,7 +21,7 @@ import torch
 
 from . import _ffi
 from . import kernels as K
-from .gramian import Gramian, LazyOperator, SpectralMixtureGramian, _axpby_, _dtype_code
+from .gramian import Gramian, LazyOperator, MixedGramian, SpectralMixtureGramian, _axpby_, _dtype_code
 
 DEFAULT_MAX_CHOLESKY_SIZE = 2 ** 14     # src/gramian.jl:201
 DEFAULT_TOL = 1e-6                      # src/gramian.jl:202
@@ -138,6 +138,8 @@ def pivoted_cholesky(G: Gramian, max_rank: int, tol: float = 0.0) -> PivotedChol
     G never formed.  The only host read is `rank`, at the end.  Returns the PivotedCholesky of `cholesky(G, pivoted=True)`: L is
     n x rank (rows in the original order), piv = the pivots followed by the remaining indices in ascending order, and
     `residual_diagonal` = diag(G - L L')."""
+    if isinstance(G, MixedGramian):
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, "pivoted_cholesky: MixedGramian is not supported (one isotropic profile only)")
     if not isinstance(G, Gramian):
         raise NotImplementedError("pivoted_cholesky: a Gramian is expected")
     if G.y is not G.x:

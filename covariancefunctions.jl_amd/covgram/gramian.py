@@ -688,6 +688,41 @@ class SpectralMixtureGramian(_OwnsHandle, _PointPairGramian):
         _ffi.check(_ffi.lib().covgram_sm_matrix(self.handle, self._px.handle, self._py.handle, out, ldo, _ffi.DEVICE))
 
 
+class MixedGramian(_PointPairGramian):
+    """Lazy SCALAR Gramian of a Sum / Product / Power whose factors do not share one input trait — EQ() + Dot(), EQ() * (Dot()**2 + 1),
+    MaternP(2) + Dot()**2 + NeuralNetwork(): GenericInput in the reference's terms, its threaded loop src/gramian.jl:78-87.  `mul!` is
+    covgram_mvm_mixed (plain terms on the kernels behind covgram_mvm, the rest in one fused pass), Matrix(G) and indexing are
+    covgram_matrix_mixed.  `gramian` builds it for exactly the kernels that have neither a covgram_kernel encoding nor a
+    spectral-mixture one and that kernels.mixed_spec lowers.  Hyper-parameter / input gradients, sparse, Barnes-Hut, pivoted Cholesky and
+    sharded forms do not exist: they raise UnsupportedKernel naming this class."""
+
+    def __init__(self, k, x, y=None, spec=None):
+        self._spec = spec if spec is not None else K.require_mixed_spec(k)   # refusals come before any device call
+        super().__init__(k, x, y)
+
+    def _on(self, xi, yj):
+        return MixedGramian(self.k, xi, yj, self._spec)
+
+    def isposdef(self):
+        return K.ismercer(self.k) and self.issymmetric()
+
+    def mul_(self, y, a, alpha=1.0, beta=0.0):
+        """y ← α G a + β y for a vector or a matrix a; β == 0 ⇒ y's previous contents (NaN included) are ignored."""
+        a = _rhs(self, y, a)
+        ctx = self._px.ctx.bind_stream()
+        return _staged(y, a, beta, lambda ap, lda, yp, ldy, nrhs: _ffi.check(_ffi.lib().covgram_mvm_mixed(
+            ctx, C.byref(self._spec), self._px.handle, self._py.handle, _ffi._P(ap), lda, _ffi._P(yp), ldy, nrhs, float(alpha), float(beta), _ffi.DEVICE)))
+
+    def _matrix(self, out, ldo):
+        _ffi.check(_ffi.lib().covgram_matrix_mixed(self._px.ctx.handle, C.byref(self._spec), self._px.handle, self._py.handle, out, ldo, _ffi.DEVICE))
+
+    def sym_partial_supported(self, world: int = 1) -> bool:
+        return False
+
+    def sym_partial_(self, y, a, rank: int, world: int):
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, "sym_partial_: MixedGramian has no symmetric (upper-triangle) partial form")
+
+
 def _sm_setup(fn, G, U, A):
     """What spectral_mixture_gradient and spectral_mixture_input_gradient (`fn`: the name in the messages) share: the refusals, before any
     device call, and the weights as the device wants them.  Returns (U, A, Ut, At): U (n, nvec) and A (m, nvec) in the Gramian's dtype
@@ -1494,11 +1529,15 @@ def _first_column(k, x: torch.Tensor, y0: torch.Tensor) -> torch.Tensor:
 
 def _plain_gramian(k, x, y=None):
     """The lazy Gramian without structure: the fused spectral-mixture operator exactly when k has no covgram_kernel encoding but is a
-    mixture the covgram_sm kernels take; otherwise Gramian (whose products raise UnsupportedKernel for a kernel without a device path)."""
+    mixture the covgram_sm kernels take; MixedGramian exactly when it has neither encoding and kernels.mixed_spec lowers it; otherwise
+    Gramian (whose products raise UnsupportedKernel for a kernel without a device path)."""
     if isinstance(k, K.AbstractKernel) and K.device_spec(k) is None:
         spec = K.spectral_mixture_spec(k, _point_dim(x))
         if spec is not None:
             return SpectralMixtureGramian(k, x, y, spec)
+        spec = K.mixed_spec(k)
+        if spec is not None:
+            return MixedGramian(k, x, y, spec)
     return Gramian(k, x, y)
 
 

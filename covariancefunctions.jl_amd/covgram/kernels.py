@@ -800,11 +800,21 @@ def _mixed_leaf(k):
     return s
 
 
-def _mixed_lower(k):
+def _mixed_value_leaf(k):
+    """The leaf hook of the scalar mixed Gramians: only a leaf's VALUE is needed, so every profile _simple_spec lowers is taken — the
+    ones singular at zero distance and Matern(ν) too — and NeuralNetwork(σ); CosineKernel alone is refused by name."""
+    if isinstance(k, NeuralNetwork):
+        return _mixed_leaf(k)
+    if isinstance(k, CosineKernel):
+        raise _Refusal(f"{type(k).__name__} belongs with the spectral mixtures (spectral_mixture_spec)")
+    return _simple_spec(k)
+
+
+def _mixed_lower(k, leaf=_mixed_leaf):
     """The mixed composite of `k`, or _Refusal: the normal form of device_spec with every factor on its own trait (the head's is 0), a
     term's factors sorted with the power last, the constant term where it first appeared, and an expression that cancels lowered to
-    the one term 0."""
-    merged = _merge_like_terms(_normal_form(k, _mixed_leaf), lambda f: (f.family, f.p, f.param, f.lengthscale, f.power))
+    the one term 0.  `leaf`: the hook of the gradient kernels (_mixed_leaf) or of the scalar Gramians (_mixed_value_leaf)."""
+    merged = _merge_like_terms(_normal_form(k, leaf), lambda f: (f.family, f.p, f.param, f.lengthscale, f.power))
     terms = [term for term in merged.values() if term[0] != 0.0] or [(0.0, [])]
     ok, nfac = _within_limits(terms)
     if not ok:
@@ -831,6 +841,25 @@ def require_mixed_gradient_spec(k):
         return _mixed_lower(k)
     except _Refusal as why:
         raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"gradient kernel of a mixed-trait composite ({type(k).__name__}): {why}") from None
+
+
+def mixed_spec(k):
+    """The covgram_kernel_composite that covgram_mvm_mixed / covgram_matrix_mixed run for the SCALAR Gramian of `k`, or None: the normal
+    form of mixed_gradient_spec (same walker, merge, order rules, writer and limits: 8 terms, 8 factors) over every leaf _simple_spec
+    lowers plus NeuralNetwork(σ).  For every kernel both accept, the two composites are equal field by field."""
+    try:
+        return require_mixed_spec(k)
+    except _ffi.UnsupportedKernel:
+        return None
+
+
+def require_mixed_spec(k):
+    try:
+        if not isinstance(k, AbstractKernel):
+            raise _Refusal(f"{type(k).__name__} is not a kernel expression")
+        return _mixed_lower(k, _mixed_value_leaf)
+    except _Refusal as why:
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"Gramian of a mixed-trait composite ({type(k).__name__}): {why}") from None
 
 
 # ----------------------------------------------------------------------------------------------

@@ -579,6 +579,20 @@ int DenseMvm::run_lanes() {
     return COVGRAM_OK;
 }
 
+// the product of ONE kernel on device-resident a and y that do not overlap: by the route of DenseMvm, or (split: its Sum split) term by term
+static int dense_mvm_run(covgram_ctx* ctx, const covgram_kernel* k, const HostKernel& hk, const SumSplit* split, const covgram_points* X,
+                         const covgram_points* Y, const void* a, int64_t lda, void* y, int64_t ldy, int32_t nrhs, double alpha, double beta, int rank, int world) {
+    if (!split) return DenseMvm{ctx, k, hk, X, Y, a, lda, y, ldy, nrhs, alpha, beta, rank, world}.run();
+    return sum_split_run(
+        *split, beta,
+        [&](const covgram_kernel* tk, double tbeta) {
+            HostKernel thk;
+            const int trc = make_host_kernel(tk, X->dtype, false, &thk);
+            return trc ? trc : DenseMvm{ctx, tk, thk, X, Y, a, lda, y, ldy, nrhs, alpha, tbeta, rank, world}.run();
+        },
+        [&] { return constant_term_mvm(ctx, X->dtype, a, Y->n, lda, 1, y, X->n, ldy, 1, nrhs, alpha * split->constant); });
+}
+
 // covgram_mvm, and (world > 0) the direct-difference form of covgram_mvm_sym_partial: validation, the Sum split, staging
 static int dense_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, const void* a, int64_t lda, void* y,
                      int64_t ldy, int32_t nrhs, double alpha, double beta, int32_t loc, int rank, int world) {
@@ -603,19 +617,22 @@ static int dense_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram_po
     Staged st;
     rc = st.begin(ctx, loc, dtype_size(X->dtype), a, lda, m, y, ldy, n, nrhs, beta);
     if (rc) return rc;
-    if (!sum) rc = DenseMvm{ctx, k, hk, X, Y, st.a, st.lda, st.y, st.ldy, nrhs, alpha, beta, rank, world}.run();
-    else
-        rc = sum_split_run(
-            split, beta,
-            [&](const covgram_kernel* tk, double tbeta) {
-                HostKernel thk;
-                const int trc = make_host_kernel(tk, X->dtype, false, &thk);
-                return trc ? trc : DenseMvm{ctx, tk, thk, X, Y, st.a, st.lda, st.y, st.ldy, nrhs, alpha, tbeta, rank, world}.run();
-            },
-            [&] { return constant_term_mvm(ctx, X->dtype, st.a, m, st.lda, 1, st.y, n, st.ldy, 1, nrhs, alpha * split.constant); });
+    rc = dense_mvm_run(ctx, k, hk, sum ? &split : nullptr, X, Y, st.a, st.lda, st.y, st.ldy, nrhs, alpha, beta, rank, world);
     if (rc) return rc;
     CG_CHECK_HIP(hipGetLastError());
     return st.finish();
+}
+
+// (driver.hpp) covgram_mvm's product behind its staging, for a driver that has staged a and y itself (mixed_mvm.hip)
+int dense_mvm_on_device(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, const void* a, int64_t lda, void* y,
+                        int64_t ldy, int32_t nrhs, double alpha, double beta) {
+    ctx->last_sum_fused = 0;
+    SumSplit split;
+    const bool sum = !sum_fused_applies(ctx, k, X, Y, nrhs) && composite_sum_terms(ctx, k, COVGRAM_DEVICE, &split);
+    HostKernel hk;
+    const int rc = make_host_kernel(k, X->dtype, false, &hk);
+    if (rc) return rc;
+    return dense_mvm_run(ctx, k, hk, sum ? &split : nullptr, X, Y, a, lda, y, ldy, nrhs, alpha, beta, 0, 0);
 }
 
 }  // namespace covgram
@@ -708,13 +725,14 @@ static const CtxField kOptions[] = {
     CG_FIELD(mfma_gate_pct), CG_FIELD(mfma_fuse_w), CG_FIELD(toeplitz_real_spectrum), CG_FIELD(rows_per_lane), CG_FIELD(jsplit), CG_FIELD(target_wgs),
     CG_FIELD(grad_keep_r), CG_FIELD(grad_expand), CG_FIELD(grad_bcast), CG_FIELD(mfma_lds), CG_FIELD(mfma_sym), CG_FIELD(dense_sym), CG_FIELD(dense_bcast),
     CG_FIELD(mfma_stamp), CG_FIELD(mfma_graded), CG_FIELD(inkernel_reduce), CG_FIELD(matrix_variant), CG_FIELD(mfma_mrhs), CG_FIELD(composite_termwise), CG_FIELD(sum_fused),
-    CG_FIELD(lowrank_reverse), CG_FIELD(mfma_sym_rt), CG_FIELD(mfma_sym_st), CG_FIELD(lowrank_wgs), CG_FIELD(grad_mixed_panel), CG_FIELD(time_kernels)};
+    CG_FIELD(lowrank_reverse), CG_FIELD(mfma_sym_rt), CG_FIELD(mfma_sym_st), CG_FIELD(lowrank_wgs), CG_FIELD(grad_mixed_panel), CG_FIELD(mixed_fuse), CG_FIELD(time_kernels)};
 static const CtxField kInfo[] = {
     CG_FIELD(last_dense_path), CG_FIELD(last_jsplit), CG_FIELD(last_kron_path), CG_FIELD(last_mfma_lds), CG_FIELD(last_mfma_sym), CG_FIELD(last_dense_sym),
     CG_FIELD(last_dense_bcast), CG_FIELD(last_mfma_f16), CG_FIELD(last_inkernel_reduce), CG_FIELD(last_grad_expand), CG_FIELD(last_grad_bcast),
     CG_FIELD(last_grad_path), CG_FIELD(last_grad_jsplit), CG_FIELD(last_hess_path), CG_FIELD(last_vgh_path), CG_FIELD(last_matrix_path),
     CG_FIELD(last_block_matrix_path), CG_FIELD(last_sum_fused), CG_FIELD(last_mfma_instance), CG_FIELD(last_mfma_graded), CG_FIELD(last_mfma_sym_rt), CG_FIELD(last_grad_mixed_path),
-    CG_FIELD(last_grad_mixed_jsplit), CG_FIELD(last_kron_arms), CG_FIELD(num_cus)};
+    CG_FIELD(last_grad_mixed_jsplit), CG_FIELD(last_kron_arms), CG_FIELD(last_mixed_path), CG_FIELD(last_mixed_jsplit),
+    CG_FIELD(last_mixed_matrix_path), CG_FIELD(num_cus)};
 #undef CG_FIELD
 
 int covgram_ctx_set_option(covgram_ctx* ctx, const char* key, int64_t value) {

@@ -149,9 +149,11 @@ struct HostKernel {
 
 // Validates `k` and fills the parameter block.  `for_gradient` keeps gamma = 1/l (no log2e fold).
 int make_host_kernel(const covgram_kernel* k, int dtype, bool for_gradient, HostKernel* out);
-// The composite behind make_host_kernel (mixed = false: one trait over the head and every factor), or the mixed-trait composite of
-// covgram_grad_mvm_mixed (mixed = true: every factor on its own trait, NeuralNetwork factors, tu_family = FAM_EXPR_DOT).
-int make_composite_kernel(const covgram_kernel_composite* c, int dtype, bool mixed, HostKernel* out);
+// The composite behind make_host_kernel (COMPOSITE_ONE_TRAIT: one trait over the head and every factor), or a mixed-trait composite (every
+// factor on its own trait, NeuralNetwork factors, tu_family = FAM_EXPR_DOT): that of covgram_grad_mvm_mixed (COMPOSITE_MIXED_GRADIENT: the
+// leaves without a jet refused) or that of covgram_mvm_mixed / covgram_matrix_mixed (COMPOSITE_MIXED_VALUES: every leaf phi_any evaluates).
+enum CompositeMode { COMPOSITE_ONE_TRAIT, COMPOSITE_MIXED_GRADIENT, COMPOSITE_MIXED_VALUES };
+int make_composite_kernel(const covgram_kernel_composite* c, int dtype, CompositeMode mode, HostKernel* out);
 
 template <typename T>
 inline KParams<T> cast_params(const KParams<double>& s) {
@@ -317,6 +319,10 @@ struct covgram_ctx {
     int64_t grad_mixed_panel = 0;       // covgram_grad_mvm_mixed, panel route: cap on the columns of a panel (0 = the 256 MB rule of the coefficient slabs)
     int64_t last_grad_mixed_path = 0;   // kernels of the last covgram_grad_mvm_mixed, bits: 1 lane-per-row, 2 panel route, 4 more than one panel, 8 z slices + reduce, 16 column split + slab reduce
     int64_t last_grad_mixed_jsplit = 0; // column split of its lane-per-row launch (0: it did not run one)
+    int64_t mixed_fuse = 0;             // covgram_mvm_mixed: 0 = plain terms (one trait, no NeuralNetwork) go to the kernels behind covgram_mvm, 1 = every term in the fused kernel
+    int64_t last_mixed_path = 0;        // parts of the last covgram_mvm_mixed, bits: 1 fused lane-per-row, 2 fused chunked, 4 isotropic group delegated, 8 dot-product group delegated, 16 fused launch split over the columns, 32 constant term added
+    int64_t last_mixed_jsplit = 0;      // column split of its fused launch (0: the fused kernel did not run)
+    int64_t last_mixed_matrix_path = 0; // covgram_matrix_mixed: 1 = x_i in registers (d <= 32), 2 = chunked; 0: none yet, or n m == 0
     // optional HIP-event bracketing of the dominant kernel of each MVM (bench.py's live roofline measurement)
     int64_t time_kernels = 0;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> timers;

@@ -1,5 +1,5 @@
 // driver.hpp — what the C-ABI drivers share: staging of host pointers, dtype dispatch, the timer bracket, the bracket of a block MVM entry, the
-// Sum split.  Served units: the point-pair entries (api.hip, matrix.hip, block_mvm.hip, grad_mixed.hip — these two through grad_driver.hpp —,
+// Sum split.  Served units: the point-pair entries (api.hip, matrix.hip, mixed_mvm.hip, block_mvm.hip, grad_mixed.hip — these two through grad_driver.hpp —,
 // sm.hip, sparse.hip, bilin_grad.hip, input_grad.hip, dense_mfma.hip, pivchol.hip), kernel_params.hip (the family names of its refusals) and the
 // structured operators (toeplitz.hip, toeplitz_direct.hip, kron.hip, lowrank.hip, barneshut.hip).  Host code only; the per-family kernel units
 // include common.hpp, not this.
@@ -139,6 +139,12 @@ inline int sum_split_run(const SumSplit& s, double beta, RunTerm run_term, AddCo
     }
     return add_constant();
 }
+
+// covgram_mvm's product behind its staging (api.hip): y <- alpha G a + beta y for one covgram_kernel — a single profile or a one-trait
+// composite, a Sum split per term — on device-resident a and y that do not overlap, by the routes of the dense driver (matrix cores,
+// factored dot product, lane per row, ...).  For a driver that has staged a and y itself and sends parts of its kernel there (mixed_mvm.hip).
+int dense_mvm_on_device(covgram_ctx* ctx, const covgram_kernel* k, const covgram_points* X, const covgram_points* Y, const void* a, int64_t lda, void* y,
+                        int64_t ldy, int32_t nrhs, double alpha, double beta);
 
 // The kernels that HessianKernel(k) / ValueGradientHessianKernel(k) (w: the wrapper's name) have a device path for: single profiles with
 // closed-form derivatives up to the fourth, no Power wrapper, d <= HESS_MAX_D.  The refusals of covgram_hess_mvm,

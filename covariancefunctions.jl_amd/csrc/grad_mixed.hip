@@ -108,7 +108,7 @@ int covgram_grad_mvm_mixed(covgram_ctx* ctx, const covgram_kernel_composite* k, 
             return COVGRAM_OK;
         },
         [&]() -> int {
-            const int rc = make_composite_kernel(k, X->dtype, true, &hk);
+            const int rc = make_composite_kernel(k, X->dtype, COMPOSITE_MIXED_GRADIENT, &hk);
             if (rc == COVGRAM_OK) { ctx->last_grad_mixed_path = 0; ctx->last_grad_mixed_jsplit = 0; }
             return rc;
         },

@@ -43,11 +43,15 @@ static void maternp_derivs0(int p, long double* d /* d[1..p] */) {
 static int make_simple_kernel(const covgram_kernel* k, int dtype, bool for_gradient, HostKernel* out);
 
 // Composite: every factor keeps its own parameter block with gamma = 1/l (unfolded EQ); rows and columns stay unscaled.
-// mixed (the composite of covgram_grad_mvm_mixed, grad_mixed.hpp): the head's trait binds nobody, every factor is validated on its OWN
-// trait, a NeuralNetwork factor keeps sigma in fkp.param, and the leaves without a jet in (x.y, |x|^2, |y|^2) are refused.
-int make_composite_kernel(const covgram_kernel_composite* c, int dtype, bool mixed, HostKernel* out) {
+// mixed (the composites of covgram_grad_mvm_mixed, grad_mixed.hpp, and of covgram_mvm_mixed / covgram_matrix_mixed, mixed_mvm.hpp): the head's
+// trait binds nobody, every factor is validated on its OWN trait and a NeuralNetwork factor keeps sigma in fkp.param; the gradient mode
+// refuses the leaves without a jet in (x.y, |x|^2, |y|^2), the values mode takes every leaf.
+int make_composite_kernel(const covgram_kernel_composite* c, int dtype, CompositeMode mode, HostKernel* out) {
     const covgram_kernel& h = c->head;
-    if (mixed) CG_REQUIRE(h.family == COVGRAM_COMPOSITE, COVGRAM_EINVAL, "covgram_grad_mvm_mixed takes a covgram_kernel_composite (head.family = %d)", h.family);
+    const bool mixed = mode != COMPOSITE_ONE_TRAIT;
+    if (mixed)
+        CG_REQUIRE(h.family == COVGRAM_COMPOSITE, COVGRAM_EINVAL, "%s takes a covgram_kernel_composite (head.family = %d)",
+                   mode == COMPOSITE_MIXED_GRADIENT ? "covgram_grad_mvm_mixed" : "covgram_mvm_mixed / covgram_matrix_mixed", h.family);
     else CG_REQUIRE(h.trait == COVGRAM_ISOTROPIC || h.trait == COVGRAM_DOTPRODUCT, COVGRAM_EINVAL, "composite: bad trait %d", h.trait);
     CG_REQUIRE(h.power == 1 && h.lengthscale == 1.0, COVGRAM_EINVAL, "composite head must have power == 1 and lengthscale == 1");
     CG_REQUIRE(c->nterms >= 1 && c->nterms <= EXPR_MAXT, COVGRAM_EUNSUPPORTED, "composite: %d terms (1..%d supported)", c->nterms, EXPR_MAXT);
@@ -76,14 +80,14 @@ int make_composite_kernel(const covgram_kernel_composite* c, int dtype, bool mix
                 CG_REQUIRE(fk.lengthscale == 1.0, COVGRAM_EINVAL, "Lengthscale applies to isotropic kernels only");
                 kp.gamma = 1.0; kp.gamma2 = 1.0; kp.param = fk.param; kp.power = fk.power;
             } else {
-                if (mixed) {
-                    CG_REQUIRE(fk.family >= 0 && fk.family < COVGRAM_NFAMILY, COVGRAM_EUNSUPPORTED, "unknown kernel family %d", fk.family);
+                if (mixed) CG_REQUIRE(fk.family >= 0 && fk.family < COVGRAM_NFAMILY, COVGRAM_EUNSUPPORTED, "unknown kernel family %d", fk.family);
+                if (mode == COMPOSITE_MIXED_GRADIENT) {
                     const char* name = kFamilyNames[fk.family];
                     CG_REQUIRE(fk.family != COVGRAM_EXP && fk.family != COVGRAM_GAMMAEXP && !(fk.family == COVGRAM_MATERNP && fk.p == 0), COVGRAM_EUNSUPPORTED,
                                "mixed gradient kernel: the leaf %s%s is singular at zero distance and has no device path here", name,
                                fk.family == COVGRAM_MATERNP ? "(0)" : "");
                     CG_REQUIRE(fk.family != COVGRAM_MATERN, COVGRAM_EUNSUPPORTED, "mixed gradient kernel: the leaf %s(nu) has no device path here (MaternP does)", name);
-                } else {
+                } else if (!mixed) {
                     CG_REQUIRE(fk.trait == h.trait, COVGRAM_EINVAL, "composite: factor %d has trait %d, head has %d (GenericInput is not a device path)",
                                nin, fk.trait, h.trait);
                 }
@@ -103,7 +107,7 @@ int make_composite_kernel(const covgram_kernel_composite* c, int dtype, bool mix
 
 int make_host_kernel(const covgram_kernel* k, int dtype, bool for_gradient, HostKernel* out) {
     CG_REQUIRE(k != nullptr, COVGRAM_EINVAL, "kernel is NULL");
-    if (k->family == COVGRAM_COMPOSITE) return make_composite_kernel((const covgram_kernel_composite*)k, dtype, false, out);
+    if (k->family == COVGRAM_COMPOSITE) return make_composite_kernel((const covgram_kernel_composite*)k, dtype, COMPOSITE_ONE_TRAIT, out);
     return make_simple_kernel(k, dtype, for_gradient, out);
 }
 

@@ -281,6 +281,23 @@ function mixed_or(G::Gramian, value::Integer, y::StridedVecOrMat{T}, a::StridedV
                 Float64(α), Float64(β), Int32(value), HOST))
     return y
 end
+# --- the SCALAR Gramian of such a composite (src/gramian.jl:78-87 on a GenericInput kernel): plain wrappers of covgram_mvm_mixed and
+# covgram_matrix_mixed on a CComposite the caller has built (every factor with its own trait; no lowering on this side)
+function mixed_mul!(y::StridedVecOrMat{T}, spec::CComposite, X::Points, Y::Points, a::StridedVecOrMat{T}, α::Real = 1, β::Real = 0) where {T <: DevFloat}
+    size(y, 2) == size(a, 2) || throw(DimensionMismatch("mixed_mul!: y has $(size(y, 2)) columns, a has $(size(a, 2))"))
+    check(ccall((:covgram_mvm_mixed, libcovgram), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int32, Float64, Float64, Int32),
+                ctx(), Ref(spec), X.handle, Y.handle, a, max(stride(a, 2), size(a, 1)), y, max(stride(y, 2), size(y, 1)), Int32(size(a, 2)),
+                Float64(α), Float64(β), HOST))
+    return y
+end
+function mixed_matrix!(out::StridedMatrix{T}, spec::CComposite, X::Points, Y::Points) where {T <: DevFloat}
+    check(ccall((:covgram_matrix_mixed, libcovgram), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32),
+                ctx(), Ref(spec), X.handle, Y.handle, out, max(stride(out, 2), size(out, 1)), HOST))
+    return out
+end
+
 function LinearAlgebra.mul!(y::StridedVector{T}, B::BlockFactorizations.BlockFactorization{T, <:Gramian{<:Any, <:GradientKernel}},
                             a::StridedVector{T}, α::Real = 1, β::Real = 0) where {T <: DevFloat}
     G = B.A

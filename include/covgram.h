@@ -78,7 +78,9 @@ extern "C" {
                                covgram_bilinear_input_grad_sm (their gradients with respect to the row points in one pass);
                                covgram_grad_mvm_mixed, the factor family COVGRAM_NEURALNETWORK, the option "grad_mixed_panel" and the
                                info keys "last_grad_mixed_path" / "last_grad_mixed_jsplit" (gradient Gramians of mixed-trait composites);
-                               the info key "last_kron_arms" (template arms of the last covgram_kron_mvm's kernels).
+                               the info key "last_kron_arms" (template arms of the last covgram_kron_mvm's kernels);
+                               covgram_mvm_mixed and covgram_matrix_mixed, the option "mixed_fuse" and the info keys "last_mixed_path" /
+                               "last_mixed_jsplit" / "last_mixed_matrix_path" (scalar Gramians of mixed-trait composites).
                                A binding checks covgram_version() against the header it mirrors at load time */
 
 typedef enum covgram_status {
@@ -109,7 +111,7 @@ typedef enum covgram_family {
     /* only inside / as the head of a covgram_kernel_composite: */
     COVGRAM_CONSTANT = 100, /* factor: the constant `scale`            src/stationary.jl:27-34   */
     COVGRAM_COMPOSITE = 101, /* head of a covgram_kernel_composite      src/algebra.jl:5-63       */
-    /* only as a factor of the composite passed to covgram_grad_mvm_mixed: */
+    /* only as a factor of the composite passed to covgram_grad_mvm_mixed, covgram_mvm_mixed or covgram_matrix_mixed: */
     COVGRAM_NEURALNETWORK = 102 /* factor: NeuralNetwork(sigma) on the RAW points, (2/pi) asin((x.y + sigma) / sqrt((1 + |x|^2 + sigma)
                                    (1 + |y|^2 + sigma))); param = sigma >= 0, trait = 0 (neither trait), lengthscale = 1   src/mercer.jl:73-85 */
 } covgram_family;
@@ -359,6 +361,38 @@ int covgram_valgrad_mvm(covgram_ctx* ctx, const covgram_kernel* k, const covgram
 int covgram_grad_mvm_mixed(covgram_ctx* ctx, const covgram_kernel_composite* k, const covgram_points* X, const covgram_points* Y,
                            const void* a, int64_t lda, void* y, int64_t ldy, int32_t nrhs, double alpha, double beta, int32_t value,
                            int32_t loc);
+
+/* The SCALAR Gramian (n x m) of such a composite — EQ() + Dot(), EQ() * (Dot()^2 + 1), MaternP(2) + Dot()^2 + NN(): GenericInput in the
+ * reference's terms, its threaded loop src/gramian.jl:78-87 — with the semantics of covgram_mvm: y <- alpha G a + beta y on nrhs columns
+ * (lda >= m, ldy >= n); beta == 0 never reads y; m = 0 gives beta y; n = 0 returns at once; a and y may overlap in any way (a is then read
+ * from a private copy).  k is the composite covgram_grad_mvm_mixed takes: head.trait is not read, every factor is validated on its own
+ * trait.  Factors: COVGRAM_CONSTANT; every isotropic family — EQ, Exponential, RQ, GammaExponential, Cauchy, IMQ, MaternP(p >= 0),
+ * Matern(nu): only the VALUE of a leaf is needed, so the leaves the gradient entry refuses are taken —, each with its own lengthscale, on
+ * |x - y|^2 formed by direct differences of the stored coordinates (no centring, no expanded form); Dot, ExponentialDot, AsinDot on x.y;
+ * COVGRAM_NEURALNETWORK (param = sigma >= 0) on the raw points; every one with its own power >= 1 and scale.
+ * The driver partitions the terms (option "mixed_fuse" = 0, the default).  A term is PLAIN when all its profile factors share one trait
+ * and none is NeuralNetwork.  The plain isotropic terms form one single-trait composite and the plain dot-product terms another (one term
+ * of one factor: a plain covgram_kernel); each runs on the device-resident a and y through the path behind covgram_mvm — matrix cores,
+ * the factored dot product, its own Sum split.  A trait's plain terms stay in the fused kernel where the fused terms evaluate leaves of
+ * that trait themselves (EQ * Dot^2 + EQ: one pass), and where covgram_mvm's validation refuses the group.  Terms of Constants only add
+ * c sum(a) to every row.  The remaining terms — Products across traits, anything with a NeuralNetwork factor — run in ONE fused kernel:
+ * lane per row for padded d <= 32 (buckets 4, 8, 16, 32), chunked beyond (any d); right-hand sides in groups of four accumulators per
+ * kernel evaluation, the remainder one by one; a fixed-order column split with a slab reduce (deterministic run to run).  Parts run in
+ * the order isotropic, dot product, fused, constant; the first applies beta, the others add.  With nothing to delegate, or with
+ * "mixed_fuse" = 1, every term, constants included, runs in the fused kernel.
+ * Info key "last_mixed_path", bits: 1 = fused lane-per-row route, 2 = fused chunked route, 4 = isotropic group delegated, 8 = dot-product
+ * group delegated, 16 = fused launch split over the columns, 32 = constant term added; 0 = no kernel ran.  "last_mixed_jsplit": the
+ * fused split, 0 if the fused kernel did not run.  Options "jsplit", "target_wgs" and "time_kernels" act on the fused kernel as on the
+ * dense route (and on the delegated parts as in covgram_mvm). */
+int covgram_mvm_mixed(covgram_ctx* ctx, const covgram_kernel_composite* k, const covgram_points* X, const covgram_points* Y, const void* a,
+                      int64_t lda, void* y, int64_t ldy, int32_t nrhs, double alpha, double beta, int32_t loc);
+
+/* Matrix(G) of the same composite, the semantics of covgram_matrix: out[i + j * ldo] = k(x_i, y_j), column-major, ldo >= n; only the
+ * rows i < n of each column are written.  ONE kernel for any d with the per-pair arithmetic of the product (the same r^2, p and
+ * interpreter order): lane per row, the columns walked inside the kernel, x_i in registers for d <= 32 and re-read in chunks beyond
+ * (info key "last_mixed_matrix_path": 1 = in registers, 2 = chunked; 0 = none yet, or n m == 0). */
+int covgram_matrix_mixed(covgram_ctx* ctx, const covgram_kernel_composite* k, const covgram_points* X, const covgram_points* Y, void* out,
+                         int64_t ldo, int32_t loc);
 
 /* Hessian-kernel Gramian (n d^2 × m d^2), src/hessian.jl:33-41: block (i,j) is the d^2 × d^2 matrix
  *     T[(a,b),(c,e)] = d^4 k(x_i, y_j) / dx_a dx_b dy_c dy_e,
