@@ -8,8 +8,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "driver.hpp"
-#include "dense_mvm.hpp"
+#include "dense_driver.hpp"
 #include "dense_sym32.hpp"
 #include "dense_bcast.hpp"
 #include "dense_wide.hpp"
@@ -478,36 +477,34 @@ int DenseMvm::run_bcast() {
     void* Pb;
     int rc = ws_reserve(ctx, 0, (size_t)mpad * (D + 2) * ts, &Pb); if (rc) return rc;
     double* Exb = (double*)Pb + (size_t)mpad * D;
-#define CG_BPL(DLV) hipLaunchKernelGGL((dense_bcast_pack_lanes_kernel<DLV>), dim3((unsigned)((mpad * DLV + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)Y->dptr, m, Y->d, \
-                                       (const double*)a, (double*)Pb, Exb, hk.kp.gamma, (const double*)Cn, mpad)
-    if (D == 16) CG_BPL(16); else if (D == 32) CG_BPL(32); else if (D == 64) CG_BPL(64);
-    else
-    hipLaunchKernelGGL(dense_bcast_pack_kernel<double>, dim3((unsigned)((mpad + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)Y->dptr, m, Y->d,
-                       (const double*)a, (double*)Pb, Exb, D, hk.kp.gamma, (const double*)Cn, mpad);
-#undef CG_BPL
+    // D a power of two: D lanes per column record; else a thread per column
+    if (!try_dim(Dims<16, 32, 64>{}, D, [&](auto DL) {
+            hipLaunchKernelGGL((dense_bcast_pack_lanes_kernel<decltype(DL)::value>), dim3((unsigned)((mpad * DL() + 255) / 256)), dim3(256), 0, ctx->stream,
+                               (const double*)Y->dptr, m, Y->d, (const double*)a, (double*)Pb, Exb, hk.kp.gamma, (const double*)Cn, mpad);
+        }))
+        hipLaunchKernelGGL(dense_bcast_pack_kernel<double>, dim3((unsigned)((mpad + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)Y->dptr, m, Y->d,
+                           (const double*)a, (double*)Pb, Exb, D, hk.kp.gamma, (const double*)Cn, mpad);
     DenseArgs da;
     da.C = Cn; da.X = X->dptr; da.n = n; da.d = X->d; da.P = Pb; da.Ex = Exb; da.m = m; da.ldy = ldy; da.nrhs = 1;
     da.Dpad = D; da.NRpad = 1; da.rows_per_lane = 1; da.variant = 0; da.bcast = 1;
     da.alpha = alpha_eff; da.beta = beta; da.hk = &hk; da.stream = ctx->stream;
     ctx->last_dense_path = 1;
-    int64_t jchunk; int jsplit;
     if (dsym) {
         // gramian(k, x): the upper triangle once on dense_bcast_sym_kernel — 64-row blocks, chunks of whole 64-column blocks, the column-sum
         // slab and the reduce kernel of dense_sym_kernel (covgram_mvm_sym_partial's cyclic blocks included)
+        int64_t jchunk; int jsplit;
         choose_split(ctx, rowblocks, m, 64, &jchunk, &jsplit);
-        rc = launch_sym(da, y, jsplit); if (rc) return rc;
+        rc = launch_sym(da, y, jsplit);
     } else {
-        const int64_t rb256 = (n + 255) / 256, npadb = rb256 * 256;
-        choose_split(ctx, rb256, m, 64, &jchunk, &jsplit, (int64_t)ctx->num_cus * 32);
-        da.npad = npadb; da.jchunk = jchunk; da.jsplit = jsplit;
-        if (jsplit == 1) da.out = y;
-        else { rc = ws_reserve(ctx, 1, (size_t)jsplit * npadb * ts, &da.out); if (rc) return rc; }
-        { TimerScope tm(ctx); rc = launch(da, dtype); }
-        if (rc) return rc;
-        if (jsplit > 1)
-            hipLaunchKernelGGL(dense_reduce_kernel<double>, dim3((unsigned)((n + 63) / 64), 1), dim3(256), 0, ctx->stream, (const double*)da.out, npadb, 1, jsplit,
-                               (double*)y, n, ldy, 1, alpha_eff, beta);
+        const int64_t rb256 = (n + 255) / 256;                        // 256-row blocks, about 32 workgroups per CU
+        da.npad = rb256 * 256;
+        rc = dense_lane_route(ctx, dtype, rb256, da.npad, n, m, 1, 1, (int64_t)ctx->num_cus * 32, false, y, ldy, alpha_eff, beta,
+                              [&](int64_t jchunk, int jsplit, void* out, unsigned*) {
+                                  da.jchunk = jchunk; da.jsplit = jsplit; da.out = out;
+                                  return launch(da, dtype);
+                              });
     }
+    if (rc) return rc;
     ctx->last_jsplit = da.jsplit;
     return COVGRAM_OK;
 }
@@ -522,15 +519,7 @@ int DenseMvm::run_lanes() {
         const int NRpad = (nr == 1) ? 1 : 4;
         const char* a_c = (const char*)a + (size_t)c0 * lda * ts;
         char* y_c = (char*)y + (size_t)c0 * ldy * ts;
-        // y <- (sum of the jsplit partial slabs, none for the empty sum) alpha + beta y
-        auto reduce = [&](const void* slab, int jsplit, double alpha_r) {
-            by_dtype(dtype, [&](auto t) {
-                using T = decltype(t);
-                hipLaunchKernelGGL(dense_reduce_kernel<T>, dim3((unsigned)((n + 63) / 64), nr), dim3(256), 0, ctx->stream, (const T*)slab, npad, NRpad, jsplit,
-                                   (T*)y_c, n, ldy, nr, (T)alpha_r, (T)beta);
-            });
-        };
-        if (m == 0) { reduce(nullptr, 0, 0.0); continue; }   // empty sum: y <- beta * y
+        if (m == 0) { dense_reduce(ctx, dtype, nullptr, npad, NRpad, 0, y_c, n, ldy, nr, 0.0, beta); continue; }   // empty sum: y <- beta * y
         void* P;
         const int PADTO = dsym32 ? 8 : PKN;                 // dense_sym32_kernel reduces eight columns at a time
         int64_t mp = ((m + PADTO - 1) / PADTO) * PADTO;     // stream padded to whole column groups
@@ -549,32 +538,31 @@ int DenseMvm::run_lanes() {
                 hipLaunchKernelGGL(dense_pack_kernel<T>, dim3((unsigned)((mp + 255) / 256)), dim3(256), 0, ctx->stream, (const T*)Y->dptr, m, Y->d, (const T*)a_c,
                                    lda, nr, 0, (T*)P, D, NRpad, PKN, (T)hk.kp.gamma, (const T*)Cn, PADTO);
         });
-        int64_t jchunk; int jsplit;
-        // chunks are multiples of 64 columns (whole packed pairs); small problems split finer than the 512-column
-        // inner accumulation block so that they still expose thousands of waves
-        choose_split(ctx, rowblocks, m, 64, &jchunk, &jsplit);
-        ctx->last_jsplit = jsplit;
         DenseArgs da;
         da.C = Cn;
         da.X = X->dptr; da.n = n; da.d = X->d; da.P = P; da.m = m; da.npad = npad; da.ldy = ldy; da.nrhs = nr;
-        da.Dpad = D; da.NRpad = NRpad; da.jchunk = jchunk; da.jsplit = jsplit; da.rows_per_lane = rows_per_lane_for(D);
+        da.Dpad = D; da.NRpad = NRpad; da.rows_per_lane = rows_per_lane_for(D);
         da.variant = (int)ctx->dense_variant; da.alpha = alpha_eff; da.beta = beta; da.hk = &hk; da.stream = ctx->stream;
         if (dsym) {
+            int64_t jchunk; int jsplit;
+            choose_split(ctx, rowblocks, m, 64, &jchunk, &jsplit);
             rc = launch_sym(da, y_c, jsplit); if (rc) return rc;
-            if (dsym32) ctx->last_jsplit = da.jsplit;       // (the fp64 kernel reports the all-entries split it started from)
+            ctx->last_jsplit = dsym32 ? da.jsplit : jsplit;   // (the fp64 kernel reports the all-entries split it started from)
             continue;
         }
-        if (jsplit == 1) da.out = y_c;
-        else { rc = ws_reserve(ctx, 1, (size_t)jsplit * NRpad * npad * ts, &da.out); if (rc) return rc; }
-        // the lane-per-row kernel can sum its own split-J slab (last-arriving workgroup of each 64-row block, fixed order: pack.hpp) — only
+        // chunks are multiples of 64 columns (whole packed pairs); small problems split finer than the 512-column
+        // inner accumulation block so that they still expose thousands of waves.
+        // The lane-per-row kernel can sum its own split-J slab (last-arriving workgroup of each 64-row block, fixed order: pack.hpp) — only
         // on request: its column splits are fine (64 at C1's size), and 64 tickets on one counter plus the uncached re-read cost more than
         // the launch they save (profiles/r04_inkernel_reduce_ab.txt: C1 27.1 -> 39.0 us, n = 16384 259 -> 262)
-        const bool ikr = !wide && inkernel_reduce_on(ctx, false, n, jsplit);
-        ctx->last_inkernel_reduce = ikr ? 1 : 0;
-        if (ikr) { rc = tickets_reserve(ctx, (size_t)rowblocks, &da.tickets); if (rc) return rc; da.yfinal = y_c; }
-        { TimerScope tm(ctx); rc = launch(da, dtype); }
+        rc = dense_lane_route(ctx, dtype, rowblocks, npad, n, m, nr, NRpad, 0, !wide, y_c, ldy, alpha_eff, beta,
+                              [&](int64_t jchunk, int jsplit, void* out, unsigned* tickets) {
+                                  ctx->last_jsplit = jsplit;
+                                  ctx->last_inkernel_reduce = tickets ? 1 : 0;
+                                  da.jchunk = jchunk; da.jsplit = jsplit; da.out = out; da.tickets = tickets; da.yfinal = tickets ? y_c : nullptr;
+                                  return launch(da, dtype);
+                              });
         if (rc) return rc;
-        if (jsplit > 1 && !ikr) reduce(da.out, jsplit, alpha_eff);
     }
     return COVGRAM_OK;
 }

@@ -18,7 +18,7 @@
 // (scalar) loads (and y_j[a], y_j[b] of its own rows through per-lane loads), evaluates r, s and the jet ONCE per (i, j) and then emits the B columns of that block column.  r is a direct difference
 // (x - y) gamma; the entries do not depend on VR, ldo or the alignment of out.  No LDS, no atomics, no scratch.
 #pragma once
-#include "common.hpp"
+#include "dispatch.hpp"
 #include "profiles.hpp"
 #include "hess_mvm.hpp"   // COVGRAM_HESS_FAMILIES: the families of the Hessian kinds
 #include <type_traits>
@@ -266,15 +266,8 @@ inline int launch_bm_one(const BlockMatArgs& a) {
 
 template <int FAM, typename T, bool HO>
 inline int launch_bm_typed(const BlockMatArgs& a) {
-    switch (a.Dpad) {
-        case 4: return launch_bm_one<FAM, T, 4, HO>(a);
-        case 8: return launch_bm_one<FAM, T, 8, HO>(a);
-        case 16: return launch_bm_one<FAM, T, 16, HO>(a);
-        case 32: return launch_bm_one<FAM, T, 32, HO>(a);
-        case 64:
-            if constexpr (!HO) return launch_bm_one<FAM, T, 64, HO>(a);
-        default: set_error("block matrix: no kernel for padded d = %d", a.Dpad); return COVGRAM_EUNSUPPORTED;
-    }
+    using Buckets = std::conditional_t<HO, Dims<4, 8, 16, 32>, Dims<4, 8, 16, 32, 64>>;
+    return by_dim(Buckets{}, a.Dpad, "block matrix: no kernel for padded d = %d", [&](auto D) { return launch_bm_one<FAM, T, decltype(D)::value, HO>(a); });
 }
 
 template <int FAM, bool HO>

@@ -50,7 +50,7 @@
 //                      column sums ("Symmetric Gramian" below), also rank r of P's share for the multi-GPU form; the launchers, one argument list per kernel family
 //   mfma_plan.hpp      the column split and the symmetric work list as plain arithmetic (no HIP; tests/mfma_plan_check.cpp)
 // Sections: the points handle's radii (device code: their reduction kernel) | the rules, each written once | shared steps | the three drivers.
-#include "driver.hpp"
+#include "dense_driver.hpp"
 #include "mfma_plan.hpp"
 #include "dense_mfma_eq.hpp"
 
@@ -378,8 +378,7 @@ static int split_out(covgram_ctx* ctx, const ColumnPlan& pl, int nrpad, float* y
 // y[:, 0..nr) <- alpha (the js slab rows added in fixed order) + beta y
 static void reduce_split(covgram_ctx* ctx, const float* slab, const ColumnPlan& pl, int nrpad, float* y, int64_t n, int64_t ldy, int nr, double alpha,
                          double beta) {
-    hipLaunchKernelGGL(dense_reduce_kernel<float>, dim3((unsigned)((n + 63) / 64), nr), dim3(256), 0, ctx->stream, slab, pl.npad, nrpad, (int)pl.js, y, n,
-                       ldy, nr, (float)alpha, (float)beta);
+    dense_reduce(ctx, slab, pl.npad, nrpad, (int)pl.js, y, n, ldy, nr, alpha, beta);
 }
 
 // the generic kernels' column fragments (norm pseudo-coordinate) and the weights of `nr` right-hand sides in NR slots per tile, packed per MVM into

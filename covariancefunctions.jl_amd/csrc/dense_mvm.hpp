@@ -20,6 +20,7 @@
 //   * accumulation is two-level (512-column inner chunks, then per-split partials) so the fp32 error
 //     against the fp64 oracle stays ~3e-7 at m = 2^17 (a sequential fp32 sum drifts to ~6e-6).
 #pragma once
+#include "dispatch.hpp"
 #include "profiles.hpp"
 
 namespace covgram {
@@ -579,21 +580,8 @@ static int launch_dense_D(const DenseArgs& a) {
 
 template <typename T, int FAM, int NR>
 static int launch_dense_NR(const DenseArgs& a) {
-    switch (a.Dpad) {
-        case 1: return launch_dense_D<T, FAM, 1, NR>(a);
-        case 2: return launch_dense_D<T, FAM, 2, NR>(a);
-        case 3: return launch_dense_D<T, FAM, 3, NR>(a);
-        case 4: return launch_dense_D<T, FAM, 4, NR>(a);
-        case 6: return launch_dense_D<T, FAM, 6, NR>(a);
-        case 8: return launch_dense_D<T, FAM, 8, NR>(a);
-        case 12: return launch_dense_D<T, FAM, 12, NR>(a);
-        case 16: return launch_dense_D<T, FAM, 16, NR>(a);
-        case 24: return launch_dense_D<T, FAM, 24, NR>(a);
-        case 32: return launch_dense_D<T, FAM, 32, NR>(a);
-        case 48: return launch_dense_D<T, FAM, 48, NR>(a);
-        case 64: return launch_dense_D<T, FAM, 64, NR>(a);
-        default: set_error("dense_mvm: padded dimension %d not compiled", a.Dpad); return COVGRAM_EUNSUPPORTED;
-    }
+    return by_dim(Dims<1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64>{}, a.Dpad, "dense_mvm: padded dimension %d not compiled",
+                  [&](auto D) { return launch_dense_D<T, FAM, decltype(D)::value, NR>(a); });
 }
 
 template <int FAM>

@@ -2,27 +2,11 @@
 // Sum split.  Served units: the point-pair entries (api.hip, matrix.hip, mixed_mvm.hip, block_mvm.hip, grad_mixed.hip — these two through grad_driver.hpp —,
 // sm.hip, sparse.hip, bilin_grad.hip, input_grad.hip, dense_mfma.hip, pivchol.hip), kernel_params.hip (the family names of its refusals) and the
 // structured operators (toeplitz.hip, toeplitz_direct.hip, kron.hip, lowrank.hip, barneshut.hip).  Host code only; the per-family kernel units
-// include common.hpp, not this.
+// include common.hpp and dispatch.hpp (by_dtype, by_bool, by_dim), not this.
 #pragma once
-#include <type_traits>
-
-#include "common.hpp"
+#include "dispatch.hpp"
 
 namespace covgram {
-
-// f(float{}) or f(double{}): ONE generic lambda for both element types of a launch
-template <typename F>
-inline decltype(auto) by_dtype(int dtype, F&& f) {
-    if (dtype == COVGRAM_F32) return f(float{});
-    return f(double{});
-}
-
-// f(std::true_type{}) or f(std::false_type{}): the same for a flag that is a template argument of the launch
-template <typename F>
-inline decltype(auto) by_bool(bool b, F&& f) {
-    if (b) return f(std::true_type{});
-    return f(std::false_type{});
-}
 
 // HIP-event bracket around the dominant kernel of a product (option "time_kernels"): the first event is recorded here, the second on EVERY way
 // out of the scope — a refused launch too, so that covgram_ctx_kernel_time never meets a counted pair whose second event was not recorded

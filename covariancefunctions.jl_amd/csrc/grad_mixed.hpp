@@ -243,19 +243,8 @@ static int launch_grad_mixed_one(const GradMixedArgs& a) {
 
 template <typename T>
 static int launch_grad_mixed_T(const GradMixedArgs& a) {
-    switch (a.Dpad) {
-        case 1: return launch_grad_mixed_one<T, 1>(a);
-        case 2: return launch_grad_mixed_one<T, 2>(a);
-        case 3: return launch_grad_mixed_one<T, 3>(a);
-        case 4: return launch_grad_mixed_one<T, 4>(a);
-        case 6: return launch_grad_mixed_one<T, 6>(a);
-        case 8: return launch_grad_mixed_one<T, 8>(a);
-        case 12: return launch_grad_mixed_one<T, 12>(a);
-        case 16: return launch_grad_mixed_one<T, 16>(a);
-        case 24: return launch_grad_mixed_one<T, 24>(a);
-        case 32: return launch_grad_mixed_one<T, 32>(a);
-        default: set_error("grad_mixed: padded dimension %d not compiled for the lane-per-row route", a.Dpad); return COVGRAM_EUNSUPPORTED;
-    }
+    return by_dim(Dims<1, 2, 3, 4, 6, 8, 12, 16, 24, 32>{}, a.Dpad, "grad_mixed: padded dimension %d not compiled for the lane-per-row route",
+                  [&](auto D) { return launch_grad_mixed_one<T, decltype(D)::value>(a); });
 }
 
 // ---- panel route ------------------------------------------------------------------------------------------------------------------------

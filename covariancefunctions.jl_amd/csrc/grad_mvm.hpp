@@ -34,6 +34,7 @@
 // across both sweeps of a column and across columns (the last chunk of column j prefetches the first of j+1; the
 // stream is padded by one record so the final prefetch stays in bounds).
 #pragma once
+#include "dispatch.hpp"
 #include "profiles.hpp"
 
 namespace covgram {
@@ -555,22 +556,8 @@ static int launch_grad_T(const GradArgs& a) {
         set_error("grad_mvm: padded dimension %d exceeds the lane-per-row limit %d for this dtype", a.Dpad, MAXD);
         return COVGRAM_EUNSUPPORTED;
     }
-    switch (a.Dpad) {
-        case 1: return launch_grad_one<T, FAM, 1>(a);
-        case 2: return launch_grad_one<T, FAM, 2>(a);
-        case 3: return launch_grad_one<T, FAM, 3>(a);
-        case 4: return launch_grad_one<T, FAM, 4>(a);
-        case 6: return launch_grad_one<T, FAM, 6>(a);
-        case 8: return launch_grad_one<T, FAM, 8>(a);
-        case 12: return launch_grad_one<T, FAM, 12>(a);
-        case 16: return launch_grad_one<T, FAM, 16>(a);
-        case 24: return launch_grad_one<T, FAM, 24>(a);
-        case 32: return launch_grad_one<T, FAM, 32>(a);
-        case 48: return launch_grad_one<T, FAM, 48>(a);
-        case 64:
-            if constexpr (sizeof(T) == 4) return launch_grad_one<T, FAM, 64>(a);
-        default: set_error("grad_mvm: padded dimension %d not compiled", a.Dpad); return COVGRAM_EUNSUPPORTED;
-    }
+    using Buckets = std::conditional_t<sizeof(T) == 4, Dims<1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64>, Dims<1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48>>;
+    return by_dim(Buckets{}, a.Dpad, "grad_mvm: padded dimension %d not compiled", [&](auto D) { return launch_grad_one<T, FAM, decltype(D)::value>(a); });
 }
 
 template <int FAM>

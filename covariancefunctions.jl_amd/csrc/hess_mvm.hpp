@@ -40,7 +40,7 @@
 // the pack kernel scales a_g by gamma and A by gamma^2, the epilogue b_g by gamma and B by gamma^2 (the constant factor of the kernel
 // goes into alpha on the host).
 #pragma once
-#include "common.hpp"
+#include "dispatch.hpp"
 #include "profiles.hpp"
 
 namespace covgram {
@@ -318,17 +318,8 @@ inline int launch_hess_one(const HessArgs& a) {
 
 template <int FAM, typename T, bool VGH>
 inline int launch_hess_typed(const HessArgs& a) {
-    switch (a.Dpad) {
-        case 1: return launch_hess_one<FAM, T, 1, VGH>(a);
-        case 2: return launch_hess_one<FAM, T, 2, VGH>(a);
-        case 4: return launch_hess_one<FAM, T, 4, VGH>(a);
-        case 8: return launch_hess_one<FAM, T, 8, VGH>(a);
-        case 16: return launch_hess_one<FAM, T, 16, VGH>(a);
-        case 32: return launch_hess_one<FAM, T, 32, VGH>(a);
-        default:
-            set_error(VGH ? "value-gradient-Hessian MVM: no kernel for padded d = %d" : "Hessian MVM: no kernel for padded d = %d", a.Dpad);
-            return COVGRAM_EUNSUPPORTED;
-    }
+    return by_dim(Dims<1, 2, 4, 8, 16, 32>{}, a.Dpad, VGH ? "value-gradient-Hessian MVM: no kernel for padded d = %d" : "Hessian MVM: no kernel for padded d = %d",
+                  [&](auto D) { return launch_hess_one<FAM, T, decltype(D)::value, VGH>(a); });
 }
 
 template <int FAM, bool VGH>

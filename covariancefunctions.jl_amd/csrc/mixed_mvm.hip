@@ -1,18 +1,21 @@
 // mixed_mvm.hip — covgram_mvm_mixed and covgram_matrix_mixed: the scalar Gramian of a composite whose factors carry their own input traits
 // (mixed_mvm.hpp).  The product's driver sends the plain terms of the composite — one trait, no NeuralNetwork factor — to the kernels behind
 // covgram_mvm (dense_mvm_on_device: matrix cores, factored dot product, the Sum split) and runs the rest in the fused kernel, on the
-// lane-per-row route (padded d <= 32) or the chunked route.
+// lane-per-row route (padded d <= 32) or the chunked route.  The column split, the partial slabs and the reduction of the fused kernel are
+// dense_lane_route / dense_reduce (dense_driver.hpp), as covgram_mvm's lane-per-row kernels use them.
 #include <math.h>
 
 #include <algorithm>
 
-#include "driver.hpp"
-#include "dense_mvm.hpp"
+#include "dense_driver.hpp"
 #include "mixed_mvm.hpp"
 
 using namespace covgram;
 
 namespace {
+
+// the padded dimension of the kernels that hold a row in registers (d <= 32); 0: the chunked kernels
+static int mixv_bucket(int d) { return d <= 4 ? 4 : (d <= 8 ? 8 : (d <= 16 ? 16 : (d <= 32 ? 32 : 0))); }
 
 // ---- the partition of the composite's terms ---------------------------------------------------------------------------------------------
 enum MixedPart { PART_ISO = 0, PART_DOT = 1, PART_FUSED = 2, PART_CONST = 3 };
@@ -113,50 +116,7 @@ static int mixed_partition(const covgram_ctx* ctx, const covgram_kernel_composit
     return COVGRAM_OK;
 }
 
-// ---- the fused kernel on device-resident a and y that do not overlap ---------------------------------------------------------------------
-struct MixedLaunch {
-    const void* X; int64_t n; int32_t d; int32_t D; int32_t nch;
-    const void* P; int64_t mpad;
-    void* out; int64_t npad, ldy; int32_t nr; int64_t jchunk; int32_t jsplit;
-    double alpha, beta;
-    const HostKernel* hk;
-    hipStream_t stream;
-};
-
-template <typename T, int NR>
-static int launch_mixed(const MixedLaunch& a) {
-    using V = typename Pk<T>::V;
-    const ExprParams<T> ep = make_params<FAM_EXPR_DOT, T>(*a.hk);
-    const dim3 grid((unsigned)(a.npad / MIXV_THREADS), (unsigned)a.jsplit);
-    const int fs = a.jsplit == 1 ? 1 : 0;
-#define CG_MIXV_LANE(DV)                                                                                                                          \
-    hipLaunchKernelGGL((mixed_lane_kernel<T, DV, NR>), grid, dim3(MIXV_THREADS), 0, a.stream, (const T*)a.X, a.n, a.d, (const V*)a.P, a.mpad, (T*)a.out, \
-                       a.npad, a.ldy, a.nr, a.jchunk, (T)a.alpha, (T)a.beta, fs, ep)
-    switch (a.D) {
-        case 4: CG_MIXV_LANE(4); break;
-        case 8: CG_MIXV_LANE(8); break;
-        case 16: CG_MIXV_LANE(16); break;
-        case 32: CG_MIXV_LANE(32); break;
-        default:
-            hipLaunchKernelGGL((mixed_chunk_kernel<T, NR>), grid, dim3(MIXV_THREADS), 0, a.stream, (const T*)a.X, a.n, a.d, a.nch, (const V*)a.P, a.mpad,
-                               (T*)a.out, a.npad, a.ldy, a.nr, a.jchunk, (T)a.alpha, (T)a.beta, fs, ep);
-    }
-#undef CG_MIXV_LANE
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("mixed_mvm launch failed: %s", hipGetErrorString(e)); return COVGRAM_EHIP; }
-    return COVGRAM_OK;
-}
-
-// y <- (sum of the jsplit slabs, none for the empty sum) alpha + beta y over nr right-hand sides
-static void mixed_reduce(covgram_ctx* ctx, int dtype, const void* slab, int64_t npad, int NRpad, int jsplit, void* y, int64_t n, int64_t ldy, int nr, double alpha,
-                         double beta) {
-    by_dtype(dtype, [&](auto t) {
-        using T = decltype(t);
-        hipLaunchKernelGGL(dense_reduce_kernel<T>, dim3((unsigned)((n + 63) / 64), (unsigned)nr), dim3(256), 0, ctx->stream, (const T*)slab, npad, NRpad, jsplit,
-                           (T*)y, n, ldy, nr, (T)alpha, (T)beta);
-    });
-}
-
+// ---- the fused kernel on device-resident a and y that do not overlap: the route of dense_driver.hpp over its own column stream ----------------
 static int mixed_fused_device(covgram_ctx* ctx, const HostKernel& hk, const covgram_points* X, const covgram_points* Y, const void* a, int64_t lda, void* y,
                               int64_t ldy, int32_t nrhs, double alpha, double beta) {
     const int64_t n = X->n, m = Y->n;
@@ -164,7 +124,7 @@ static int mixed_fused_device(covgram_ctx* ctx, const HostKernel& hk, const covg
     const int dtype = X->dtype;
     const size_t ts = dtype_size(dtype);
     const int PKN = dtype == COVGRAM_F32 ? 2 : 1;
-    const int D = d <= 4 ? 4 : (d <= 8 ? 8 : (d <= 16 ? 16 : (d <= 32 ? 32 : 0)));   // the lane-per-row buckets; 0: chunked
+    const int D = mixv_bucket(d);
     const int nch = (d + MIXV_CH - 1) / MIXV_CH;
     const int64_t mpad = ((m + MIXV_CB - 1) / MIXV_CB) * MIXV_CB;                      // whole interpreter blocks on either route
     const int64_t rowblocks = (n + MIXV_THREADS - 1) / MIXV_THREADS, npad = rowblocks * MIXV_THREADS;
@@ -183,21 +143,30 @@ static int mixed_fused_device(covgram_ctx* ctx, const HostKernel& hk, const covg
             if (D) hipLaunchKernelGGL(mixed_pack_kernel<T>, pg, dim3(256), 0, ctx->stream, (const T*)Y->dptr, m, d, (const T*)a_c, lda, nr, (T*)P, D, nr, PKN, mpad);
             else hipLaunchKernelGGL(mixed_chunk_pack_kernel<T>, pg, dim3(256), 0, ctx->stream, (const T*)Y->dptr, m, d, nch, (const T*)a_c, lda, nr, (T*)P, nr, PKN, mpad);
         });
-        int64_t jchunk; int jsplit;
-        choose_split(ctx, rowblocks, m, 64, &jchunk, &jsplit);    // chunks of whole 64-column blocks, as the dense route
-        ctx->last_mixed_jsplit = jsplit;
-        ctx->last_mixed_path |= (D ? 1 : 2) | (jsplit > 1 ? 16 : 0);
-        MixedLaunch ml;
-        ml.X = X->dptr; ml.n = n; ml.d = d; ml.D = D; ml.nch = nch; ml.P = P; ml.mpad = mpad; ml.npad = npad; ml.ldy = ldy; ml.nr = nr;
-        ml.jchunk = jchunk; ml.jsplit = jsplit; ml.alpha = alpha_eff; ml.beta = beta; ml.hk = &hk; ml.stream = ctx->stream;
-        ml.out = y_c;
-        if (jsplit > 1) { rc = ws_reserve(ctx, 1, (size_t)jsplit * nr * npad * ts, &ml.out); if (rc) return rc; }
-        {
-            TimerScope tm(ctx);
-            rc = by_dtype(dtype, [&](auto t) { return nr == 4 ? launch_mixed<decltype(t), 4>(ml) : launch_mixed<decltype(t), 1>(ml); });
-        }
+        rc = dense_lane_route(ctx, dtype, rowblocks, npad, n, m, nr, nr, 0, false, y_c, ldy, alpha_eff, beta, [&](int64_t jchunk, int jsplit, void* out, unsigned*) {
+            ctx->last_mixed_jsplit = jsplit;
+            ctx->last_mixed_path |= (D ? 1 : 2) | (jsplit > 1 ? 16 : 0);
+            const dim3 grid((unsigned)rowblocks, (unsigned)jsplit);
+            const int fs = jsplit == 1 ? 1 : 0;
+            by_dtype(dtype, [&](auto t) {
+                by_bool(nr == 4, [&](auto four) {
+                    using T = decltype(t);
+                    using V = typename Pk<T>::V;
+                    constexpr int NR = decltype(four)::value ? 4 : 1;
+                    const ExprParams<T> ep = make_params<FAM_EXPR_DOT, T>(hk);
+                    if (!try_dim(Dims<4, 8, 16, 32>{}, D, [&](auto DV) {
+                            hipLaunchKernelGGL((mixed_lane_kernel<T, decltype(DV)::value, NR>), grid, dim3(MIXV_THREADS), 0, ctx->stream, (const T*)X->dptr, n, d,
+                                               (const V*)P, mpad, (T*)out, npad, ldy, nr, jchunk, (T)alpha_eff, (T)beta, fs, ep);
+                        }))
+                        hipLaunchKernelGGL((mixed_chunk_kernel<T, NR>), grid, dim3(MIXV_THREADS), 0, ctx->stream, (const T*)X->dptr, n, d, nch, (const V*)P, mpad,
+                                           (T*)out, npad, ldy, nr, jchunk, (T)alpha_eff, (T)beta, fs, ep);
+                });
+            });
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) { set_error("mixed_mvm launch failed: %s", hipGetErrorString(e)); return (int)COVGRAM_EHIP; }
+            return (int)COVGRAM_OK;
+        });
         if (rc) return rc;
-        if (jsplit > 1) mixed_reduce(ctx, dtype, ml.out, npad, nr, jsplit, y_c, n, ldy, nr, alpha_eff, beta);
         c0 += nr;
     }
     return COVGRAM_OK;
@@ -209,7 +178,7 @@ static int mixed_device(covgram_ctx* ctx, const MixedPlan& plan, const covgram_p
     const int64_t n = X->n, m = Y->n;
     const int dtype = X->dtype;
     if (m == 0) {                                                // no columns: y <- beta y
-        mixed_reduce(ctx, dtype, nullptr, n, 1, 0, y, n, ldy, nrhs, 0.0, beta);
+        dense_reduce(ctx, dtype, nullptr, n, 1, 0, y, n, ldy, nrhs, 0.0, beta);
         return COVGRAM_OK;
     }
     int rc;
@@ -226,7 +195,7 @@ static int mixed_device(covgram_ctx* ctx, const MixedPlan& plan, const covgram_p
     if (plan.fused) {
         rc = mixed_fused_device(ctx, plan.fused_hk, X, Y, a, lda, y, ldy, nrhs, alpha, part_beta()); if (rc) return rc;
     }
-    if (first) mixed_reduce(ctx, dtype, nullptr, n, 1, 0, y, n, ldy, nrhs, 0.0, beta);   // constant terms only
+    if (first) dense_reduce(ctx, dtype, nullptr, n, 1, 0, y, n, ldy, nrhs, 0.0, beta);   // constant terms only
     if (plan.constant != 0.0) {
         rc = constant_term_mvm(ctx, dtype, a, m, lda, 1, y, n, ldy, 1, nrhs, alpha * plan.constant); if (rc) return rc;
         ctx->last_mixed_path |= 32;
@@ -283,11 +252,11 @@ int covgram_matrix_mixed(covgram_ctx* ctx, const covgram_kernel_composite* k, co
         using T = decltype(t);
         const ExprParams<T> ep = make_params<FAM_EXPR_DOT, T>(hk);
         TimerScope tm(ctx);
-#define CG_MIXV_MAT(DV)                                                                                                                             \
-        hipLaunchKernelGGL((mixed_matrix_kernel<T, DV>), grid, dim3(256), 0, ctx->stream, (const T*)X->dptr, n, (const T*)Y->dptr, m, d, (T*)st.y, st.ldy, \
-                           (T)hk.kp.scale, ep)
-        if (d <= 4) CG_MIXV_MAT(4); else if (d <= 8) CG_MIXV_MAT(8); else if (d <= 16) CG_MIXV_MAT(16); else if (d <= 32) CG_MIXV_MAT(32); else CG_MIXV_MAT(0);
-#undef CG_MIXV_MAT
+        // (the bucket is one of the list: nothing to refuse)
+        try_dim(Dims<0, 4, 8, 16, 32>{}, mixv_bucket(d), [&](auto D) {
+            hipLaunchKernelGGL((mixed_matrix_kernel<T, decltype(D)::value>), grid, dim3(256), 0, ctx->stream, (const T*)X->dptr, n, (const T*)Y->dptr, m, d,
+                               (T*)st.y, st.ldy, (T)hk.kp.scale, ep);
+        });
     });
     CG_CHECK_HIP(hipGetLastError());
     return st.finish();

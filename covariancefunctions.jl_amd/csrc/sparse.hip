@@ -334,12 +334,8 @@ static void launch_sparse_mvm(const covgram_sparse* S, const void* a, int64_t ld
 template <typename T>
 static void launch_sparse_mvm_t(const covgram_sparse* S, const void* a, int64_t lda, void* y, int64_t ldy, int nrhs, double alpha, double beta,
                                 hipStream_t stream) {
-    switch (S->group) {
-        case 1: launch_sparse_mvm<T, 1>(S, a, lda, y, ldy, nrhs, alpha, beta, stream); break;
-        case 4: launch_sparse_mvm<T, 4>(S, a, lda, y, ldy, nrhs, alpha, beta, stream); break;
-        case 16: launch_sparse_mvm<T, 16>(S, a, lda, y, ldy, nrhs, alpha, beta, stream); break;
-        default: launch_sparse_mvm<T, 64>(S, a, lda, y, ldy, nrhs, alpha, beta, stream); break;
-    }
+    auto launch = [&](auto G) { launch_sparse_mvm<T, decltype(G)::value>(S, a, lda, y, ldy, nrhs, alpha, beta, stream); };
+    if (!try_dim(Dims<1, 4, 16>{}, S->group, launch)) launch(std::integral_constant<int, 64>{});
 }
 
 template <typename T, bool FILL>
