@@ -19,12 +19,13 @@ from .kernels import (AbstractKernel, MercerKernel, StationaryKernel, IsotropicK
                       GenericInput, IsotropicInput, DotProductInput, StationaryInput, StationaryLinearFunctionalInput,
                       PeriodicInput, input_trait, register_input_trait, ismercer, isstationary, isisotropic, isdot,
                       device_spec, Spectral, SpectralMixture, SM, spectral_mixture_spec, require_sm_spec, require_hessian_spec, require_vgh_spec, require_pivchol_spec, DomainError,
-                      hyperparameters, with_hyperparameters, spectral_mixture_chain_rules, mixed_gradient_spec, require_mixed_gradient_spec, mixed_spec, require_mixed_spec)
+                      hyperparameters, with_hyperparameters, spectral_mixture_chain_rules, mixed_gradient_spec, require_mixed_gradient_spec, mixed_spec, require_mixed_spec,
+                      mixed_parameter_spec, require_mixed_parameter_spec)
 from .gramian import (Gramian, MixedGramian, BlockGramian, MixedBlockGramian, HessianGramian, ValueGradientHessianGramian, SymmetricToeplitz, Toeplitz, Circulant, KroneckerProduct, kronecker,
                       SeparableGramian, LazyMatrixProduct, LazyMatrixSum, ScaledOperator, LinearMapBlockGramian, CosineBlockGramian, PointJacobianBlockGramian, Fill, LazyOperator, LazyGrid, StepRangeLen,
                       srange, gramian, mul_, get_ctx, set_option, get_info, kernel_time, SparseGramian, sparse, decay_radius,
                       BarnesHutFactorization, require_barneshut_spec, SpectralMixtureGramian, bilinear_gradient, bilinear_chain_rules,
-                      bilinear_input_gradient, spectral_mixture_gradient, spectral_mixture_input_gradient)
+                      bilinear_input_gradient, mixed_bilinear_gradient, spectral_mixture_gradient, spectral_mixture_input_gradient)
 from .dist import ShardedGramian, shard_bounds
 from .solve import (cg, mbcg, cg_tridiagonals, lanczos_quadrature, logdet, inv_quad_logdet, inv_quad_logdet_gradient, minres, solve, toeplitz_solve, durbin, levinson,
                     trench)

@@ -26,6 +26,7 @@ MATERNP_MAX_P = 8
 PIVCHOL_MAX_RANK = 1024   # COVGRAM_PIVCHOL_MAX_RANK
 SM_MAX_COMPONENTS, SM_MAX_D = 32, 16   # COVGRAM_SM_MAX_COMPONENTS, COVGRAM_SM_MAX_D
 BILINEAR_MAX_NVEC, BILINEAR_MAX_D = 32, 64   # limits of covgram_bilinear_grad
+MIXED_GRAD_NOUT = 24                         # COVGRAM_MIXED_GRAD_NOUT: the doubles covgram_bilinear_grad_mixed writes
 COMM_ID_BYTES = 128
 BCG_SLAB, BCG_FIELDS = 64, 8   # COVGRAM_BCG_SLAB, COVGRAM_BCG_FIELDS
 BCG_RZ, BCG_TOL2, BCG_RR, BCG_ACTIVE, BCG_ITERS = range(5)   # COVGRAM_BCG_*: the fields of the batched CG state
@@ -162,6 +163,7 @@ PROTOTYPES = {
     "covgram_sm_destroy": (C.c_int, [_P]),
     "covgram_bilinear_grad_sm": (C.c_int, [_P, _P, _P, _P, _I64, _P, _I64, _I32, C.POINTER(_D), _I32]),
     "covgram_bilinear_input_grad_sm": (C.c_int, [_P, _P, _P, _P, _I64, _P, _I64, _I32, C.POINTER(_D), _I32]),
+    "covgram_bilinear_grad_mixed": (C.c_int, [_P, C.POINTER(covgram_kernel_composite), _P, _P, _P, _I64, _P, _I64, _I32, C.POINTER(_D), _I32]),
     "covgram_bilinear_grad": (C.c_int, [_P, _KP, _P, _P, _P, _I64, _P, _I64, _I32, _I32, C.POINTER(_D), _I32]),
     "covgram_bilinear_input_grad": (C.c_int, [_P, _KP, _P, _P, _P, _I64, _P, _I64, _I32, C.POINTER(_D), _I32]),
     "covgram_debug_kernel_params": (C.c_int, [_KP, _I32, _I32, C.POINTER(_D)]),

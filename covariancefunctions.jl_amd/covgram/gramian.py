@@ -693,8 +693,9 @@ class MixedGramian(_PointPairGramian):
     MaternP(2) + Dot()**2 + NeuralNetwork(): GenericInput in the reference's terms, its threaded loop src/gramian.jl:78-87.  `mul!` is
     covgram_mvm_mixed (plain terms on the kernels behind covgram_mvm, the rest in one fused pass), Matrix(G) and indexing are
     covgram_matrix_mixed.  `gramian` builds it for exactly the kernels that have neither a covgram_kernel encoding nor a
-    spectral-mixture one and that kernels.mixed_spec lowers.  Hyper-parameter / input gradients, sparse, Barnes-Hut, pivoted Cholesky and
-    sharded forms do not exist: they raise UnsupportedKernel naming this class."""
+    spectral-mixture one and that kernels.mixed_spec lowers.  Hyper-parameter gradients of its bilinear forms are mixed_bilinear_gradient
+    (bilinear_gradient refuses it).  Input gradients, sparse, Barnes-Hut, pivoted Cholesky and sharded forms do not exist: they raise
+    UnsupportedKernel naming this class."""
 
     def __init__(self, k, x, y=None, spec=None):
         self._spec = spec if spec is not None else K.require_mixed_spec(k)   # refusals come before any device call
@@ -721,6 +722,51 @@ class MixedGramian(_PointPairGramian):
 
     def sym_partial_(self, y, a, rank: int, world: int):
         raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, "sym_partial_: MixedGramian has no symmetric (upper-triangle) partial form")
+
+
+def mixed_bilinear_gradient(G, U, A, _spec=None):
+    """(value, grad) of the bilinear form Σ_t U[:, t]ᵀ G A[:, t] = Σ_ij W_ij k(x_i, y_j), W = U Aᵀ, with respect to EVERY hyper-parameter of
+    a Sum / Product / Power whose factors carry their own input traits, in ONE fused pass over the pairs (csrc/mixed_bilin_grad.hip,
+    covgram_bilinear_grad_mixed): W is formed per pair in registers, nothing of size n × m exists.  `G` is the MixedGramian of
+    gramian(k, x[, y]) — EQ() + Dot(), EQ() * (Dot()**2 + 1), MaternP(2) + Dot()**2 + NeuralNetwork() — or a plain Gramian without
+    ARD / ScaledInputKernel in front, which covers what bilinear_gradient leaves out: Products of two non-constant same-trait kernels and
+    dot-product kernels such as Polynomial(3, σ).  U is (n,) or (n, nvec), A (m,) or (m, nvec).  `value` is a float64 0-dim CPU tensor,
+    `grad` a float64 CPU tensor in hyperparameters(G.k) order.  The device returns 24 numbers (include/covgram.h); the chain rules to the
+    leaves of the kernel tree are the matrix J of kernels.require_mixed_parameter_spec: grad = J @ out, value = Σ_t c_t out[t].  More
+    than 32 columns run in chunks of 32 summed in fp64.  Everything else — spectral mixtures, block, structured, sparse and sharded
+    operators, a Gramian behind ARD / ScaledInputKernel, and every kernel the lowering refuses (Matern with real ν, Cosine, more than
+    8 terms or factors) — raises UnsupportedKernel by name before any device call."""
+    fn = "mixed_bilinear_gradient"
+    if type(G) is not MixedGramian and type(G) is not Gramian:
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"{fn}: {type(G).__name__} is not supported (the MixedGramian or Gramian of gramian(k, x[, y]) only)")
+    if getattr(G, "scaled_input", None) is not None:
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"{fn}: a Gramian behind {type(G.scaled_input).__name__} (ARD) is not supported")
+    comp, J = _spec if _spec is not None else K.require_mixed_parameter_spec(G.k)
+    n, m = G.shape
+    d = G.x.shape[1]
+    if d > BILINEAR_MAX_D:
+        raise _ffi.DimensionMismatch(_ffi.EINVAL, f"{fn}: d = {d} exceeds {BILINEAR_MAX_D}")
+    U = _vec_arg(U, n, G.dtype, G.device, "U")
+    A = _vec_arg(A, m, G.dtype, G.device, "A")
+    U = U[:, None] if U.dim() == 1 else U
+    A = A[:, None] if A.dim() == 1 else A
+    if U.dim() != 2 or A.dim() != 2 or U.shape[1] != A.shape[1] or U.shape[1] < 1:
+        raise _ffi.DimensionMismatch(_ffi.EINVAL, f"DimensionMismatch: U has shape {tuple(U.shape)}, A {tuple(A.shape)}: equal column counts expected")
+    Ut, At = U.t().contiguous(), A.t().contiguous()
+    nvec = U.shape[1]
+    lib = _ffi.lib()
+    ctx = G._px.ctx.bind_stream()
+    py = None if G._py is G._px else G._py.handle
+    acc = torch.zeros(_ffi.MIXED_GRAD_NOUT, dtype=torch.float64)
+    for c0 in range(0, nvec, BILINEAR_MAX_NVEC):
+        nv = min(BILINEAR_MAX_NVEC, nvec - c0)
+        o = torch.empty(_ffi.MIXED_GRAD_NOUT, dtype=torch.float64, device=G.device)
+        _ffi.check(lib.covgram_bilinear_grad_mixed(ctx, C.byref(comp), G._px.handle, py, _ffi._P(Ut[c0:].data_ptr()), max(n, 1),
+                                                   _ffi._P(At[c0:].data_ptr()), max(m, 1), nv, C.cast(o.data_ptr(), C.POINTER(C.c_double)), _ffi.DEVICE))
+        acc += o.cpu()
+    out = acc.numpy()
+    value = math.fsum(c * out[t] for t, c in enumerate(K.mixed_term_coefficients(comp)))
+    return torch.tensor(value, dtype=torch.float64), torch.from_numpy(J @ out)
 
 
 def _sm_setup(fn, G, U, A):

@@ -872,7 +872,7 @@ _NO_PARAMETER = (ExponentiatedQuadratic, Exponential, Cauchy, MaternP, Matern, D
 def hyperparameters(k):
     """[(path, name, value)]: the leaves of the kernel expression `k` in a fixed order — depth first, arguments left to right, a
     wrapper's own parameter after its inner kernel's.  Leaves: Constant.c ("scale"), Lengthscale.l ("l"), RationalQuadratic.alpha,
-    GammaExponential.gamma, InverseMultiQuadratic.c ("c"), the entries of a Cosine's frequency vector ("mu"), and the entries of a
+    GammaExponential.gamma, InverseMultiQuadratic.c ("c"), NeuralNetwork.sigma ("sigma"), the entries of a Cosine's frequency vector ("mu"), and the entries of a
     diagonal ScaledInputKernel in the parametrisation the object stores: "l" for ARD(k, l) (lengthscales), "U" for
     ScaledInputKernel(k, U) (the multipliers).  `path` is the tuple of steps from the root (argument index of a Sum / Product, "k"
     into a wrapper, the dimension of an ARD or Cosine entry).  MaternP's p, Matern's nu
@@ -894,6 +894,8 @@ def hyperparameters(k):
         if type(k) in _OWN_PARAMETER:
             name = _OWN_PARAMETER[type(k)]
             return [(path, name, getattr(k, name))]
+        if isinstance(k, NeuralNetwork):
+            return [(path, "sigma", k.sigma)]
         if isinstance(k, _NO_PARAMETER):
             return []
         raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"hyperparameters: {type(k).__name__} is not a node of a parameter tree")
@@ -923,10 +925,144 @@ def with_hyperparameters(k, theta):
             inner = build(k.k)
             vals = np.array([next(it) for _ in range(len(k.U))])
             return ARD(inner, vals) if k.l is not None else ScaledInputKernel(inner, vals)
-        if type(k) in _OWN_PARAMETER:
+        if type(k) in _OWN_PARAMETER or isinstance(k, NeuralNetwork):
             return type(k)(next(it))
         return k
     return build(k)
+
+
+# ----------------------------------------------------------------------------------------------
+# hyper-parameter gradients of mixed-trait composites: the composite of covgram_bilinear_grad_mixed and the host chain rules
+# ----------------------------------------------------------------------------------------------
+MIXED_GRAD_NOUT = _ffi.MIXED_GRAD_NOUT
+_MIXED_Z0, _MIXED_P0 = _ffi.COMPOSITE_MAX_TERMS, _ffi.COMPOSITE_MAX_TERMS + _ffi.COMPOSITE_MAX_FACTORS
+
+
+def _provenance_form(k, path=(), scales=(), budget=64):
+    """Sum-of-products normal form of `k` that remembers where everything came from: a list of terms (consts, leaves), `consts` the tuple
+    of paths of the Constant leaves multiplied into the term (one entry per occurrence) and `leaves` a tuple of (path, leaf kernel,
+    ((path, l) of every Lengthscale node above it)), one entry per occurrence.  The walk is _normal_form's: Sum concatenates, Product
+    distributes, Power(k, p) multiplies p copies of k out — copies that share their paths, which is what lets them merge again."""
+    if isinstance(k, Constant):
+        return [((path,), ())]
+    if isinstance(k, Lengthscale):
+        return _provenance_form(k.k, path + ("k",), scales + ((path, k.l),), budget)
+    if isinstance(k, CosineKernel):
+        raise _Refusal(f"{type(k).__name__} belongs with the spectral mixtures (spectral_mixture_gradient)")
+    if isinstance(k, NeuralNetwork) or type(k) in _BASE:
+        if isinstance(k, Matern) and _simple_spec(k).family == _ffi.MATERN:
+            raise _Refusal(f"Matern(ν = {k.nu}) has no parameter derivatives on the device (half-integer ν: MaternP)")
+        if scales and not isinstance(k, IsotropicKernel):
+            raise _Refusal(f"Lengthscale over {type(k).__name__}: lengthscales apply to isotropic kernels only")
+        return [((), ((path, k, scales),))]
+    if isinstance(k, Sum):
+        out = [term for i, a in enumerate(k.args) for term in _provenance_form(a, path + (i,), scales, budget)]
+    elif isinstance(k, Product) or (isinstance(k, Power) and k.p >= 1):
+        parts = [(a, path + (i,)) for i, a in enumerate(k.args)] if isinstance(k, Product) else [(k.k, path + ("k",))] * k.p
+        out = [((), ())]
+        for a, pa in parts:
+            e = _provenance_form(a, pa, scales, budget)
+            out = [(c1 + c2, f1 + f2) for (c1, f1) in out for (c2, f2) in e]
+            if len(out) > budget:
+                break
+    else:
+        raise _Refusal(f"{type(k).__name__} is not a Sum / Product / Power / Constant / Lengthscale over the supported leaves")
+    if len(out) > budget:
+        raise _Refusal(f"the expression multiplies out to more than {budget} terms")
+    return out
+
+
+def _mixed_parameter_lower(k):
+    leaves = hyperparameters(k)
+    row_of = {(path, name): i for i, (path, name, _) in enumerate(leaves)}
+    value_of = {path: v for path, name, v in leaves if name == "scale"}
+    # merge by PROVENANCE: the copies of a leaf within a term into one factor with a power, the terms over the same (leaf, power) set into one
+    # term whose coefficient is a polynomial in the Constants: {sorted tuple of Constant paths: multiplicity}
+    merged = {}
+    for consts, occ in _provenance_form(k):
+        fac = {}
+        for path, leaf, scales in occ:
+            fac[path] = (leaf, scales, fac[path][2] + 1 if path in fac else 1)
+        key = frozenset((path, pw) for path, (_, _, pw) in fac.items())
+        mono = tuple(sorted(consts, key=repr))
+        if key not in merged:
+            merged[key] = ({}, fac)
+        merged[key][0][mono] = merged[key][0].get(mono, 0) + 1
+    terms = list(merged.values())
+    nfac = sum(max(len(fac), 1) for _, fac in terms)
+    if len(terms) > _ffi.COMPOSITE_MAX_TERMS or nfac > _ffi.COMPOSITE_MAX_FACTORS:
+        raise _Refusal(f"the normal form has {len(terms)} terms and {nfac} factors; the composite holds {_ffi.COMPOSITE_MAX_TERMS} terms "
+                       f"and {_ffi.COMPOSITE_MAX_FACTORS} factors")
+    J = np.zeros((len(leaves), MIXED_GRAD_NOUT))
+    lowered, fi = [], 0
+    for t, (poly, fac) in enumerate(terms):
+        c = 0.0
+        for mono, mult in poly.items():
+            c += mult * math.prod(value_of[p] for p in mono)
+            for i, p in enumerate(mono):                     # d/dconst of the monomial: leave ONE occurrence out (never a division)
+                J[row_of[(p, "scale")], t] += mult * math.prod(value_of[o] for j, o in enumerate(mono) if j != i)
+        specs = []
+        for path, (leaf, scales, pw) in fac.items():
+            s = _mixed_leaf_any(leaf)
+            s.power, s.scale = pw, 1.0
+            s.lengthscale = math.prod(l for _, l in scales)
+            specs.append(s)
+            for lpath, l in scales:
+                J[row_of[(lpath, "l")], _MIXED_Z0 + fi] += -2.0 / l
+            name = "sigma" if isinstance(leaf, NeuralNetwork) else _OWN_PARAMETER.get(type(leaf))
+            if name is not None:
+                J[row_of[(path, name)], _MIXED_P0 + fi] += 1.0
+            fi += 1
+        fi += 0 if fac else 1                                 # a term of constants only occupies one Constant factor
+        lowered.append((c, specs))
+    return _composite(lowered, 0), J
+
+
+def _mixed_leaf_any(leaf):
+    """The covgram_kernel of one leaf of the parameter lowering: NeuralNetwork(σ) as its own family, every compiled profile otherwise."""
+    if isinstance(leaf, NeuralNetwork):
+        return _mixed_leaf(leaf)
+    return _simple_spec(leaf)
+
+
+def require_mixed_parameter_spec(k):
+    """(composite, J) for covgram_bilinear_grad_mixed and its host chain rules: `composite` the covgram_kernel_composite of `k` in the
+    normal form of mixed_spec MERGED BY PROVENANCE — the p copies of a leaf under Power(k, p) become one factor of power p, terms over the
+    same leaves add their coefficients (Polynomial(2, σ) is Dot² + 2σ·Dot + σ²), but two different leaves that hold equal numbers stay
+    separate factors and terms, and no term is dropped because its coefficient is 0: every leaf keeps its own derivative.  `J` is the
+    dense len(hyperparameters(k)) × 24 float64 matrix of the chain rules: with `out` the 24 numbers of the device,
+        grad = J @ out,        value = Σ_t c_t out[t]   (c_t: the scale of term t's first factor in `composite`)
+    Rows: a Constant gets Σ_t ∂c_t/∂const · e_t (c_t is a polynomial in the Constants, differentiated here, never divided); a
+    Lengthscale node −(2/l) Σ e_{8+f} over the isotropic factors beneath it (nested lengthscales each with their own l); an own
+    parameter (RQ α, γ-exponential γ, IMQ c, NeuralNetwork σ) e_{16+f}.  Leaves: the isotropic profiles except Matern with real ν,
+    Dot, ExponentialDot, AsinDot, NeuralNetwork, Constant.  More than 8 terms or 8 factors, a CosineKernel, Matern(ν) and any other node
+    raise UnsupportedKernel naming what and why, before any device call."""
+    try:
+        if not isinstance(k, AbstractKernel):
+            raise _Refusal(f"{type(k).__name__} is not a kernel expression")
+        return _mixed_parameter_lower(k)
+    except _Refusal as why:
+        raise _ffi.UnsupportedKernel(_ffi.EUNSUPPORTED, f"hyper-parameter gradients of a mixed-trait composite ({type(k).__name__}): {why}") from None
+
+
+def mixed_term_coefficients(comp):
+    """[c_t]: the coefficient of every term of a covgram_kernel_composite — head scale times the scales of the term's factors."""
+    out, fi = [], 0
+    for t in range(comp.nterms):
+        c = comp.head.scale
+        for _ in range(comp.nfactors[t]):
+            c *= comp.factors[fi].scale
+            fi += 1
+        out.append(c)
+    return out
+
+
+def mixed_parameter_spec(k):
+    """require_mixed_parameter_spec(k), or None where it refuses."""
+    try:
+        return require_mixed_parameter_spec(k)
+    except _ffi.UnsupportedKernel:
+        return None
 
 
 # ----------------------------------------------------------------------------------------------

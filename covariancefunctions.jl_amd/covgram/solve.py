@@ -378,7 +378,7 @@ def inv_quad_logdet_gradient(A: LazyOperator, b: torch.Tensor, probes=16, maxite
     """(bᵀA⁻¹b, log det A, x = A⁻¹b, grad_inv_quad, grad_logdet, info): inv_quad_logdet and the derivatives of its two terms with respect
     to the hyper-parameters of the kernel, for A = G + σ²I or G + Diagonal(d) (as _split_shift splits it; G alone works too) with G the
     Gramian of gramian(k, x) — or the SpectralMixtureGramian of a spectral mixture, whose bilinear forms spectral_mixture_gradient
-    evaluates in place of bilinear_gradient.  ONE mbcg on [b | Z], exactly as inv_quad_logdet runs it, then with α = A⁻¹b and the probe solves A⁻¹z_t
+    evaluates in place of bilinear_gradient, or the MixedGramian of a mixed-trait Sum / Product, whose forms mixed_bilinear_gradient evaluates.  ONE mbcg on [b | Z], exactly as inv_quad_logdet runs it, then with α = A⁻¹b and the probe solves A⁻¹z_t
         grad_inv_quad = −αᵀ(∂G/∂θ)α,     grad_logdet ≈ (1/p) Σ_t (M⁻¹z_t)ᵀ(∂G/∂θ)(A⁻¹z_t)   (M⁻¹z = z without a preconditioner),
     both float64 CPU tensors in hyperparameters(k) order.  The negative log marginal likelihood ½ bᵀA⁻¹b + ½ log det A has the gradient
     ½ (grad_inv_quad + grad_logdet).  When the diagonal term is a scalar shift — every entry of the 1-D tensor equal — the derivative
@@ -387,10 +387,14 @@ def inv_quad_logdet_gradient(A: LazyOperator, b: torch.Tensor, probes=16, maxite
     pass: that is what gives the per-probe terms, info["grad_logdet_values"] (p × parameters), and from them
     info["grad_logdet_stderr"], the per-parameter standard error of grad_logdet.  The gradient of precond.logdet() is not part of
     grad_logdet: with a preconditioner that depends on θ the estimate is that of tr(A⁻¹∂A) all the same, since E[(M⁻¹z)zᵀ] = I for z ~ N(0, M)."""
-    from .gramian import Gramian, SpectralMixtureGramian, bilinear_gradient, spectral_mixture_gradient, _bilinear_plan
+    from .gramian import Gramian, MixedGramian, SpectralMixtureGramian, bilinear_gradient, mixed_bilinear_gradient, spectral_mixture_gradient, _bilinear_plan
+    from .kernels import require_mixed_parameter_spec
     G, diag = _split_shift(A)
     if type(G) is SpectralMixtureGramian:
         form_gradient = spectral_mixture_gradient
+    elif type(G) is MixedGramian:
+        lowered = require_mixed_parameter_spec(G.k)             # UnsupportedKernel by name, before the solve
+        form_gradient = lambda G, u, a: mixed_bilinear_gradient(G, u, a, _spec=lowered)
     elif type(G) is Gramian:
         form_gradient = bilinear_gradient
         _bilinear_plan(G.k)                                     # UnsupportedKernel by name, before the solve

@@ -152,7 +152,8 @@ int make_host_kernel(const covgram_kernel* k, int dtype, bool for_gradient, Host
 // The composite behind make_host_kernel (COMPOSITE_ONE_TRAIT: one trait over the head and every factor), or a mixed-trait composite (every
 // factor on its own trait, NeuralNetwork factors, tu_family = FAM_EXPR_DOT): that of covgram_grad_mvm_mixed (COMPOSITE_MIXED_GRADIENT: the
 // leaves without a jet refused) or that of covgram_mvm_mixed / covgram_matrix_mixed (COMPOSITE_MIXED_VALUES: every leaf phi_any evaluates).
-enum CompositeMode { COMPOSITE_ONE_TRAIT, COMPOSITE_MIXED_GRADIENT, COMPOSITE_MIXED_VALUES };
+// COMPOSITE_MIXED_PARAMETERS: that of covgram_bilinear_grad_mixed, every leaf of the values mode except Matern(nu).
+enum CompositeMode { COMPOSITE_ONE_TRAIT, COMPOSITE_MIXED_GRADIENT, COMPOSITE_MIXED_VALUES, COMPOSITE_MIXED_PARAMETERS };
 int make_composite_kernel(const covgram_kernel_composite* c, int dtype, CompositeMode mode, HostKernel* out);
 
 template <typename T>

@@ -45,13 +45,15 @@ static int make_simple_kernel(const covgram_kernel* k, int dtype, bool for_gradi
 // Composite: every factor keeps its own parameter block with gamma = 1/l (unfolded EQ); rows and columns stay unscaled.
 // mixed (the composites of covgram_grad_mvm_mixed, grad_mixed.hpp, and of covgram_mvm_mixed / covgram_matrix_mixed, mixed_mvm.hpp): the head's
 // trait binds nobody, every factor is validated on its OWN trait and a NeuralNetwork factor keeps sigma in fkp.param; the gradient mode
-// refuses the leaves without a jet in (x.y, |x|^2, |y|^2), the values mode takes every leaf.
+// refuses the leaves without a jet in (x.y, |x|^2, |y|^2), the values mode takes every leaf, the parameters mode (covgram_bilinear_grad_mixed,
+// mixed_bilin_grad.hip) every leaf but Matern(nu).
 int make_composite_kernel(const covgram_kernel_composite* c, int dtype, CompositeMode mode, HostKernel* out) {
     const covgram_kernel& h = c->head;
     const bool mixed = mode != COMPOSITE_ONE_TRAIT;
     if (mixed)
         CG_REQUIRE(h.family == COVGRAM_COMPOSITE, COVGRAM_EINVAL, "%s takes a covgram_kernel_composite (head.family = %d)",
-                   mode == COMPOSITE_MIXED_GRADIENT ? "covgram_grad_mvm_mixed" : "covgram_mvm_mixed / covgram_matrix_mixed", h.family);
+                   mode == COMPOSITE_MIXED_GRADIENT ? "covgram_grad_mvm_mixed"
+                   : mode == COMPOSITE_MIXED_PARAMETERS ? "covgram_bilinear_grad_mixed" : "covgram_mvm_mixed / covgram_matrix_mixed", h.family);
     else CG_REQUIRE(h.trait == COVGRAM_ISOTROPIC || h.trait == COVGRAM_DOTPRODUCT, COVGRAM_EINVAL, "composite: bad trait %d", h.trait);
     CG_REQUIRE(h.power == 1 && h.lengthscale == 1.0, COVGRAM_EINVAL, "composite head must have power == 1 and lengthscale == 1");
     CG_REQUIRE(c->nterms >= 1 && c->nterms <= EXPR_MAXT, COVGRAM_EUNSUPPORTED, "composite: %d terms (1..%d supported)", c->nterms, EXPR_MAXT);
@@ -87,6 +89,9 @@ int make_composite_kernel(const covgram_kernel_composite* c, int dtype, Composit
                                "mixed gradient kernel: the leaf %s%s is singular at zero distance and has no device path here", name,
                                fk.family == COVGRAM_MATERNP ? "(0)" : "");
                     CG_REQUIRE(fk.family != COVGRAM_MATERN, COVGRAM_EUNSUPPORTED, "mixed gradient kernel: the leaf %s(nu) has no device path here (MaternP does)", name);
+                } else if (mode == COMPOSITE_MIXED_PARAMETERS) {
+                    CG_REQUIRE(fk.family != COVGRAM_MATERN, COVGRAM_EUNSUPPORTED,
+                               "bilinear_grad_mixed: the leaf %s with real nu is not supported (half-integer nu: MaternP)", kFamilyNames[fk.family]);
                 } else if (!mixed) {
                     CG_REQUIRE(fk.trait == h.trait, COVGRAM_EINVAL, "composite: factor %d has trait %d, head has %d (GenericInput is not a device path)",
                                nin, fk.trait, h.trait);

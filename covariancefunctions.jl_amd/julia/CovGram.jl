@@ -291,6 +291,17 @@ function mixed_mul!(y::StridedVecOrMat{T}, spec::CComposite, X::Points, Y::Point
                 Float64(α), Float64(β), HOST))
     return y
 end
+# every hyper-parameter derivative of Σ_t U[:, t]' G A[:, t] of such a composite in one pass (covgram_bilinear_grad_mixed): the 24 Float64 of
+# include/covgram.h — out[t] per term without its coefficient, out[8 + f] = Σ W c_t z ∂ψ_f/∂z Π ψ_g, out[16 + f] = Σ W c_t ∂ψ_f/∂θ_f Π ψ_g
+const MIXED_GRAD_NOUT = 24           # COVGRAM_MIXED_GRAD_NOUT
+function mixed_bilinear_grad(spec::CComposite, X::Points, Y::Points, U::StridedVecOrMat{T}, A::StridedVecOrMat{T}) where {T <: DevFloat}
+    size(U, 2) == size(A, 2) || throw(DimensionMismatch("mixed_bilinear_grad: U is n × nvec, A is m × nvec"))
+    out = zeros(Float64, MIXED_GRAD_NOUT)
+    check(ccall((:covgram_bilinear_grad_mixed, libcovgram), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int32, Ptr{Float64}, Int32),
+                ctx(), Ref(spec), X.handle, Y.handle, U, max(stride(U, 2), size(U, 1)), A, max(stride(A, 2), size(A, 1)), Int32(size(U, 2)), out, HOST))
+    return out
+end
 function mixed_matrix!(out::StridedMatrix{T}, spec::CComposite, X::Points, Y::Points) where {T <: DevFloat}
     check(ccall((:covgram_matrix_mixed, libcovgram), Cint,
                 (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32),

@@ -770,6 +770,31 @@ int covgram_bilinear_grad_sm(covgram_sm* S, const covgram_points* X, const covgr
 int covgram_bilinear_input_grad_sm(covgram_sm* S, const covgram_points* X, const covgram_points* Y, const void* U, int64_t ldu, const void* A,
                                    int64_t lda, int32_t nvec, double* dX, int32_t loc);
 
+/* ---- Hyper-parameter gradients of the bilinear forms sum_t u_t' G a_t of a MIXED-TRAIT composite in ONE pass over the pairs
+ * (csrc/mixed_bilin_grad.hip), W = U A' as in covgram_bilinear_grad.  `k` is the composite of covgram_mvm_mixed: a Sum of terms
+ * c_t prod_f psi_f with psi_f = phi_f(z_f)^power_f on the argument of the factor's own trait (isotropic: z = r^2 / l_f^2 with r^2 by direct
+ * differences; dot product: p = x.y; COVGRAM_NEURALNETWORK: sigma in `param`), the coefficient c_t = head.scale times the scales of the
+ * term's factors.  `out` holds COVGRAM_MIXED_GRAD_NOUT = 24 DOUBLES whatever the points' dtype; f is the FLAT index of a factor in
+ * k->factors:
+ *     out[t]      = sum_ij W_ij prod_{f in t} psi_f                                t < nterms: term t WITHOUT c_t (constants only: sum W),
+ *                                                                                  so that the value is sum_t c_t out[t]
+ *     out[8 + f]  = sum_ij W_ij c_t z_f dpsi_f/dz_f prod_{g != f} psi_g            isotropic factors: d/dl_f = -(2 / l_f) out[8 + f]
+ *     out[16 + f] = sum_ij W_ij c_t dpsi_f/dtheta_f prod_{g != f} psi_g            theta: RQ alpha, gamma-exponential gamma, IMQ c,
+ *                                                                                  NeuralNetwork sigma
+ * and every other entry is written as exact 0.0.  The products over the other factors are multiplied up, never divided out.
+ * Leaves: EQ, Exponential, RQ, GammaExponential, Cauchy, IMQ, MaternP(p >= 0), each with its own lengthscale; Dot, ExponentialDot,
+ *   AsinDot; NeuralNetwork(sigma); Constant.  A COVGRAM_MATERN factor: COVGRAM_EUNSUPPORTED naming the leaf.
+ * U, A, ldu, lda, nvec (1 .. 32), d (1 .. 64), Y == NULL, loc and the status codes: as covgram_bilinear_grad.
+ * A pair whose scaled z_f is 0 (with Y == NULL the whole diagonal) adds exactly 0 to out[8 + f], also for the leaves whose derivative
+ *   is unbounded there, and the finite limit to out[16 + f]; rows and columns beyond the sets add nothing.
+ * A lane adds at most 128 pairs in the points' precision before the sum continues in fp64; partial sums are added in a fixed order, no
+ *   atomics: two calls with the same arguments agree bit for bit.  n m == 0 gives 24 zeros.  With loc == DEVICE the call is
+ *   stream-ordered and never synchronises.  Options: "time_kernels" brackets the pair kernel and its reduction; "jsplit" > 0 fixes the
+ *   number of column chunks. */
+#define COVGRAM_MIXED_GRAD_NOUT 24 /* COVGRAM_COMPOSITE_MAX_TERMS + 2 * COVGRAM_COMPOSITE_MAX_FACTORS */
+int covgram_bilinear_grad_mixed(covgram_ctx* ctx, const covgram_kernel_composite* k, const covgram_points* X, const covgram_points* Y, const void* U,
+                                int64_t ldu, const void* A, int64_t lda, int32_t nvec, double* out, int32_t loc);
+
 /* Test hook: the double-precision parameter block handed to the device kernels for `k`
  * (out45[0..8] = gamma, gamma^2, scale, param, c0, 2p+1, Taylor bound, d1, d2; then the MaternP tables
  * H_p, H_{p-1}, H_{p-2} and Taylor coefficients, 9 doubles each).  Needs no device. */
